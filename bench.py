@@ -2,7 +2,13 @@
 """Headline benchmark: archetypal-analysis outer iterations per second on the synthetic
 fp32 100000 x 4096, k = 32 problem (BASELINE.json configs[3]/[4]).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline line.  --full adds
+everything else the benchmark measures or checks, each with runs of its own: the estimators'
+loop, per-kernel timings and the roofline, QP statistics, the final cost in both forms, the CPU
+baseline with the parity checks against the oracle, and the float64 leg.  --dump-outputs DIR
+writes what the timed steps computed (see dump_outputs) as DIR/<name>.npy.
 
 A "step" is ONE outer iteration of the alternating solver on data already resident in
 HBM: dictionary SPG update (reference archetypal_analysis.py:324-341 with the
@@ -36,23 +42,44 @@ HBM_PEAK_GBS = 8000.0                 # MI355X_MICROARCH.md: HBM3E 8 TB/s
 MFMA_F32_PEAK_TFLOPS = 157.3          # MI355X_MICROARCH.md: dense fp32 matrix peak
 
 
-def synthetic_rows(lo, hi, n=N_SAMPLES, p=N_FEATURES, k=N_COMPONENTS):
+def synthetic_rows(lo, hi, n=N_SAMPLES, p=N_FEATURES, k=N_COMPONENTS, workers=None):
     """Rows [lo, hi) of the benchmark matrix X = Zt B + 0.05 noise (float32).  Archetypes
     B from RandomState(0); every BLOCK_ROWS-row block of (Zt, noise) from its own
-    RandomState(1000 + block), so the matrix does not depend on how it is sharded."""
+    RandomState(1000 + block), so the matrix does not depend on how it is sharded.
+
+    The random draws of the blocks run on `workers` threads (NumPy's generators release the
+    GIL; default: the CPUs of this process, at most 16); the product Zt B and the sum run on
+    the calling thread in block order, so the bits do not depend on the number of threads."""
+    from collections import deque
+    from concurrent.futures import ThreadPoolExecutor
     B = np.random.RandomState(0).standard_normal((k, p))
     out = np.empty((hi - lo, p), dtype=np.float32)
     b0, b1 = lo // BLOCK_ROWS, (hi + BLOCK_ROWS - 1) // BLOCK_ROWS
-    for blk in range(b0, b1):
+
+    def draws(blk):
         r0, r1 = blk * BLOCK_ROWS, min((blk + 1) * BLOCK_ROWS, n)
         rng = np.random.RandomState(1000 + blk)
         Zt = rng.uniform(size=(r1 - r0, k))
         Zt /= Zt.sum(axis=1, keepdims=True)
         Zt = Zt ** 4                                      # peaky weights: identifiable hull
         Zt /= Zt.sum(axis=1, keepdims=True)
-        rows = Zt.dot(B) + 0.05 * rng.standard_normal((r1 - r0, p))
+        return r0, r1, Zt, 0.05 * rng.standard_normal((r1 - r0, p))
+
+    def place(r0, r1, Zt, rows):
+        rows += Zt.dot(B)                                 # Zt B + 0.05 noise
         s0, s1 = max(lo, r0), min(hi, r1)
         out[s0 - lo:s1 - lo] = rows[s0 - r0:s1 - r0]
+
+    if workers is None:
+        workers = min(16, len(os.sched_getaffinity(0)))
+    with ThreadPoolExecutor(max(1, workers)) as pool:
+        pending = deque()                                 # bounded: at most 2 x workers blocks in memory
+        for blk in range(b0, b1):
+            pending.append(pool.submit(draws, blk))
+            if len(pending) > 2 * workers:
+                place(*pending.popleft().result())
+        while pending:
+            place(*pending.popleft().result())
     return out
 
 
@@ -64,6 +91,34 @@ def start_factors(n=N_SAMPLES, k=N_COMPONENTS):
     Z = rs.uniform(size=(n, k))
     Z /= Z.sum(axis=1, keepdims=True)
     return C, Z
+
+
+DUMP_BYTES = 64 << 20                  # --dump-outputs: at most this much in all
+
+
+def dump_outputs(dirname, ctx, costs, rank, world):
+    """What the timed path hands its caller, as float64 .npy files: `costs` (the costs after
+    the dictionary and the weights update of every timed step, as outer_iterations returns
+    them), and the factors after the last step, `dictionary` C (k x n) and `weights` Z (n x k).
+    Factors larger than DUMP_BYTES keep a fixed sample of the samples (RandomState(2), in
+    order; `sample_index` lists them).  Sharded runs gather the factors; rank 0 writes."""
+    if world > 1:
+        ctx.global_view = True                            # get_state gathers every rank's rows
+    C, Z, _ = ctx.get_state()
+    ctx.global_view = False
+    if rank != 0:
+        return
+    out = {"costs": np.asarray(costs, dtype=np.float64)}
+    n, k = Z.shape
+    room = DUMP_BYTES - out["costs"].nbytes - 4096        # 4096: the .npy headers
+    if 2 * k * n * 8 > room:
+        idx = np.sort(np.random.RandomState(2).choice(n, room // ((2 * k + 1) * 8), replace=False))
+        C, Z = C[:, idx], Z[idx]
+        out["sample_index"] = idx.astype(np.float64)
+    out["dictionary"], out["weights"] = C, Z
+    os.makedirs(dirname, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a, dtype=np.float64))
 
 
 def exchange_unique_id(rank, world, backend):
@@ -161,13 +216,18 @@ def main():
     ap.add_argument("--p", type=int, default=N_FEATURES)
     ap.add_argument("--k", type=int, default=N_COMPONENTS)
     ap.add_argument("--dtype", default="float32", choices=["float32", "float64"])
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also measure and check everything else (estimator loop, per-kernel "
+                         "timings and roofline, QP statistics, CPU baseline and parity, float64 leg)")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the costs of the timed steps and the factors after the last one as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline and the parity checks")
     # SURVEY.md 8(d) allows a row sample for the CPU baseline; 40 000 rows: from 32 768 rows per GPU on
     # the product runs the pass kernels it runs at full size, so `parity_on_sample` puts the TIMED
     # kernels (k_row_local_f32_dma, k_reduce_rows_f32<1,4>) against the oracle, not their short-shard siblings
     ap.add_argument("--cpu-sample", type=int, default=40000)
     ap.add_argument("--cpu-steps", type=int, default=3)
-    ap.add_argument("--no-f64", action="store_true", help="skip the float64 (reference dtype) leg")
+    ap.add_argument("--no-f64", action="store_true", help="with --full: skip the float64 (reference dtype) leg")
     ap.add_argument("--clock-warmup-ms", type=float, default=300.0,
                     help="run the two pass kernels on scratch operands this long before the W warm-up steps "
                          "(GPU clock ramp after the host-side data generation; 0: off)")
@@ -227,31 +287,35 @@ def main():
     elapsed = time.perf_counter() - t0                     # host has read the last cost: device idle
     elapsed = float(ctx.allreduce_host([elapsed], "max")[0])
 
-    # the loop the estimators run (aa_iterate: the same updates plus the device-side monotonicity
-    # check / stopping rule / conditional snapshot after every iteration, host polling every 8),
-    # timed on the same state: tolerance 0 never fires, so exactly `steps` iterations run
-    # (single rank only: the device loop has not run on more than one GPU yet, and nothing after
-    # the timed region may put a multi-GPU bench line at risk; tools/two_rank_check.py covers it)
-    elapsed_loop = None
-    if world == 1:
-        t0 = time.perf_counter()
-        _, st_loop = ctx.iterate(float(costs[-1]), args.steps, 0.0, "abs_delta_f", False, True, True, spg_kw, qp_kw)
-        elapsed_loop = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, ctx, costs, rank, world)
 
-    # dominant kernels, timed live with HIP events on the solver's stream: every launch of the
-    # two pass kernels inside 10 further outer iterations is bracketed by an event pair
-    # (in context, i.e. with the clocks and cache state the timed region has; a back-to-back
-    # loop of one kernel runs ~10 % slower)
-    ctx.gemm_timing(True)
-    ctx.outer_iterations(10, spg_kw, qp_kw)
-    ms_reduce, n_reduce, ms_local, n_local = ctx.gemm_timing(False)   # C X / D X / Z'X ; (CX) X' / X (X'Z)
-    pass_kernels = ctx.pass_kernels()
-    ms_probe = ctx.time_kernel(5, 10)                      # plain streaming read of X (best probe shape)
-    qp_stats = ctx.weights_update(**qp_kw)                 # one more QP pass for its statistics
-    recon = ctx.reconstruction_cost()
-    trace_cost = ctx.cost()
-    ms_reduce = float(ctx.allreduce_host([ms_reduce], "max")[0])
-    ms_local = float(ctx.allreduce_host([ms_local], "max")[0])
+    if args.full:
+        # the loop the estimators run (aa_iterate: the same updates plus the device-side monotonicity
+        # check / stopping rule / conditional snapshot after every iteration, host polling every 8),
+        # timed on the same state: tolerance 0 never fires, so exactly `steps` iterations run
+        # (single rank only: the device loop has not run on more than one GPU yet, and nothing after
+        # the timed region may put a multi-GPU bench line at risk; tools/two_rank_check.py covers it)
+        elapsed_loop = None
+        if world == 1:
+            t0 = time.perf_counter()
+            _, st_loop = ctx.iterate(float(costs[-1]), args.steps, 0.0, "abs_delta_f", False, True, True, spg_kw, qp_kw)
+            elapsed_loop = time.perf_counter() - t0
+
+        # dominant kernels, timed live with HIP events on the solver's stream: every launch of the
+        # two pass kernels inside 10 further outer iterations is bracketed by an event pair
+        # (in context, i.e. with the clocks and cache state the timed region has; a back-to-back
+        # loop of one kernel runs ~10 % slower)
+        ctx.gemm_timing(True)
+        ctx.outer_iterations(10, spg_kw, qp_kw)
+        ms_reduce, n_reduce, ms_local, n_local = ctx.gemm_timing(False)   # C X / D X / Z'X ; (CX) X' / X (X'Z)
+        pass_kernels = ctx.pass_kernels()
+        ms_probe = ctx.time_kernel(5, 10)                      # plain streaming read of X (best probe shape)
+        qp_stats = ctx.weights_update(**qp_kw)                 # one more QP pass for its statistics
+        recon = ctx.reconstruction_cost()
+        trace_cost = ctx.cost()
+        ms_reduce = float(ctx.allreduce_host([ms_reduce], "max")[0])
+        ms_local = float(ctx.allreduce_host([ms_local], "max")[0])
     ctx.close()
     if uid_path and rank == 0:
         try:
@@ -261,49 +325,6 @@ def main():
     if rank != 0:
         return
 
-    # HBM traffic of the two pass kernels from the PMC counters (rocprofv3 --pmc FETCH_SIZE /
-    # WRITE_SIZE in separate passes, tools/gpu_pmc.sh; FETCH_SIZE doubled as the MI355X guide
-    # prescribes for 16-B/lane streaming reads on gfx950).  Counters cannot be read from
-    # inside this process, so the last committed measurement of the same configuration is
-    # reported (profiles/pmc_traffic.json) -- null when there is none for this shape.
-    traffic = None
-    traffic_note = "no PMC measurement committed for this shape / these kernels"
-    try:
-        import hashlib
-        with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as fh:
-            pmc = json.load(fh)
-        with open(os.path.join(ROOT, "matrix-factorization-case-studies_amd", "csrc", "kernels_gemm.hip"), "rb") as fh:
-            sha = hashlib.sha1(fh.read()).hexdigest()
-        # only a measurement of THESE kernels (same source file) on THIS shape is reported
-        if (pmc.get("n"), pmc.get("p"), pmc.get("k"), pmc.get("n_gpus")) == (n, p, k, world) \
-                and pmc.get("dtype") == args.dtype and pmc.get("kernels_gemm_sha1") == sha:
-            traffic = 0.5 * (pmc["reduce_rows_bytes"] + pmc["row_local_bytes"])
-            traffic_note = ("profiles/pmc_traffic.json (kernels_gemm.hip sha1 %s): reduce_rows %.4g B, "
-                            "row_local %.4g B per launch" % (sha[:12], pmc["reduce_rows_bytes"],
-                                                             pmc["row_local_bytes"]))
-    except (OSError, ValueError, KeyError):
-        pass
-
-    # MFMA utilisation from the SQ counters (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE,
-    # tools/gpu_pmc_mfma.sh): busy cycles of the matrix pipes over SIMD-cycles of the dispatch; like
-    # the traffic counters it cannot be read from inside this process, so the committed
-    # measurement of this configuration is reported next to the flops/time figure
-    mfma_pmc = None
-    try:
-        with open(os.path.join(ROOT, "profiles", "pmc_mfma.json")) as fh:
-            pm = json.load(fh)["kernels"]
-        if (n, p, k, world, args.dtype) == (N_SAMPLES, N_FEATURES, N_COMPONENTS, 1, "float32"):
-            mfma_pmc = {name.split("<")[0]: round(v["mfma_busy_frac_of_simd_cycles"], 4)
-                        for name, v in pm.items() if "mfma_busy_frac_of_simd_cycles" in v}
-    except (OSError, ValueError, KeyError):
-        pass
-
-    es = 4 if args.dtype == "float32" else 8
-    n_loc = hi - lo
-    bytes_pass = float(n_loc) * p * es                     # algorithmic bytes of one pass over X
-    flops_pass = 2.0 * k * n_loc * p
-    ms_dom = 0.5 * (ms_reduce + ms_local)                  # 2 + 2 launches per outer iteration
-    achieved_gbs = bytes_pass / (ms_dom * 1e-3) / 1e9
     its = args.steps / elapsed
     flops_alg = 12.0 * k * n * p                           # 6 passes x 2knp
     result = {
@@ -323,35 +344,83 @@ def main():
                                "delta=0, dictionary spg max_iterations=1, default weights QP"
                                % (n, p, k, world),
                    "parallelism": "rows/%d" % world},
-        "roofline": {"bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                     "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
-                     "kernel": "%s / %s (mean of the two pass kernels, event pairs around every launch in 10 outer iterations)" % pass_kernels,
-                     "ms_reduce_rows": ms_reduce, "ms_row_local": ms_local,
-                     "launches_timed": [n_reduce, n_local],
-                     "ms_streaming_read_probe": ms_probe,
-                     "bytes_per_launch": bytes_pass, "flops_per_launch": flops_pass,
-                     "mfma_frac_of_kernel": flops_pass / (ms_dom * 1e-3) / (MFMA_F32_PEAK_TFLOPS * 1e12),
-                     "mfma_busy_frac_pmc": mfma_pmc,
-                     "mfma_busy_source": "profiles/pmc_mfma.json (SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), per kernel)"},
-        "mfma_frac_outer_iteration": flops_alg / world / (elapsed / args.steps) / (MFMA_F32_PEAK_TFLOPS * 1e12),
-        "cost": {"initial": cost0, "final_trace_form": trace_cost, "final_residual_form": recon,
-                 "after_each_update_last": [float(costs[-2]), float(costs[-1])]},
-        "estimator_loop": None if elapsed_loop is None else {
+    }
+    if args.full:
+        # HBM traffic of the two pass kernels from the PMC counters (rocprofv3 --pmc FETCH_SIZE /
+        # WRITE_SIZE in separate passes, tools/gpu_pmc.sh; FETCH_SIZE doubled as the MI355X guide
+        # prescribes for 16-B/lane streaming reads on gfx950).  Counters cannot be read from
+        # inside this process, so the last committed measurement of the same configuration is
+        # reported (profiles/pmc_traffic.json) -- null when there is none for this shape.
+        traffic = None
+        traffic_note = "no PMC measurement committed for this shape / these kernels"
+        try:
+            import hashlib
+            with open(os.path.join(ROOT, "profiles", "pmc_traffic.json")) as fh:
+                pmc = json.load(fh)
+            with open(os.path.join(ROOT, "matrix-factorization-case-studies_amd", "csrc", "kernels_gemm.hip"), "rb") as fh:
+                sha = hashlib.sha1(fh.read()).hexdigest()
+            # only a measurement of THESE kernels (same source file) on THIS shape is reported
+            if (pmc.get("n"), pmc.get("p"), pmc.get("k"), pmc.get("n_gpus")) == (n, p, k, world) \
+                    and pmc.get("dtype") == args.dtype and pmc.get("kernels_gemm_sha1") == sha:
+                traffic = 0.5 * (pmc["reduce_rows_bytes"] + pmc["row_local_bytes"])
+                traffic_note = ("profiles/pmc_traffic.json (kernels_gemm.hip sha1 %s): reduce_rows %.4g B, "
+                                "row_local %.4g B per launch" % (sha[:12], pmc["reduce_rows_bytes"],
+                                                                 pmc["row_local_bytes"]))
+        except (OSError, ValueError, KeyError):
+            pass
+
+        # MFMA utilisation from the SQ counters (rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES / GRBM_GUI_ACTIVE,
+        # tools/gpu_pmc_mfma.sh): busy cycles of the matrix pipes over SIMD-cycles of the dispatch; like
+        # the traffic counters it cannot be read from inside this process, so the committed
+        # measurement of this configuration is reported next to the flops/time figure
+        mfma_pmc = None
+        try:
+            with open(os.path.join(ROOT, "profiles", "pmc_mfma.json")) as fh:
+                pm = json.load(fh)["kernels"]
+            if (n, p, k, world, args.dtype) == (N_SAMPLES, N_FEATURES, N_COMPONENTS, 1, "float32"):
+                mfma_pmc = {name.split("<")[0]: round(v["mfma_busy_frac_of_simd_cycles"], 4)
+                            for name, v in pm.items() if "mfma_busy_frac_of_simd_cycles" in v}
+        except (OSError, ValueError, KeyError):
+            pass
+
+        es = 4 if args.dtype == "float32" else 8
+        n_loc = hi - lo
+        bytes_pass = float(n_loc) * p * es                     # algorithmic bytes of one pass over X
+        flops_pass = 2.0 * k * n_loc * p
+        ms_dom = 0.5 * (ms_reduce + ms_local)                  # 2 + 2 launches per outer iteration
+        achieved_gbs = bytes_pass / (ms_dom * 1e-3) / 1e9
+        result["roofline"] = {
+            "bound": "hbm", "achieved": achieved_gbs, "peak": HBM_PEAK_GBS, "unit": "GB/s",
+            "frac": achieved_gbs / HBM_PEAK_GBS, "traffic": traffic, "traffic_source": traffic_note,
+            "kernel": "%s / %s (mean of the two pass kernels, event pairs around every launch in 10 outer iterations)" % pass_kernels,
+            "ms_reduce_rows": ms_reduce, "ms_row_local": ms_local,
+            "launches_timed": [n_reduce, n_local],
+            "ms_streaming_read_probe": ms_probe,
+            "bytes_per_launch": bytes_pass, "flops_per_launch": flops_pass,
+            "mfma_frac_of_kernel": flops_pass / (ms_dom * 1e-3) / (MFMA_F32_PEAK_TFLOPS * 1e12),
+            "mfma_busy_frac_pmc": mfma_pmc,
+            "mfma_busy_source": "profiles/pmc_mfma.json (SQ_VALU_MFMA_BUSY_CYCLES / (GRBM_GUI_ACTIVE / 8 XCDs x 1024 SIMDs), per kernel)"}
+    result["mfma_frac_outer_iteration"] = flops_alg / world / (elapsed / args.steps) / (MFMA_F32_PEAK_TFLOPS * 1e12)
+    result["cost"] = {"initial": cost0}
+    if args.full:
+        result["cost"].update(final_trace_form=trace_cost, final_residual_form=recon)
+    result["cost"]["after_each_update_last"] = [float(costs[-2]), float(costs[-1])]
+    if args.full:
+        result["estimator_loop"] = None if elapsed_loop is None else {
             "value": args.steps / elapsed_loop, "unit": "it/s",
             "ms_per_step": 1e3 * elapsed_loop / args.steps,
             "what": "aa_iterate, the loop ArchetypalAnalysis.fit_transform runs (device-side "
                     "monotonicity check + stopping rule + snapshot per iteration), %d iterations"
-                    % (st_loop.n_iter + 1)},
-        "qp": {"mean_passes_per_sample": qp_stats.total_passes / float(n_loc),
-               "max_passes": qp_stats.max_passes, "samples_finished_by_wave_kernel": qp_stats.reserved},
-        "datagen_s": t_gen,
-        # the two pass kernels run on scratch operands for this long BEFORE the W warm-up steps (no solver state
-        # touched): the GPU leaves the host-side data generation with idle clocks, and 5 warm-up iterations are
-        # 10 ms.  Without it the same window reads ~1 % lower (profiles/round4_ab.txt, call 5f)
-        "clock_warmup_ms": args.clock_warmup_ms,
-    }
+                    % (st_loop.n_iter + 1)}
+        result["qp"] = {"mean_passes_per_sample": qp_stats.total_passes / float(n_loc),
+                        "max_passes": qp_stats.max_passes, "samples_finished_by_wave_kernel": qp_stats.reserved}
+    result["datagen_s"] = t_gen
+    # the two pass kernels run on scratch operands for this long BEFORE the W warm-up steps (no solver state
+    # touched): the GPU leaves the host-side data generation with idle clocks, and 5 warm-up iterations are
+    # 10 ms.  Without it the same window reads ~1 % lower (profiles/round4_ab.txt, experiment 5f)
+    result["clock_warmup_ms"] = args.clock_warmup_ms
 
-    if not args.no_cpu_baseline and world == 1:
+    if args.full and not args.no_cpu_baseline and world == 1:
         base = cpu_baseline(k, p, spg_kw, min(args.cpu_sample, n), args.cpu_steps)
         ns = min(args.cpu_sample, n)
         # the same sample through the HIP path for a like-for-like cost comparison
@@ -394,7 +463,7 @@ def main():
                     "and of the fp32 accumulation",
         }
         result["parity_converged"] = converged_parity(k, p, args.dtype, local_rank, spg_kw, qp_kw)
-    if world == 1 and args.dtype == "float32" and not args.no_f64:
+    if args.full and world == 1 and args.dtype == "float32" and not args.no_f64:
         # the reference dtype (the estimators' default) on the same workload: X as float64 (3.3 GB)
         Xd = X.astype(np.float64)
         with _backend.Context(dtype="float64", device=local_rank) as c4:

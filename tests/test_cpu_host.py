@@ -346,3 +346,64 @@ def test_restart_feed_draws_in_the_sequential_loops_order():
         bad.wait(1)
     with pytest.raises(KeyError):
         bad.join()
+
+
+def test_bench_rows_do_not_depend_on_threads_or_shards():
+    """bench.synthetic_rows draws its blocks on worker threads: the matrix is bit for bit the
+    serial block-by-block definition, whatever the thread count and the shard bounds."""
+    import bench
+    n, p, k, br = 2600, 48, 5, bench.BLOCK_ROWS
+    B = np.random.RandomState(0).standard_normal((k, p))
+    want = np.empty((n, p), dtype=np.float32)
+    for blk in range((n + br - 1) // br):
+        r0, r1 = blk * br, min((blk + 1) * br, n)
+        rng = np.random.RandomState(1000 + blk)
+        Zt = rng.uniform(size=(r1 - r0, k))
+        Zt /= Zt.sum(axis=1, keepdims=True)
+        Zt = Zt ** 4
+        Zt /= Zt.sum(axis=1, keepdims=True)
+        want[r0:r1] = Zt.dot(B) + 0.05 * rng.standard_normal((r1 - r0, p))
+    for workers in (1, 3, None):
+        assert bench.synthetic_rows(0, n, n, p, k, workers=workers).tobytes() == want.tobytes()
+    parts = [bench.synthetic_rows(lo, hi, n, p, k) for lo, hi in ((0, 777), (777, 1999), (1999, n))]
+    assert np.concatenate(parts).tobytes() == want.tobytes()
+
+
+def test_bench_dump_outputs(tmp_path, monkeypatch):
+    """--dump-outputs: float64 costs and factors as .npy files; factors over the budget keep a
+    fixed, ordered sample of the samples, listed in sample_index."""
+    import bench
+
+    class Ctx(object):
+        global_view = False
+
+        def __init__(self, n, k):
+            rs = np.random.RandomState(0)
+            self.C, self.Z = rs.uniform(size=(k, n)), rs.uniform(size=(n, k))
+
+        def get_state(self):
+            return self.C, self.Z, np.ones(self.C.shape[0])
+
+    ctx, costs = Ctx(1000, 4), np.linspace(2.0, 1.0, 6)
+    bench.dump_outputs(str(tmp_path / "all"), ctx, costs, 0, 1)
+    got = {f[:-4]: np.load(str(tmp_path / "all" / f)) for f in os.listdir(str(tmp_path / "all"))}
+    assert sorted(got) == ["costs", "dictionary", "weights"]
+    assert all(a.dtype == np.float64 for a in got.values())
+    assert np.array_equal(got["costs"], costs) and np.array_equal(got["dictionary"], ctx.C)
+    assert np.array_equal(got["weights"], ctx.Z)
+
+    monkeypatch.setattr(bench, "DUMP_BYTES", 40000)
+    for d in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / d), ctx, costs, 0, 1)
+    files = sorted(os.listdir(str(tmp_path / "a")))
+    assert files == ["costs.npy", "dictionary.npy", "sample_index.npy", "weights.npy"]
+    assert sum(os.path.getsize(str(tmp_path / "a" / f)) for f in files) <= 40000
+    idx = np.load(str(tmp_path / "a" / "sample_index.npy")).astype(int)
+    assert np.all(np.diff(idx) > 0)
+    assert np.array_equal(np.load(str(tmp_path / "a" / "weights.npy")), ctx.Z[idx])
+    assert np.array_equal(np.load(str(tmp_path / "a" / "dictionary.npy")), ctx.C[:, idx])
+    for f in files:
+        assert np.array_equal(np.load(str(tmp_path / "a" / f)), np.load(str(tmp_path / "b" / f)))
+
+    bench.dump_outputs(str(tmp_path / "other_rank"), ctx, costs, 1, 1)     # only rank 0 writes
+    assert not os.path.exists(str(tmp_path / "other_rank"))

@@ -1,18 +1,19 @@
 #!/bin/bash
-: "${GRAFT_REPO_ROOT:=$(cd "$(dirname "$0")/.." && pwd)}"; export GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 # scratch: HBM traffic counters for the two GEMM kernels (separate --pmc passes, as the
 # MI355X guide prescribes; no sys/hip trace domains together with --pmc)
-mkdir -p gpurun_out
+OUT=${OUT:-$ROOT/out}; mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd); export OUT
 cd /tmp && export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmc_$C -- python3 $GRAFT_REPO_ROOT/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-f64 > $GRAFT_REPO_ROOT/gpurun_out/pmc_$C.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmc_$C -- python3 $ROOT/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-f64 > $OUT/pmc_$C.log 2>&1
   echo "pmc $C exit=$?"
 done
-cd $GRAFT_REPO_ROOT
+cd $ROOT
 python3 - <<'PY'
-import csv, glob, collections
+import csv, glob, collections, os
+OUT = os.environ["OUT"]
 for C in ("FETCH_SIZE", "WRITE_SIZE"):
-    files = glob.glob("gpurun_out/pmc_%s/**/*counter_collection.csv" % C, recursive=True)
+    files = glob.glob(os.path.join(OUT, "pmc_%s/**/*counter_collection.csv" % C), recursive=True)
     agg = collections.defaultdict(list)
     for f in files:
         for r in csv.DictReader(open(f)):
@@ -36,6 +37,6 @@ for name, key in (("reduce_rows", "k_reduce_rows_f32"), ("row_local", "k_row_loc
     f, w = pick("FETCH_SIZE", key), pick("WRITE_SIZE", key)
     out[name + "_FETCH_SIZE_KB"], out[name + "_WRITE_SIZE_KB"] = f, w
     out[name + "_bytes"] = (2 * f + w) * 1024 if f is not None and w is not None else None
-json.dump(out, open("gpurun_out/pmc_traffic.json", "w"), indent=1)
+json.dump(out, open(os.path.join(OUT, "pmc_traffic.json"), "w"), indent=1)
 print(json.dumps(out, indent=1))
 PY

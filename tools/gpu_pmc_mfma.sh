@@ -1,31 +1,32 @@
 #!/bin/bash
-: "${GRAFT_REPO_ROOT:=$(cd "$(dirname "$0")/.." && pwd)}"; export GRAFT_REPO_ROOT
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 # MFMA-utilisation counters of the pass kernels and the QP kernels on the headline problem:
 # separate --pmc passes (SQ has 8 slots; GRBM is independent), program directly after `--`,
-# --kernel-trace only (no sys/hip trace domains together with --pmc).  Summary -> gpurun_out/pmc_mfma.json
-mkdir -p gpurun_out
+# --kernel-trace only (no sys/hip trace domains together with --pmc).  Summary -> $OUT/pmc_mfma.json (default: out/ in the repo root)
+OUT=${OUT:-$ROOT/out}; mkdir -p "$OUT" && OUT=$(cd "$OUT" && pwd); export OUT
 cd /tmp && export TMPDIR=/tmp
 i=0
 for C in "SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES SQ_WAVES SQ_WAVE_CYCLES GRBM_GUI_ACTIVE" \
          "SQ_INSTS_VALU_MFMA_MOPS_F32 SQ_INSTS_VALU_MFMA_MOPS_F64 SQ_INSTS_MFMA SQ_ACTIVE_INST_ANY SQ_WAIT_ANY SQ_WAIT_INST_ANY"; do
   i=$((i+1))
-  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $GRAFT_REPO_ROOT/gpurun_out/pmcmfma_$i -- python3 $GRAFT_REPO_ROOT/bench.py --steps 12 --warmup 5 --no-cpu-baseline --no-f64 > $GRAFT_REPO_ROOT/gpurun_out/pmcmfma_$i.log 2>&1
+  timeout -k 10 300 rocprofv3 --pmc $C --kernel-trace --output-format csv -d $OUT/pmcmfma_$i -- python3 $ROOT/bench.py --full --steps 12 --warmup 5 --no-cpu-baseline --no-f64 > $OUT/pmcmfma_$i.log 2>&1
   echo "pmc group $i ($C) exit=$?"
 done
-cd $GRAFT_REPO_ROOT
+cd $ROOT
 python3 - <<'PY'
-import csv, glob, collections, json
+import csv, glob, collections, json, os
+OUT = os.environ["OUT"]
 agg = collections.defaultdict(lambda: collections.defaultdict(list))
 dur = collections.defaultdict(list)
-for f in glob.glob("gpurun_out/pmcmfma_*/**/*counter_collection.csv", recursive=True):
+for f in glob.glob(os.path.join(OUT, "pmcmfma_*/**/*counter_collection.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"].split("(")[0].replace("void aa::", "").replace("aa::", "")
         agg[k][r["Counter_Name"]].append(float(r["Counter_Value"]))
-for f in glob.glob("gpurun_out/pmcmfma_1/**/*kernel_trace.csv", recursive=True):
+for f in glob.glob(os.path.join(OUT, "pmcmfma_1/**/*kernel_trace.csv"), recursive=True):
     for r in csv.DictReader(open(f)):
         k = r["Kernel_Name"].split("(")[0].replace("void aa::", "").replace("aa::", "")
         dur[k].append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
-out = {"source": "rocprofv3 --pmc (two passes, tools/gpu_pmc_mfma.sh) on bench.py --steps 12 --warmup 5, MI355X; counter values are per dispatch, "
+out = {"source": "rocprofv3 --pmc (two passes, tools/gpu_pmc_mfma.sh) on bench.py --full --steps 12 --warmup 5, MI355X; counter values are per dispatch, "
                  "summed over the chip by rocprofv3; durations from the kernel trace of the first pass (counter collection serialises and slows dispatches)",
        "simds": 1024, "kernels": {}}
 for k in sorted(agg):
@@ -43,5 +44,5 @@ for k in sorted(agg):
     print("==", k)
     for c, v in sorted(d.items()):
         print("   %-36s %18.4f" % (c, v))
-json.dump(out, open("gpurun_out/pmc_mfma.json", "w"), indent=1)
+json.dump(out, open(os.path.join(OUT, "pmc_mfma.json"), "w"), indent=1)
 PY
