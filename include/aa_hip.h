@@ -482,6 +482,31 @@ int aa_gpnh_weights_update(aa_ctx *ctx, const double *WtW, const aa_qp_params *p
  * without the penalty term (added on the host). */
 int aa_gpnh_residual_cost(aa_ctx *ctx, double *cost);
 
+/* ------------------------------------------------------------ KernelAA.transform */
+/* Weights of new samples y for a fitted kernel model (dictionary C, scale factors alpha, D = diag(alpha) C):
+ * the per-sample simplex QPs of ArchetypalAnalysis.transform (archetypal_analysis.py:1151-1199) in kernel
+ * form, A = D K D' and b_y = -D kappa(X_train, y).  The context's data matrix (aa_set_data, data form) holds
+ * what the linear terms are computed from, the weights go through aa_gpnh_set_factors (Z only) and
+ * aa_gpnh_weights_update (A), and the cost is aa_kernel_transform_cost.
+ *
+ * aa_set_rbf_reference: the implicit RBF kernel exp(-gamma ||y - x||^2).  The data matrix holds the new
+ *   samples Y (m x p, float64 context); XS (s x p, leading dimension ld) are the training rows in the support
+ *   of D, V (s x k, leading dimension ldv) = D' restricted to them.  Sizes the factor buffers for k
+ *   components (like aa_gpnh_set_factors).  Single rank, as aa_set_rbf_features.
+ * aa_rbf_cross: XW[r][i] = sum_c exp(-gamma max(|y_r|^2 + |x_c|^2 - 2 y_r.x_c, 0)) V[c][i] into the buffer
+ *   aa_gpnh_weights_update reads (b = -XW), never forming the m x s kernel: both products on the f64
+ *   matrix cores (csrc/kernels_gemm.hip: k_rbf_cross_mfma), column splits summed in a fixed order;
+ *   XW (nullable) receives a copy.
+ *   Replaces the kernel evaluation behind B = D kappa(X, Y) of the reference's transform (:1180-1190).
+ * aa_kernel_transform_cost: 0.5 sum_t (d_t + 2 w_t.b_t + w_t' A w_t) / m from the resident weights and
+ *   linear terms, A (k x k, host), d = kappa(y_t, y_t) (m values, host; NULL: 1 for every row, the RBF
+ *   kernel); one deterministic reduction.  The transform analogue of the kernel-form cost
+ *   (archetypal_analysis.py:200-217, :411-422), which aa_gpnh_residual_cost (data space) is not. */
+int aa_set_rbf_reference(aa_ctx *ctx, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
+                         double gamma);
+int aa_rbf_cross(aa_ctx *ctx, double *XW /* nullable: m x k copy of the result, row-major */);
+int aa_kernel_transform_cost(aa_ctx *ctx, const double *A, const double *diag, double *cost);
+
 /* ------------------------------------------------------------ the two passes, on their own */
 /* The two contractions against the resident matrix that every update is built from, callable
  * with caller-supplied small operands (unit tests of the pass kernels against X.dot(...) in
@@ -508,7 +533,9 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * 1 = row-local (CX X', X X'Z; n x k out), 2..5 = a plain streaming read of X (the read
  * bandwidth the memory system delivers; reference point for the roofline) with 4 / 8 / 16 / 8
  * loads in flight per thread on 4096 / 2048 / 1024 / 8192 blocks; 6 / 7 = the load pattern
- * of the row-local kernel alone, from the row-major matrix / from a tiled view of the same bytes.
+ * of the row-local kernel alone, from the row-major matrix / from a tiled view of the same bytes;
+ * 8 = K Z of the implicit RBF kernel (k_rbf_kv; a context after aa_set_rbf_features + aa_set_state),
+ * 9 = the cross RBF product of aa_rbf_cross (a context after aa_set_rbf_reference).
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

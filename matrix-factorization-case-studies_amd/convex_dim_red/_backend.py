@@ -141,6 +141,10 @@ _SIGNATURES = {
     "aa_gpnh_reduce": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp, _dp]),
     "aa_gpnh_weights_update": (ctypes.c_int, [_vp, _dp, ctypes.POINTER(QPParams), ctypes.POINTER(QPStats)]),
     "aa_gpnh_residual_cost": (ctypes.c_int, [_vp, _dp]),
+    "aa_set_rbf_reference": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _dp,
+                                            ctypes.c_long, ctypes.c_double]),
+    "aa_rbf_cross": (ctypes.c_int, [_vp, _dp]),
+    "aa_kernel_transform_cost": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
     "aa_gpnh_iterate": (ctypes.c_int, [_vp, ctypes.POINTER(GPNHParams), ctypes.POINTER(QPParams), _dp, _dp,
                                        ctypes.POINTER(IterStats)]),
     "aa_gpnh_get_dictionary": (ctypes.c_int, [_vp, _dp, ctypes.c_long]),
@@ -776,6 +780,34 @@ class Context(object):
     def gpnh_residual_cost(self):
         c = ctypes.c_double(0)
         _check(self.lib.aa_gpnh_residual_cost(self.h, ctypes.byref(c)))
+        return c.value
+
+    # -- KernelAA.transform (aa_set_rbf_reference / aa_rbf_cross / aa_kernel_transform_cost)
+    def set_rbf_reference(self, XS, V, gamma):
+        """Reference set of the cross RBF product for the resident rows Y (set_data): the training rows
+        ``XS`` (s x p) and ``V`` (s x k, = D' on them).  Sizes the factor buffers for k components."""
+        XS, V = _c64(XS), _c64(V)
+        if XS.ndim != 2 or V.ndim != 2 or V.shape[0] != XS.shape[0]:
+            raise ValueError("reference rows (s x p) and V (s x k) expected")
+        s, p = XS.shape
+        k = V.shape[1]
+        _check(self.lib.aa_set_rbf_reference(self.h, int(k), _ptr(XS), s, p, p, _ptr(V), k, float(gamma)))
+        self.k = k
+
+    def rbf_cross(self, fetch=False):
+        """XW = rbf(Y, XS) V into the QP's linear-term buffer (what gpnh_weights_update reads); with
+        ``fetch`` also returned (m x k)."""
+        out = np.empty((self.n, self.k)) if fetch else None
+        _check(self.lib.aa_rbf_cross(self.h, None if out is None else _ptr(out)))
+        return out
+
+    def kernel_transform_cost(self, A, diag=None):
+        """0.5 sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) / m from the resident weights and linear terms;
+        ``diag`` (m values) = kappa(y_t, y_t), None: 1 (RBF)."""
+        A = _c64(A)
+        d = None if diag is None else _c64(diag)
+        c = ctypes.c_double(0)
+        _check(self.lib.aa_kernel_transform_cost(self.h, _ptr(A), None if d is None else _ptr(d), ctypes.byref(c)))
         return c.value
 
     def spg_scalars(self):

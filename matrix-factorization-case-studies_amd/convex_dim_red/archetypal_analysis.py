@@ -22,6 +22,7 @@ import time
 import warnings
 
 import numpy as np
+from sklearn.exceptions import NotFittedError
 from sklearn.utils import check_array, check_random_state
 
 from . import _backend
@@ -415,6 +416,13 @@ def _iterate_aa(X, weights, dictionary, alpha, delta=0,
                                   tolerance, max_iterations, verbose, **kwargs)
 
 
+def _transform_hessian(ctx, alpha):
+    """A = D K D' (k x k, D = diag(alpha) C) of KernelAA.transform, from the device's C K C' of the final
+    dictionary (the Hessian of the weights QPs, archetypal_analysis.py:369-396)."""
+    alpha = np.asarray(alpha, dtype=np.float64)
+    return alpha[:, np.newaxis] * ctx.grams()[1] * alpha[np.newaxis, :]
+
+
 def _fit_on_data_matrix(self, data, linear_kernel, label, dictionary=None, weights=None, alpha=None,
                         update_dictionary=True, update_weights=True, update_scale_factors=True,
                         **kwargs):
@@ -488,6 +496,8 @@ def _fit_on_data_matrix(self, data, linear_kernel, label, dictionary=None, weigh
             self.max_iterations, self.verbose, **self._solver_kwargs())
         out = self._finish(result)
         self._cx = ctx.archetypes()
+        if linear_kernel:                        # KernelAA.transform: C K C' of the final dictionary
+            self._ckct = ctx.grams()[1]
     return out
 
 
@@ -593,6 +603,7 @@ class KernelAA(_BaseAA):
     def _kernel_aa(self, kernel, dictionary=None, weights=None, alpha=None,
                    update_dictionary=True, update_weights=True,
                    update_scale_factors=True, **kwargs):
+        self.__dict__.pop('_transform_state', None)      # a failed fit leaves nothing to transform with
         features = kwargs.pop('features', False)
         which = kwargs.pop('implicit_kernel', 'linear')
         gamma = kwargs.pop('gamma', None)
@@ -612,7 +623,13 @@ class KernelAA(_BaseAA):
             out = _fit_on_data_matrix(self, kernel, True, "Kernel AA", dictionary, weights, alpha,
                                       update_dictionary, update_weights, update_scale_factors,
                                       **kwargs)
-            self.__dict__.pop('_cx', None)
+            cx = self.__dict__.pop('_cx')
+            ckct = self.__dict__.pop('_ckct')
+            alpha_ = np.asarray(self.alpha, dtype=np.float64)
+            self._transform_state = dict(
+                form='linear', n_samples=kernel.shape[0], n_features=kernel.shape[1],
+                A=alpha_[:, np.newaxis] * ckct * alpha_[np.newaxis, :],
+                archetypes=alpha_[:, np.newaxis] * cx)                  # D X, k x p
             return out
         kernel = np.asarray(kernel)
         n_samples = kernel.shape[0]
@@ -634,11 +651,17 @@ class KernelAA(_BaseAA):
         self.dictionary = dictionary.copy()
         self.alpha = alpha.copy()
 
-        return self._finish(_iterate_kernel_aa(
-            kernel, self.weights, self.dictionary, self.alpha, delta=self.delta,
-            update_weights=update_weights, update_dictionary=update_dictionary,
-            update_scale_factors=update_scale_factors, tolerance=self.tolerance,
-            max_iterations=self.max_iterations, verbose=self.verbose, **self._solver_kwargs()))
+        # _iterate_kernel_aa, with the context kept open for the Hessian of transform()
+        with _backend.Context(dtype=np.float64) as ctx:
+            ctx.set_data(np.asarray(kernel, dtype=np.float64), form=_backend.FORM_KERNEL)
+            result = _iterate_on_device(
+                ctx, "Kernel AA", self.weights, self.dictionary, self.alpha, self.delta, update_weights,
+                update_dictionary, update_scale_factors, self.tolerance, self.max_iterations, self.verbose,
+                **self._solver_kwargs())
+            state = dict(form='kernel', n_samples=n_samples, A=_transform_hessian(ctx, result[2]))
+        out = self._finish(result)
+        self._transform_state = state
+        return out
 
     def _kernel_aa_rbf(self, X, gamma, dictionary, weights, alpha, update_dictionary, update_weights,
                        update_scale_factors, **kwargs):
@@ -685,10 +708,19 @@ class KernelAA(_BaseAA):
             self.weights = weights.copy()
             self.dictionary = dictionary.copy()
             self.alpha = alpha.copy()
-            return self._finish(_iterate_on_device(
+            result = _iterate_on_device(
                 ctx, "Kernel AA", self.weights, self.dictionary, self.alpha, self.delta, update_weights,
                 update_dictionary, update_scale_factors, self.tolerance, self.max_iterations, self.verbose,
-                **self._solver_kwargs()))
+                **self._solver_kwargs())
+            A = _transform_hessian(ctx, result[2])
+        out = self._finish(result)
+        # transform() needs the training rows in the support of D = diag(alpha) C only
+        D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
+        support = np.flatnonzero(np.any(D != 0, axis=0))
+        self._transform_state = dict(form='rbf', n_samples=n_samples, n_features=X.shape[1], A=A, gamma=float(gamma),
+                                     support=support, support_rows=np.ascontiguousarray(X[support]),
+                                     support_dictionary=np.ascontiguousarray(D[:, support]))
+        return out
 
     def fit_transform(self, data, dictionary=None, weights=None, alpha=None, **kwargs):
         """Factorise the kernel matrix ``data`` (n x n) and return the weights.  With
@@ -704,6 +736,70 @@ class KernelAA(_BaseAA):
     def fit(self, kernel, **kwargs):
         self.fit_transform(kernel, **kwargs)
         return self
+
+    def transform(self, data, diagonal=None):
+        """Weights of new samples for the fitted model, and their cost: the per-sample simplex QPs of
+        ``ArchetypalAnalysis.transform`` (reference :1151-1199, which writes them in kernel form) with
+        ``A = D K D'`` and ``b_y = -D kappa(X, y)``, ``D = diag(alpha) C``, from fresh random starting weights
+        (``self.random_state``), ``max_iterations`` SPG passes at most; the cost is
+        ``0.5 sum_y (kappa(y, y) + 2 w_y.b_y + w_y' A w_y) / m`` (the kernel-form cost, reference :200-217).
+
+        ``data`` is what the model was fitted on, for the new samples:
+          * an explicit kernel matrix: the cross kernel ``kappa(Y, X)`` (m x n_samples), with ``diagonal``
+            = ``kappa(y, y)`` (m values, required);
+          * ``features=True``: the new feature rows Y (m x n_features) -- linear kernel: ``Y (D X)'`` as in
+            ``ArchetypalAnalysis.transform`` and the cost ``0.5 ||Y - W D X||^2 / m``; ``kernel='rbf'``: the RBF
+            values against the training rows in the support of D on the f64 matrix cores (aa_rbf_cross),
+            the m x n cross kernel never formed.
+        Returns ``(weights, cost)``; ``weights`` is also stored in ``self.weights``."""
+        state = getattr(self, '_transform_state', None)
+        if state is None:
+            raise NotFittedError('This KernelAA instance is not fitted yet: call fit or fit_transform '
+                                 'before transform')
+        if isinstance(data, DeviceData):
+            raise TypeError('KernelAA.transform takes a host array, not DeviceData')
+        data = np.asarray(data, dtype=np.float64)
+        form = state['form']
+        width, what = ((state['n_samples'], 'the cross kernel kappa(Y, X_train): one column per training sample')
+                       if form == 'kernel' else
+                       (state['n_features'], 'the feature rows of the new samples'))
+        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != width:
+            raise ValueError('KernelAA.transform: expected %s, an (m, %d) array with m >= 1; got shape %s'
+                             % (what, width, data.shape))
+        m, k = data.shape[0], self.n_components
+        if form == 'kernel':
+            if diagonal is None:
+                raise ValueError('KernelAA.transform: `diagonal` (kappa(y, y) of the %d new samples) is required '
+                                 'for a model fitted on an explicit kernel matrix' % m)
+            diagonal = np.asarray(diagonal, dtype=np.float64)
+            if diagonal.shape != (m,):
+                raise ValueError('KernelAA.transform: `diagonal` must hold %d values (one per row of data); '
+                                 'got shape %s' % (m, diagonal.shape))
+        elif diagonal is not None:
+            raise ValueError('KernelAA.transform: `diagonal` is only taken for a model fitted on an explicit '
+                             'kernel matrix; with features=True it follows from the features')
+        kw = dict(self.weights_solver_kwargs)
+        kw['max_iterations'] = self.max_iterations            # reference :1194
+        A = state['A']
+        initial_weights = right_stochastic_matrix((m, k), random_state=self.random_state)
+        with _backend.Context(dtype=np.float64) as ctx:
+            ctx.set_data(data, form=_backend.FORM_DATA)
+            if form == 'kernel':
+                D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
+                ctx.gpnh_set_factors(k, W=D.T, Z=initial_weights)          # kappa(Y, X) D'
+            elif form == 'linear':
+                ctx.gpnh_set_factors(k, W=state['archetypes'].T, Z=initial_weights)   # Y (D X)'
+            else:
+                ctx.set_rbf_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'])
+                ctx.rbf_cross()                                             # kappa(Y, X_S) D_S'
+                ctx.gpnh_set_factors(k, Z=initial_weights)
+            ctx.gpnh_weights_update(A, **kw)
+            self.weights = ctx.gpnh_get_weights()
+            if form == 'linear':
+                cost = ctx.gpnh_residual_cost()                             # 0.5 ||Y - W D X||^2 / m
+            else:
+                cost = ctx.kernel_transform_cost(A, diagonal)
+        return self.weights, cost
 
 
 class ArchetypalAnalysis(_BaseAA):

@@ -254,6 +254,13 @@ struct Ctx {
     long feat_p = 0, feat_ld = 0;
     int implicit_kernel = 0;                   // 0: none; 1: K_ij = exp(-rbf_gamma ||x_i - x_j||^2), never formed (aa_set_rbf_features)
     double rbf_gamma = 0.0;
+    // KernelAA.transform on the implicit RBF kernel (aa_set_rbf_reference): the reference rows X_S
+    // [cross_s_pad][p_pad], their squared norms, V = D' on them [cross_s_pad][KP], the squared norms of the
+    // resident rows (also the linear kernel's diagonal), and the kernel-form cost's operands
+    DevBuf crossX, crossNorm, crossV, rowNorm, xformCost;
+    long cross_s = 0, cross_s_pad = 0;
+    int cross_k = 0;
+    double cross_gamma = 0.0;
     DevBuf fsScratch;                          // FurthestSum on the device: running sums, one distance column, state, alive flags
     bool qp_iters_valid = false;               // qpIters belongs to the current rows / state
     bool linear_kernel = false;                // data form, KernelAA conventions: K = X X' implicit (aa_set_linear_kernel)
@@ -350,6 +357,11 @@ int launch_row_sqnorm_sum(Ctx *c, double *trace_out_host);
 int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double *xj_host, double *d_host);
 int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall);   // out = K V for the implicit kernel (tall in, tall out)
 int launch_rbf_norms(Ctx *c);
+int launch_rbf_cross(Ctx *c);      // Gr (XW) = rbf(Y, X_S) V for the reference set of aa_set_rbf_reference
+int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double *nrm);   // nrm[r] = |F_r|^2
+// sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) over the resident rows (A: KP x KP device, d: device or null = 1;
+// part: (n + 255) / 256 + 1 doubles of scratch)
+int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_dev, double *part, double *out_host);
 int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n_ex, int extra_steps,
                         int *selected_host, int *tie_host);
 int launch_row_broadcast(Ctx *c, long j_local, bool own);

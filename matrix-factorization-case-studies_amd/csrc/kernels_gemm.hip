@@ -1461,6 +1461,137 @@ int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall)
     return AA_OK;
 }
 
+// ---------------------------------------------------------------------------
+// Cross RBF product of KernelAA.transform (archetypal_analysis.py:1151-1199 in kernel form):
+//   out[r][i] = sum_c exp(-gamma max(|y_r|^2 + |x_c|^2 - 2 y_r.x_c, 0)) V[c][i]
+// for the rows y_r of the resident data matrix Y ([n_pad][ld], the rows of the new samples) against a
+// reference set X_S ([s_pad][ld], the training rows in the support of the dictionary) and V = D'
+// restricted to them ([s_pad][KP]).  Both products run on v_mfma_f64_16x16x4_f64 (operand / result maps
+// at the head of the f64 section above).  A block owns 64 rows of Y, a wave 16 of them, and walks over
+// 64-column tiles of X_S:
+//   * S' = X_C Y_R' with the column index c as the MFMA row (A = X_C, B = Y_R, both staged through LDS
+//     in 32-feature chunks): lane l, reg q holds S[r = l&15][c = 16 mt + (l>>4) + 4 q];
+//   * that is the A-operand map of the second product (row r = l&15, contraction index c = l>>4 in the
+//     k-step (mt, q)), so E = exp(...) is formed in the registers it was computed in and
+//     out_R += E V_C is one MFMA per k-step and 16-component tile, with no LDS round trip of E.
+// Rows and columns are different sets: no diagonal shortcut.  Padding columns (c >= s) have zero rows
+// of V, padding rows (r >= m) are written as zeros.  grid.y splits the column tiles; the splits are
+// summed in a fixed order by k_sum_chunks, so the result is deterministic.
+// m s (2 p + 2 KP) flop (p rounded up to 4, s to 64, KP = 32 / 64).  The 32-feature chunks are read from
+// the zero-padded rows (ld = p rounded up to 128); the MFMAs stop at p rounded up to 4.
+// ---------------------------------------------------------------------------
+template <int KP>
+__global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict__ Y, const double *__restrict__ ny,
+                                                        const double *__restrict__ XS, const double *__restrict__ ns,
+                                                        const double *__restrict__ V, long ld, int pk, long m,
+                                                        long m_pad, long s_tiles, long tiles_per_split, double gamma,
+                                                        double *__restrict__ out)
+{
+    constexpr int NT = KP / 16, TC = 32, LS = 34, VS = KP + 16;
+    __shared__ __attribute__((aligned(16))) double ys[64 * LS];
+    __shared__ __attribute__((aligned(16))) double xs[64 * LS];
+    __shared__ __attribute__((aligned(16))) double vs[64 * VS];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int lc = lane & 15, lr = lane >> 4;
+    const long r0 = (long)blockIdx.x * 64;                // grid.x = m_pad / 64 exactly
+    const double nyr = ny[r0 + 16 * wave + lc];           // |y_r|^2 of the row this lane's S values belong to
+    f64x4g o[NT];
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt) o[nt] = (f64x4g){0.0, 0.0, 0.0, 0.0};
+
+    long ct0 = (long)blockIdx.y * tiles_per_split, ct1 = ct0 + tiles_per_split;
+    if (ct1 > s_tiles) ct1 = s_tiles;
+    for (long ct = ct0; ct < ct1; ++ct) {
+        const long c0 = ct * 64;
+        f64x4g sacc[4];
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt) sacc[mt] = (f64x4g){0.0, 0.0, 0.0, 0.0};
+        for (int q0 = 0; q0 < pk; q0 += TC) {
+            __syncthreads();                              // the previous chunk has been read
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int cid = t + 256 * e, row = cid >> 4, col = 2 * (cid & 15);
+                *reinterpret_cast<f64x2g *>(ys + row * LS + col) =
+                    *reinterpret_cast<const f64x2g *>(Y + (r0 + row) * ld + q0 + col);
+                *reinterpret_cast<f64x2g *>(xs + row * LS + col) =
+                    *reinterpret_cast<const f64x2g *>(XS + (c0 + row) * ld + q0 + col);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int s = 0; s < TC / 4; ++s) {
+                if (q0 + 4 * s >= pk) break;              // block-uniform: the last chunk ends at p rounded up to 4
+                const double b = ys[(16 * wave + lc) * LS + 4 * s + lr];
+#pragma unroll
+                for (int mt = 0; mt < 4; ++mt)
+                    sacc[mt] = __builtin_amdgcn_mfma_f64_16x16x4f64(xs[(16 * mt + lc) * LS + 4 * s + lr], b, sacc[mt],
+                                                                    0, 0, 0);
+            }
+        }
+        // the V rows of this tile (vs was last read before the barriers of the chunk loop)
+        for (int e = t; e < 64 * KP; e += 256) vs[(e / KP) * VS + e % KP] = V[(c0 + e / KP) * KP + e % KP];
+        __syncthreads();
+#pragma unroll
+        for (int mt = 0; mt < 4; ++mt)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) {
+                const int cl = 16 * mt + lr + 4 * q;      // column of the tile this lane's value belongs to
+                const double d2 = fmax(nyr + ns[c0 + cl] - 2.0 * sacc[mt][q], 0.0);
+                const double ev = exp(-gamma * d2);
+#pragma unroll
+                for (int nt = 0; nt < NT; ++nt)
+                    o[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ev, vs[cl * VS + 16 * nt + lc], o[nt], 0, 0, 0);
+            }
+    }
+    double *dst = out + (size_t)blockIdx.y * m_pad * KP;
+#pragma unroll
+    for (int nt = 0; nt < NT; ++nt)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const long r = r0 + 16 * wave + lr + 4 * q;
+            dst[r * KP + 16 * nt + lc] = r < m ? o[nt][q] : 0.0;
+        }
+}
+
+int launch_rbf_cross(Ctx *c)
+{
+    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->dtype == AA_F64, AA_ERR_STATE, "no reference set");
+    const long rtiles = c->n_pad / 64, stiles = c->cross_s_pad / 64;
+    long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU, as launch_implicit_kv
+    if (nsplit > stiles) nsplit = stiles;
+    if (nsplit < 1) nsplit = 1;
+    const long tps = (stiles + nsplit - 1) / nsplit;
+    nsplit = (stiles + tps - 1) / tps;
+    double *out_tall = c->Gr.as<double>();
+    double *dst = out_tall;
+    if (nsplit > 1) {
+        AA_CHECK(c->rlPartial.alloc((size_t)nsplit * c->n_pad * c->KP * sizeof(double)));
+        dst = c->rlPartial.as<double>();
+    }
+    const dim3 grid((unsigned)rtiles, (unsigned)nsplit);
+#define CROSS(KPV)                                                                                             \
+    hipLaunchKernelGGL(k_rbf_cross_mfma<KPV>, grid, dim3(256), 0, c->stream, (const double *)c->X.as<double>(),  \
+                       (const double *)c->rowNorm.as<double>(), (const double *)c->crossX.as<double>(),         \
+                       (const double *)c->crossNorm.as<double>(), (const double *)c->crossV.as<double>(),       \
+                       c->p_pad, (int)round_up(c->p, 4), c->n, c->n_pad, stiles, tps, c->cross_gamma, dst)
+    if (c->KP == 32) CROSS(32); else CROSS(64);
+#undef CROSS
+    if (nsplit > 1) {
+        const long elems = c->n_pad * c->KP;
+        hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
+                           (const double *)dst, elems, (int)nsplit, out_tall);
+    }
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double *nrm)
+{
+    hipLaunchKernelGGL(k_rbf_norms, dim3((unsigned)((rows + 255) / 256)), dim3(256), 0, c->stream, F, ld, (int)p, rows,
+                       nrm);
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
 // 0: operands straight from global memory; 1: X staged in wave-private LDS;
 // >= 2: block-tiled, B shared through LDS: 2 = 64-column tiles, 3 = 64 double-buffered,
 // 4 (default) = 128, 5 = 32 double-buffered, 6 = 128 double-buffered, 7 = 32;

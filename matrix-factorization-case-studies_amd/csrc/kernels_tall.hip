@@ -4172,4 +4172,64 @@ int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const
     return AA_OK;
 }
 
+// Kernel-form cost of KernelAA.transform (the per-sample terms of archetypal_analysis.py:411-422 with the
+// new samples' kernel values): one thread per row t, v_t = d_t - 2 z_t.XW_t + z_t' A z_t with b_t = -XW_t
+// the QP's linear term; the block's values are summed in a fixed tree, the block partials by
+// k_sum_partials in block order -- deterministic.  Padding components of Z, XW and A are zero.
+template <int KP>
+__global__ __launch_bounds__(256) void k_kernel_transform_cost(const double *__restrict__ Z,
+                                                               const double *__restrict__ XW,
+                                                               const double *__restrict__ A,
+                                                               const double *__restrict__ d, long n,
+                                                               double *__restrict__ partial)
+{
+    __shared__ double as[KP * KP];
+    __shared__ double red[256];
+    for (int e = threadIdx.x; e < KP * KP; e += 256) as[e] = A[e];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    double v = 0.0;
+    if (t < n) {
+        double z[KP];
+#pragma unroll
+        for (int i = 0; i < KP; ++i) z[i] = Z[t * KP + i];
+        double wb = 0.0, wAw = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < KP; ++i) {
+            double ai = 0.0;
+#pragma unroll
+            for (int j = 0; j < KP; ++j) ai = fma(as[i * KP + j], z[j], ai);
+            const double zi = Z[t * KP + i];
+            wAw = fma(zi, ai, wAw);
+            wb = fma(zi, XW[t * KP + i], wb);
+        }
+        v = (d ? d[t] : 1.0) - 2.0 * wb + wAw;
+    }
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) partial[blockIdx.x] = red[0];
+}
+
+int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_dev, double *part, double *out_host)
+{
+    const long nb = (c->n + 255) / 256;                  // part: nb + 1 doubles
+    if (c->KP == 32)
+        hipLaunchKernelGGL(k_kernel_transform_cost<32>, dim3((unsigned)nb), dim3(256), 0, c->stream,
+                           (const double *)c->Zt.as<double>(), (const double *)c->Gr.as<double>(), A_dev, d_dev, c->n,
+                           part);
+    else
+        hipLaunchKernelGGL(k_kernel_transform_cost<64>, dim3((unsigned)nb), dim3(256), 0, c->stream,
+                           (const double *)c->Zt.as<double>(), (const double *)c->Gr.as<double>(), A_dev, d_dev, c->n,
+                           part);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const double *)part, nb, part + nb);
+    AA_CHECK_HIP(hipGetLastError());
+    AA_CHECK_HIP(hipMemcpyAsync(out_host, part + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    return AA_OK;
+}
+
 }  // namespace aa

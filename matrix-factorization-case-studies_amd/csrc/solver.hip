@@ -743,6 +743,7 @@ int aa_ctx_destroy(aa_ctx *h)
     DevBuf *all[] = {&c->X, &c->Ct, &c->Zt, &c->Dt, &c->Gr, &c->Gn, &c->gk, &c->gn, &c->H, &c->tmpTall,
                      &c->P, &c->Q, &c->ZtX, &c->Pw, &c->Qw, &c->wideScratch, &c->partial, &c->rlPartial, &c->redPartial,
                      &c->gramOut, &c->gramState, &c->costDev, &c->costSlot, &c->redOut, &c->redGather, &c->listGather, &c->scalars, &c->proj, &c->projList, &c->projSegCnt, &c->Mdev, &c->alphaDev, &c->iterState, &c->snapC, &c->snapZ, &c->snapAlpha, &c->qpIters, &c->qpPerm, &c->fsScratch, &c->feat, &c->featNorm,
+                     &c->crossX, &c->crossNorm, &c->crossV, &c->rowNorm, &c->xformCost,
                      &c->qpStats, &c->qpLive, &c->slotCosts, &c->slotCounters, &c->slotStates, &c->slotCost0, &c->slotSnapP, &c->slotSaveP, &c->slotSaveGr, &c->tmpTall2, &c->redPartial2, &c->redOut2, &c->proj2, &c->projList2, &c->projSegCnt2};
     for (DevBuf *b : all) b->release();
     if (c->evFork2) (void)hipEventDestroy(c->evFork2);
@@ -860,6 +861,7 @@ int aa_set_data(aa_ctx *h, const void *X, int host_dtype, long n, long p, long l
     c->form = form;
     c->linear_kernel = false;
     c->implicit_kernel = 0;
+    c->cross_s = 0;                              // a reference set belongs to the rows it was set for
     c->n = n;
     c->p = p;
     c->n_pad = round_up(n, 128);
@@ -2147,6 +2149,77 @@ int aa_gpnh_residual_cost(aa_ctx *h, double *cost)
     return AA_OK;
 }
 
+// ------------------------------------------------------------------ KernelAA.transform
+int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
+                         double gamma)
+{
+    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
+               "aa_set_rbf_reference needs the new samples as a float64 data matrix (aa_set_data)");
+    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
+               s, p, c->p, ld, ldv);
+    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(ensure_problem(c, k));
+    const long s_pad = round_up(s, 64);
+    AA_CHECK(c->crossX.alloc((size_t)s_pad * c->p_pad * sizeof(double)));
+    AA_CHECK_HIP(ctx_memset(c, c->crossX.p, 0, c->crossX.bytes));
+    AA_CHECK_HIP(ctx_memcpy2d(c, c->crossX.p, (size_t)c->p_pad * sizeof(double), XS, (size_t)ld * sizeof(double),
+                              (size_t)p * sizeof(double), (size_t)s, hipMemcpyHostToDevice));
+    std::vector<double> v((size_t)s_pad * c->KP, 0.0);
+    for (long j = 0; j < s; ++j)
+        for (int i = 0; i < k; ++i) v[(size_t)j * c->KP + i] = V[j * ldv + i];
+    AA_CHECK(c->crossV.alloc(v.size() * sizeof(double)));
+    AA_CHECK_HIP(ctx_memcpy(c, c->crossV.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    AA_CHECK(c->crossNorm.alloc((size_t)s_pad * sizeof(double)));
+    AA_CHECK(launch_row_norms(c, c->crossX.as<double>(), c->p_pad, p, s_pad, c->crossNorm.as<double>()));
+    AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
+    AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, p, c->n_pad, c->rowNorm.as<double>()));
+    c->cross_s = s;
+    c->cross_s_pad = s_pad;
+    c->cross_k = k;
+    c->cross_gamma = gamma;
+    c->gpnh_valid = false;
+    return AA_OK;
+}
+
+int aa_rbf_cross(aa_ctx *h, double *XW)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE,
+               "aa_set_rbf_reference first");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(launch_rbf_cross(c));
+    c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
+    if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
+    return AA_OK;
+}
+
+int aa_kernel_transform_cost(aa_ctx *h, const double *A, const double *diag, double *cost)
+{
+    AA_REQUIRE(h && A && cost, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_state && c->gpnh_valid, AA_ERR_STATE, "weights and linear terms first");
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the kernel-form transform cost is single-rank");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    const size_t GS = (size_t)c->KP * c->KP;
+    const long nb = (c->n + 255) / 256;
+    AA_CHECK(c->xformCost.alloc((GS + (size_t)c->n_pad + (size_t)nb + 1) * sizeof(double)));
+    double *base = c->xformCost.as<double>();
+    std::vector<double> a(GS, 0.0);
+    for (int i = 0; i < c->k; ++i)
+        for (int j = 0; j < c->k; ++j) a[(size_t)i * c->KP + j] = A[(size_t)i * c->k + j];
+    AA_CHECK_HIP(ctx_memcpy(c, base, a.data(), GS * sizeof(double), hipMemcpyHostToDevice));
+    if (diag) AA_CHECK_HIP(ctx_memcpy(c, base + GS, diag, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice));
+    double s = 0.0;
+    AA_CHECK(launch_kernel_transform_cost(c, base, diag ? base + GS : nullptr, base + GS + c->n_pad, &s));
+    *cost = 0.5 * s / (double)c->n;
+    return AA_OK;
+}
+
 // ------------------------------------------------------------------ stateless ops
 int aa_simplex_project_rows(int device, const double *in, double *out, long rows, long cols)
 {
@@ -2337,8 +2410,14 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
 {
     AA_REQUIRE(h && ms_avg && reps >= 1, AA_ERR_ARG, "bad arguments");
     Ctx *c = &h->c;
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
-    AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
+    if (which == 8)
+        AA_REQUIRE(c->implicit_kernel && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit RBF kernel with state");
+    else if (which == 9)
+        AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE, "aa_time_kernel 9: aa_set_rbf_reference first");
+    else {
+        AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
+        AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
+    }
     AA_CHECK_HIP(hipSetDevice(c->device));
     hipEvent_t e0, e1;
     AA_CHECK_HIP(hipEventCreate(&e0));
@@ -2355,6 +2434,10 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                 rc = launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>());
             else if (which >= 2 && which <= 7)
                 rc = launch_stream_probe(c, which - 2);
+            else if (which == 8)
+                rc = launch_implicit_kv(c, c->Zt.as<double>(), c->H.as<double>());
+            else if (which == 9)
+                rc = launch_rbf_cross(c);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
