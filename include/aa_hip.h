@@ -294,6 +294,14 @@ int aa_weights_update(aa_ctx *ctx, const aa_qp_params *params, aa_qp_stats *stat
  * data first (aa_set_data / aa_share_data release the alias, never the owner's memory). */
 int aa_share_data(aa_ctx *ctx, const aa_ctx *owner);
 
+/* Cross-validation on resident data (bin/run_hadisst_aa.py:213-245: TimeSeriesSplit fits on growing
+ * prefixes of the training rows and transforms the block behind each, `training_data[train_index]` /
+ * `training_data[test_index]` being fresh host slices): rows [row0, row0 + n) of owner's resident DATA
+ * matrix become ctx's data matrix, exactly as after aa_set_data on the same values -- a device-to-device
+ * copy, the host is not involved.  Same device, same dtype, data form, both single rank, no implicit
+ * kernel.  Unlike aa_share_data the copy owns its memory: the owner may be destroyed afterwards. */
+int aa_set_data_rows(aa_ctx *ctx, const aa_ctx *owner, long row0, long n);
+
 /* KernelAA on the implicit linear kernel K = X X' (SURVEY 8(f4)): with `on` != 0 the resident
  * DATA matrix X (n x p) stands in for the n x n kernel matrix of _iterate_kernel_aa
  * (archetypal_analysis.py:399-531), which is never formed: every product with K runs as two
@@ -482,6 +490,17 @@ int aa_gpnh_weights_update(aa_ctx *ctx, const double *WtW, const aa_qp_params *p
  * without the penalty term (added on the host). */
 int aa_gpnh_residual_cost(aa_ctx *ctx, double *cost);
 
+/* Reconstruction scores of the drivers' validation branch (bin/run_hadisst_aa.py:235-241, :285-290,
+ * :325-366: inverse_transform, then mean_squared_error(data, reconstruction, squared=False) on the host):
+ * with R = X - Z W' on the resident matrix (never stored),
+ *   col_sse[q] = sum_t R[t][q]^2 (p values), row_sse[t] = sum_q R[t][q]^2 (n values), *sse = sum of all;
+ * every output is nullable, float64.  One pass over X with the product on the f64 matrix cores
+ * (csrc/kernels_tall.hip: k_residual_scores), float64 arithmetic in both context dtypes, fixed summation
+ * orders (two calls return the same bits).  Preconditions of aa_gpnh_residual_cost (data form,
+ * aa_gpnh_set_factors has set Wt and Z -- the state ArchetypalAnalysis.transform leaves behind), whose
+ * value is 0.5 * sse / n.  Single rank: a context with a communicator is refused with AA_ERR_ARG. */
+int aa_gpnh_residual_scores(aa_ctx *ctx, double *col_sse, double *row_sse, double *sse);
+
 /* ------------------------------------------------------------ KernelAA.transform */
 /* Weights of new samples y for a fitted kernel model (dictionary C, scale factors alpha, D = diag(alpha) C):
  * the per-sample simplex QPs of ArchetypalAnalysis.transform (archetypal_analysis.py:1151-1199) in kernel
@@ -535,7 +554,9 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * loads in flight per thread on 4096 / 2048 / 1024 / 8192 blocks; 6 / 7 = the load pattern
  * of the row-local kernel alone, from the row-major matrix / from a tiled view of the same bytes;
  * 8 = K Z of the implicit RBF kernel (k_rbf_kv; a context after aa_set_rbf_features + aa_set_state),
- * 9 = the cross RBF product of aa_rbf_cross (a context after aa_set_rbf_reference).
+ * 9 = the cross RBF product of aa_rbf_cross (a context after aa_set_rbf_reference),
+ * 10 = the scores pass of aa_gpnh_residual_scores, 11 = the residual pass of aa_gpnh_residual_cost (both
+ * without the copy to the host; a context after aa_gpnh_set_factors with dictionary and weights).
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

@@ -113,6 +113,7 @@ _SIGNATURES = {
     "aa_set_linear_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
     "aa_set_rbf_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double]),
     "aa_share_data": (ctypes.c_int, [_vp, _vp]),
+    "aa_set_data_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long]),
     "aa_set_data_weighted": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                             _dp, ctypes.c_long, ctypes.c_long,
                                             ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_long)]),
@@ -141,6 +142,7 @@ _SIGNATURES = {
     "aa_gpnh_reduce": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp, _dp]),
     "aa_gpnh_weights_update": (ctypes.c_int, [_vp, _dp, ctypes.POINTER(QPParams), ctypes.POINTER(QPStats)]),
     "aa_gpnh_residual_cost": (ctypes.c_int, [_vp, _dp]),
+    "aa_gpnh_residual_scores": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
     "aa_set_rbf_reference": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _dp,
                                             ctypes.c_long, ctypes.c_double]),
     "aa_rbf_cross": (ctypes.c_int, [_vp, _dp]),
@@ -363,9 +365,8 @@ class Context(object):
         self.lib = load_library()
         self.h = _vp()
         self.dtype_code = dtype_code(dtype)
-        _check(self.lib.aa_ctx_create(ctypes.byref(self.h),
-                                      device_index() if device is None else device,
-                                      self.dtype_code))
+        self.device = device_index() if device is None else device
+        _check(self.lib.aa_ctx_create(ctypes.byref(self.h), self.device, self.dtype_code))
         self.k = 0
         self.n = 0
         self.p = 0
@@ -464,6 +465,13 @@ class Context(object):
         _check(self.lib.aa_share_data(self.h, owner.h))
         self.n, self.p = owner.n, owner.p
         self._data_owner = owner                  # keeps the owner alive
+
+    def set_data_rows(self, owner, row0, n):
+        """Rows [row0, row0 + n) of ``owner``'s resident data matrix become this context's data matrix
+        (aa_set_data_rows): a device-to-device copy that owns its memory."""
+        _check(self.lib.aa_set_data_rows(self.h, owner.h, int(row0), int(n)))
+        self.n, self.p = int(n), owner.p
+        self.row_lo, self.n_global = 0, int(n)
 
     def set_rbf_features(self, X, gamma):
         """The implicit RBF kernel exp(-gamma ||x_i - x_j||^2) of the rows of X as this context's kernel
@@ -781,6 +789,17 @@ class Context(object):
         c = ctypes.c_double(0)
         _check(self.lib.aa_gpnh_residual_cost(self.h, ctypes.byref(c)))
         return c.value
+
+    def gpnh_residual_scores(self, columns=True, samples=True, total=True):
+        """Sums of squares of R = X - Z W' on the resident matrix in one pass (aa_gpnh_residual_scores):
+        ``(column_sse[p], sample_sse[n], sse)``; an output that is not asked for is None."""
+        col = np.empty(self.p) if columns else None
+        row = np.empty(self.n) if samples else None
+        tot = ctypes.c_double(0)
+        _check(self.lib.aa_gpnh_residual_scores(self.h, None if col is None else _ptr(col),
+                                                None if row is None else _ptr(row),
+                                                ctypes.byref(tot) if total else None))
+        return col, row, (tot.value if total else None)
 
     # -- KernelAA.transform (aa_set_rbf_reference / aa_rbf_cross / aa_kernel_transform_cost)
     def set_rbf_reference(self, XS, V, gamma):

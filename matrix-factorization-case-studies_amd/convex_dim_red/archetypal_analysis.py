@@ -31,6 +31,7 @@ from .preprocessing import DeviceData
 from .simplex_projection import simplex_project_rows  # noqa: F401  (reference re-export)
 from .spg import quad_simplex_spg, spg  # noqa: F401
 from .stochastic_matrices import right_stochastic_matrix
+from .validation import _residual_scores, _score_arguments
 from .validation_utils import check_array_shape, check_stochastic_matrix
 
 INTEGER_TYPES = (numbers.Integral, np.integer)
@@ -801,6 +802,24 @@ class KernelAA(_BaseAA):
                 cost = ctx.kernel_transform_cost(A, diagonal)
         return self.weights, cost
 
+    def score(self, data, weights=None):
+        """Reconstruction scores of ``data`` (m x n_features, host array or ``DeviceData``) for a model
+        fitted with ``features=True`` on the linear kernel, whose archetypes ``D X`` live in data space:
+        ``validation.Scores`` of ``data - weights (D X)`` (``weights`` None: the model's own, as after
+        ``fit_transform`` or ``transform``).  Models fitted on an explicit kernel matrix or on the RBF
+        kernel have no data-space residual (their cost is the kernel form's, see ``transform``)."""
+        state = getattr(self, '_transform_state', None)
+        if state is None:
+            raise NotFittedError('This KernelAA instance is not fitted yet: call fit or fit_transform '
+                                 'before score')
+        if state['form'] != 'linear':
+            raise ValueError("KernelAA.score: a model fitted on %s has no data-space residual; only "
+                             "features=True on the linear kernel has (archetypes D X)"
+                             % ('an explicit kernel matrix' if state['form'] == 'kernel' else 'the RBF kernel'))
+        data, weights = _score_arguments('KernelAA', data, state['n_features'], self.n_components, weights,
+                                         self.weights)
+        return _residual_scores(data, np.asarray(state['archetypes'], dtype=np.float64), weights, self.dtype)
+
 
 class ArchetypalAnalysis(_BaseAA):
     """Standard archetypal analysis ``min ||X - Z C X||_F^2`` (reference :913-1215).
@@ -869,6 +888,22 @@ class ArchetypalAnalysis(_BaseAA):
             self.weights = ctx.gpnh_get_weights()
             cost = ctx.gpnh_residual_cost()
         return self.weights, cost
+
+    def score(self, data, weights=None):
+        """Reconstruction scores of ``data`` (m x n_features, host array or ``DeviceData``) under the
+        fitted archetypes: ``validation.Scores`` of ``data - weights . archetypes`` -- the cost
+        ``transform`` returns, the drivers' RMSE (``mean_squared_error(data, inverse_transform(weights),
+        squared=False)``, bin/run_hadisst_aa.py:230-244), the pooled RMSE and the sums of squares per
+        feature and per sample -- from one pass over the matrix on the device (aa_gpnh_residual_scores);
+        the reconstruction is never formed.  ``weights`` (m x n_components) None: the model's own, as
+        after ``fit_transform`` or ``transform`` of the same rows.  No random numbers are drawn."""
+        if self.archetypes is None:
+            raise NotFittedError('This ArchetypalAnalysis instance is not fitted yet: call fit_transform '
+                                 'before score')
+        archetypes = np.asarray(self.archetypes, dtype=np.float64)
+        data, weights = _score_arguments('ArchetypalAnalysis', data, archetypes.shape[1], archetypes.shape[0],
+                                         weights, self.weights)
+        return _residual_scores(data, archetypes, weights, self.dtype)
 
     def inverse_transform(self, weights):
         return weights.dot(self.archetypes)

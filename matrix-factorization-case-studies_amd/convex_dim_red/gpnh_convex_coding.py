@@ -19,12 +19,14 @@ import time
 import warnings
 
 import numpy as np
+from sklearn.exceptions import NotFittedError
 from sklearn.utils import check_array, check_random_state
 
 from . import _backend
 from .furthest_sum import furthest_sum_from_columns
 from .preprocessing import DeviceData
 from .stochastic_matrices import right_stochastic_matrix
+from .validation import _residual_scores, _score_arguments
 from .validation_utils import check_unit_axis_sums, check_array_shape
 
 INTEGER_TYPES = (numbers.Integral, np.integer)
@@ -425,6 +427,20 @@ class GPNHConvexCoding(object):
         cost_ = self._gpnh_convex_coding(data=data, dictionary=self.dictionary,
                                          update_dictionary=False, update_weights=True)[0]
         return self.weights, cost_
+
+    def score(self, data, weights=None):
+        """Reconstruction scores of ``data`` (m x n_features, host array or ``DeviceData``) under the
+        fitted dictionary: ``validation.Scores`` of ``data - weights . dictionary'`` from one pass over
+        the matrix on the device (aa_gpnh_residual_scores).  ``cost`` is the data term of the GPNH cost
+        (reference :199-210); ``lambda_W`` x the penalty, which does not depend on the data, is not added.
+        ``weights`` None: the model's own.  No random numbers are drawn."""
+        if self.dictionary is None:
+            raise NotFittedError('This GPNHConvexCoding instance is not fitted yet: call fit or fit_transform '
+                                 'before score')
+        dictionary = np.asarray(self.dictionary, dtype=np.float64)            # n_features x k
+        data, weights = _score_arguments('GPNHConvexCoding', data, dictionary.shape[0], dictionary.shape[1],
+                                         weights, self.weights)
+        return _residual_scores(data, np.ascontiguousarray(dictionary.T), weights, self.dtype)
 
     def inverse_transform(self, weights):
         return weights.dot(self.dictionary.T)

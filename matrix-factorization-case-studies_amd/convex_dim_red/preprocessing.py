@@ -43,6 +43,36 @@ class DeviceData(object):
             raise RuntimeError("DeviceData has been closed")
         return _backend._Borrowed(self._ctx)
 
+    def rows(self, start, stop=None):
+        """Rows ``[start, stop)`` (or a ``slice`` with step 1) as a new ``DeviceData``: a device-to-device
+        copy (aa_set_data_rows) with a lifetime of its own -- what the drivers' cross-validation slices
+        on the host (``training_data[train_index]``, bin/run_hadisst_aa.py:217-218).  ``valid`` and
+        ``original_shape`` are inherited."""
+        n_total = self.shape[0]
+        if isinstance(start, slice):
+            if stop is not None:
+                raise ValueError("DeviceData.rows: a slice or (start, stop), not both")
+            if start.step not in (None, 1):
+                raise ValueError("DeviceData.rows: the block must be contiguous (slice step 1)")
+            lo = 0 if start.start is None else start.start
+            hi = n_total if start.stop is None else start.stop
+        else:
+            lo, hi = start, (n_total if stop is None else stop)
+        if not all(isinstance(v, (int, np.integer)) for v in (lo, hi)):
+            raise ValueError("DeviceData.rows: integer bounds expected; got %r, %r" % (lo, hi))
+        lo, hi = int(lo), int(hi)
+        if lo < 0 or hi > n_total or hi <= lo:
+            raise ValueError("DeviceData.rows: [%d, %d) is empty or outside the %d rows held" % (lo, hi, n_total))
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        ctx = _backend.Context(dtype=self.dtype, device=self._ctx.device)
+        try:
+            ctx.set_data_rows(self._ctx, lo, hi - lo)
+        except Exception:
+            ctx.close()
+            raise
+        return DeviceData(ctx, (hi - lo, self.shape[1]), self.valid, self.original_shape)
+
     def to_host(self):
         if self._host is None:
             self._host = self._ctx.get_data()

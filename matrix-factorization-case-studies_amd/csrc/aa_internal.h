@@ -261,6 +261,7 @@ struct Ctx {
     long cross_s = 0, cross_s_pad = 0;
     int cross_k = 0;
     double cross_gamma = 0.0;
+    DevBuf scoreScratch;                       // aa_gpnh_residual_scores: [slab][p_pad] | [split][n_pad] partials, the sums, the total
     DevBuf fsScratch;                          // FurthestSum on the device: running sums, one distance column, state, alive flags
     bool qp_iters_valid = false;               // qpIters belongs to the current rows / state
     bool linear_kernel = false;                // data form, KernelAA conventions: K = X X' implicit (aa_set_linear_kernel)
@@ -400,7 +401,10 @@ int side_end(Ctx *c);
 extern int g_proj_res_side, g_grad_side;
 int proj_poll_multirank(Ctx *c);   // multi-rank: read the deferred overflow flag / list lengths (host sync point)   // multi-rank: row j -> wideScratch on every rank
 int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const double *alpha_dev,
-                         double *out_host);
+                         double *out_host /* null: launches only (aa_time_kernel) */);
+// column / row / total sums of squares of X - Z W' (Z = Zt, W = P) in one pass on the f64 matrix cores;
+// host outputs nullable; fetch == false: launches only (aa_time_kernel)
+int launch_residual_scores(Ctx *c, double *col_host, double *row_host, double *sse_host, bool fetch = true);
 
 // ------------------------------------------------------------------ kernels_qp.hip
 // A_host (k x k) and bscale_host (k or null) come from the host, or -- A_host == nullptr --

@@ -4167,6 +4167,7 @@ int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, part, nb, out);
     AA_CHECK_HIP(hipGetLastError());
     if ((c->world > 1 || c->force_comm)) AA_CHECK(comm_allreduce(c, out, 1, 0));
+    if (!out_host) return AA_OK;                 // aa_time_kernel: the launches only
     AA_CHECK_HIP(hipMemcpyAsync(out_host, out, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     return AA_OK;
@@ -4228,6 +4229,205 @@ int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_de
     hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const double *)part, nb, part + nb);
     AA_CHECK_HIP(hipGetLastError());
     AA_CHECK_HIP(hipMemcpyAsync(out_host, part + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    return AA_OK;
+}
+
+// ---------------------------------------------------------------------------
+// Reconstruction scores (aa_gpnh_residual_scores; the drivers' inverse_transform + mean_squared_error,
+// bin/run_hadisst_aa.py:235-241, :285-290): R = X - Z W' on the resident matrix, never stored --
+//   col_sse[c] = sum_r R[r][c]^2,  row_sse[r] = sum_c R[r][c]^2,  sse = sum of all,
+// from ONE pass over X, the product on v_mfma_f64_16x16x4_f64 (A lane l = Z[row l&15][comp 4 s + (l>>4)],
+// B lane l = W[comp 4 s + (l>>4)][column of l&15], D lane l, reg q = row (l>>4) + 4 q, column of l&15).
+// A block owns a 64-row slab (a wave a 16-row tile, its Z fragments in registers for the whole kernel)
+// and the 64-column chunks of its column split (grid.y).  Per chunk: the wave's 16 x 64 piece of X goes
+// to registers in the accumulators' layout -- the four 16-column MFMA tiles take the columns
+// c0 + 32 u + 2 (l&15) + e, so a lane loads two adjacent elements and a row is read in 256-byte
+// (float: 128-byte) runs, as in k_reduce_rows_f64_mfma --, the W chunk (4 ceil(k/4) x 64 float64) is
+// staged through LDS once per block, ceil(k/4) MFMAs per tile form Z W', and the squared differences go
+// into float64 running sums: per lane and row over the chunks (row sums), per lane and column over the
+// 4 rows, then over the 4 row groups of the wave (xor shuffles) and the 4 waves (LDS, wave order) into
+// colPart[slab][column].  Rows >= n, columns >= p and components >= k are masked, so padding never
+// contributes whatever the buffers hold.  k_scores_finish adds the slab partials per column (16 interleaved groups of slabs, each in slab
+// order, then the groups in order) and the split partials per row in split order; k_sum_partials adds the column sums in a fixed
+// tree.  No atomics anywhere: two runs give the same bits.
+// Bounds: 1 x X bytes; 2 * 4 ceil(k/4) * n_pad * p_pad flop on the f64 matrix cores.
+// ---------------------------------------------------------------------------
+typedef double sc_f64x2 __attribute__((ext_vector_type(2)));
+typedef float sc_f32x2 __attribute__((ext_vector_type(2)));
+template <typename T> struct ScPair;
+template <> struct ScPair<double> { typedef sc_f64x2 type; };
+template <> struct ScPair<float> { typedef sc_f32x2 type; };
+
+template <typename T, int KP>
+__global__ __launch_bounds__(256) void k_residual_scores(const T *__restrict__ X, long ldx, long n, int p,
+                                                         int p_pad, const double *__restrict__ Z,
+                                                         const double *__restrict__ W, int k,
+                                                         int cols_per_split, long n_pad,
+                                                         double *__restrict__ colPart,
+                                                         double *__restrict__ rowPart)
+{
+    typedef typename ScPair<T>::type XPair;
+    constexpr int KS = KP / 4, LS = 66;               // LDS row stride: 64 columns + 2 (16-byte aligned rows)
+    __shared__ __attribute__((aligned(16))) double ws[KP * LS];
+    __shared__ double cpart[4][64];
+    const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
+    const int lc = lane & 15, lr = lane >> 4;
+    const long rw = (long)blockIdx.x * 64 + 16 * wave;    // grid.x = n_pad / 64 exactly
+    const int cb = (int)blockIdx.y * cols_per_split;
+    int ce = cb + cols_per_split;
+    if (ce > p_pad) ce = p_pad;
+    const int ksteps = (k + 3) >> 2;
+
+    double za[KS];
+#pragma unroll
+    for (int s = 0; s < KS; ++s) {
+        const int comp = 4 * s + lr;
+        za[s] = (comp < k && rw + lc < n) ? Z[(rw + lc) * KP + comp] : 0.0;
+    }
+    double rs[4] = {0.0, 0.0, 0.0, 0.0};
+
+    for (int c0 = cb; c0 < ce; c0 += 64) {
+        XPair xv[4][2];
+#pragma unroll
+        for (int q = 0; q < 4; ++q)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+                xv[q][u] = *reinterpret_cast<const XPair *>(X + (rw + lr + 4 * q) * ldx + c0 + 32 * u + 2 * lc);
+        // (the previous chunk's reads of ws ended before its second barrier)
+        for (int e = t; e < ksteps * 4 * 32; e += 256) {
+            const int row = e >> 5, col = 2 * (e & 31);
+            sc_f64x2 v = {0.0, 0.0};
+            if (row < k) v = *reinterpret_cast<const sc_f64x2 *>(W + (long)row * p_pad + c0 + col);
+            *reinterpret_cast<sc_f64x2 *>(ws + row * LS + col) = v;
+        }
+        __syncthreads();
+        f64x4 acc[2][2];
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) acc[u][e] = (f64x4){0.0, 0.0, 0.0, 0.0};
+#pragma unroll
+        for (int s = 0; s < KS; ++s) {
+            if (s < ksteps) {                         // block-uniform: components beyond k rounded up to 4 are skipped
+#pragma unroll
+                for (int u = 0; u < 2; ++u) {
+                    const sc_f64x2 b = *reinterpret_cast<const sc_f64x2 *>(ws + (4 * s + lr) * LS + 32 * u + 2 * lc);
+                    acc[u][0] = __builtin_amdgcn_mfma_f64_16x16x4f64(za[s], b[0], acc[u][0], 0, 0, 0);
+                    acc[u][1] = __builtin_amdgcn_mfma_f64_16x16x4f64(za[s], b[1], acc[u][1], 0, 0, 0);
+                }
+            }
+        }
+        double cs[2][2] = {{0.0, 0.0}, {0.0, 0.0}};
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            const bool row_ok = rw + lr + 4 * q < n;
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 2; ++e) {
+                    const bool ok = row_ok && c0 + 32 * u + 2 * lc + e < p;
+                    const double r = ok ? (double)xv[q][u][e] - acc[u][e][q] : 0.0;
+                    const double r2 = r * r;
+                    rs[q] += r2;
+                    cs[u][e] += r2;
+                }
+        }
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) {
+                double v = cs[u][e];
+                v += __shfl_xor(v, 16);
+                v += __shfl_xor(v, 32);
+                if (lr == 0) cpart[wave][32 * u + 2 * lc + e] = v;
+            }
+        __syncthreads();
+        if (t < 64)
+            colPart[(size_t)blockIdx.x * p_pad + c0 + t] = ((cpart[0][t] + cpart[1][t]) + cpart[2][t]) + cpart[3][t];
+        // (cpart is written again only behind the next chunk's first barrier)
+    }
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        double v = rs[q];
+        v += __shfl_xor(v, 1);
+        v += __shfl_xor(v, 2);
+        v += __shfl_xor(v, 4);
+        v += __shfl_xor(v, 8);
+        if (lc == 0) rowPart[(size_t)blockIdx.y * n_pad + rw + lr + 4 * q] = v;
+    }
+}
+
+// col[c] = sum over the slabs of colPart[slab][c], row[r] = sum over the column splits of rowPart[split][r],
+// both in a fixed order: the first p_pad / 16 blocks take 16 columns each -- thread (g, c) adds the slabs
+// g, g + 16, ... of its column in increasing order, the 16 group sums are added in group order --, the
+// others 256 rows each, splits in increasing order.  (One thread per column walking all slabs was a chain
+// of dependent-latency loads: 70 us for 350 slabs.)
+__global__ __launch_bounds__(256) void k_scores_finish(const double *__restrict__ colPart, long nslab, long p_pad,
+                                                       const double *__restrict__ rowPart, int nsplit, long n_pad,
+                                                       double *__restrict__ col, double *__restrict__ row)
+{
+    __shared__ double sm[16][17];
+    const long colBlocks = p_pad / 16;                  // p_pad is a multiple of 128
+    if ((long)blockIdx.x < colBlocks) {
+        const int cl = threadIdx.x & 15, g = threadIdx.x >> 4;
+        const long c = (long)blockIdx.x * 16 + cl;
+        double s = 0.0;
+#pragma unroll 8
+        for (long b = g; b < nslab; b += 16) s += colPart[(size_t)b * p_pad + c];
+        sm[g][cl] = s;
+        __syncthreads();
+        if (g == 0) {
+            double v = sm[0][cl];
+#pragma unroll
+            for (int q = 1; q < 16; ++q) v += sm[q][cl];
+            col[c] = v;
+        }
+        return;
+    }
+    const long r = ((long)blockIdx.x - colBlocks) * 256 + threadIdx.x;
+    if (r < n_pad) {
+        double s = 0.0;
+#pragma unroll 8
+        for (int j = 0; j < nsplit; ++j) s += rowPart[(size_t)j * n_pad + r];
+        row[r] = s;
+    }
+}
+
+int launch_residual_scores(Ctx *c, double *col_host, double *row_host, double *sse_host, bool fetch)
+{
+    const long nslab = c->n_pad / 64, chunks = c->p_pad / 64;       // n_pad, p_pad: multiples of 128
+    long nsplit = (1024 + nslab - 1) / nslab;                       // about 4 blocks per CU
+    if (nsplit > chunks) nsplit = chunks;
+    if (nsplit > 65535) nsplit = 65535;
+    const long cps = (chunks + nsplit - 1) / nsplit * 64;
+    nsplit = (c->p_pad + cps - 1) / cps;
+    const size_t nCol = (size_t)nslab * c->p_pad, nRow = (size_t)nsplit * c->n_pad;
+    AA_CHECK(c->scoreScratch.alloc((nCol + nRow + c->p_pad + c->n_pad + 1) * sizeof(double)));
+    double *colPart = c->scoreScratch.as<double>(), *rowPart = colPart + nCol, *col = rowPart + nRow,
+           *row = col + c->p_pad, *tot = row + c->n_pad;
+    const dim3 grid((unsigned)nslab, (unsigned)nsplit);
+#define SCORES(T, KPV)                                                                                   \
+    hipLaunchKernelGGL((k_residual_scores<T, KPV>), grid, dim3(256), 0, c->stream, (const T *)c->X.as<T>(),\
+                       c->p_pad, c->n, (int)c->p, (int)c->p_pad, (const double *)c->Zt.as<double>(),     \
+                       (const double *)c->P.as<double>(), c->k, (int)cps, c->n_pad, colPart, rowPart)
+    if (c->dtype == AA_F32) {
+        if (c->KP == 32) SCORES(float, 32); else SCORES(float, 64);
+    } else {
+        if (c->KP == 32) SCORES(double, 32); else SCORES(double, 64);
+    }
+#undef SCORES
+    hipLaunchKernelGGL(k_scores_finish, dim3((unsigned)(c->p_pad / 16 + (c->n_pad + 255) / 256)), dim3(256), 0, c->stream,
+                       (const double *)colPart, nslab, c->p_pad, (const double *)rowPart, (int)nsplit, c->n_pad, col,
+                       row);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const double *)col, c->p_pad, tot);
+    AA_CHECK_HIP(hipGetLastError());
+    if (!fetch) return AA_OK;                    // aa_time_kernel: the launches only
+    if (col_host)
+        AA_CHECK_HIP(hipMemcpyAsync(col_host, col, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (row_host)
+        AA_CHECK_HIP(hipMemcpyAsync(row_host, row, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (sse_host) AA_CHECK_HIP(hipMemcpyAsync(sse_host, tot, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     return AA_OK;
 }

@@ -743,7 +743,7 @@ int aa_ctx_destroy(aa_ctx *h)
     DevBuf *all[] = {&c->X, &c->Ct, &c->Zt, &c->Dt, &c->Gr, &c->Gn, &c->gk, &c->gn, &c->H, &c->tmpTall,
                      &c->P, &c->Q, &c->ZtX, &c->Pw, &c->Qw, &c->wideScratch, &c->partial, &c->rlPartial, &c->redPartial,
                      &c->gramOut, &c->gramState, &c->costDev, &c->costSlot, &c->redOut, &c->redGather, &c->listGather, &c->scalars, &c->proj, &c->projList, &c->projSegCnt, &c->Mdev, &c->alphaDev, &c->iterState, &c->snapC, &c->snapZ, &c->snapAlpha, &c->qpIters, &c->qpPerm, &c->fsScratch, &c->feat, &c->featNorm,
-                     &c->crossX, &c->crossNorm, &c->crossV, &c->rowNorm, &c->xformCost,
+                     &c->crossX, &c->crossNorm, &c->crossV, &c->rowNorm, &c->xformCost, &c->scoreScratch,
                      &c->qpStats, &c->qpLive, &c->slotCosts, &c->slotCounters, &c->slotStates, &c->slotCost0, &c->slotSnapP, &c->slotSaveP, &c->slotSaveGr, &c->tmpTall2, &c->redPartial2, &c->redOut2, &c->proj2, &c->projList2, &c->projSegCnt2};
     for (DevBuf *b : all) b->release();
     if (c->evFork2) (void)hipEventDestroy(c->evFork2);
@@ -934,6 +934,46 @@ int aa_share_data(aa_ctx *h, const aa_ctx *owner)
     c->have_trace = o->have_trace;
     c->trace = o->trace;
     c->k = 0;
+    c->KP = 0;
+    c->have_state = false;
+    c->grams_valid = false;
+    return AA_OK;
+}
+
+int aa_set_data_rows(aa_ctx *h, const aa_ctx *owner, long row0, long n)
+{
+    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_rows: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
+    AA_REQUIRE(o->device == c->device && o->dtype == c->dtype, AA_ERR_ARG,
+               "aa_set_data_rows: same device and same data type needed");
+    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
+               "aa_set_data_rows is single-rank");
+    AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
+               row0 + n, o->n);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    c->form = AA_FORM_DATA;
+    c->linear_kernel = false;
+    c->implicit_kernel = 0;
+    c->cross_s = 0;
+    c->n = n;
+    c->p = o->p;
+    c->n_pad = round_up(n, 128);
+    c->p_pad = o->p_pad;
+    c->n_global = n;
+    c->row_offset = 0;
+    c->have_data = false;
+    const size_t es = esize(c);
+    c->X.release();
+    AA_CHECK(c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * es));   // zero filled: the padding of aa_set_data
+    // rows are contiguous with the same leading dimension, their padding columns already zero
+    AA_CHECK_HIP(ctx_memcpy(c, c->X.p, reinterpret_cast<const unsigned char *>(o->X.p) + (size_t)row0 * o->p_pad * es,
+                            (size_t)n * c->p_pad * es, hipMemcpyDeviceToDevice));
+    c->have_data = true;
+    c->have_trace = false;
+    c->k = 0;   // forces (re)allocation of the factor buffers
     c->KP = 0;
     c->have_state = false;
     c->grams_valid = false;
@@ -2149,6 +2189,19 @@ int aa_gpnh_residual_cost(aa_ctx *h, double *cost)
     return AA_OK;
 }
 
+int aa_gpnh_residual_scores(aa_ctx *h, double *col_sse, double *row_sse, double *sse)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG,
+               "aa_gpnh_residual_scores is single-rank (the multi-rank form needs an all-reduce of the column sums)");
+    AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA, AA_ERR_STATE,
+               "aa_gpnh_residual_scores needs a stored data matrix (data form)");
+    AA_REQUIRE(c->have_state && c->gpnh_valid, AA_ERR_STATE, "set_factors first");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    return launch_residual_scores(c, col_sse, row_sse, sse);
+}
+
 // ------------------------------------------------------------------ KernelAA.transform
 int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
                          double gamma)
@@ -2414,6 +2467,10 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         AA_REQUIRE(c->implicit_kernel && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit RBF kernel with state");
     else if (which == 9)
         AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE, "aa_time_kernel 9: aa_set_rbf_reference first");
+    else if (which == 10 || which == 11)
+        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->have_state && c->gpnh_valid &&
+                       c->world == 1 && !c->force_comm,
+                   AA_ERR_STATE, "aa_time_kernel 10 / 11: aa_gpnh_set_factors (dictionary and weights) first, single rank");
     else {
         AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
         AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
@@ -2438,6 +2495,10 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                 rc = launch_implicit_kv(c, c->Zt.as<double>(), c->H.as<double>());
             else if (which == 9)
                 rc = launch_rbf_cross(c);
+            else if (which == 10)
+                rc = launch_residual_scores(c, nullptr, nullptr, nullptr, false);
+            else if (which == 11)
+                rc = launch_residual_cost(c, c->Zt.as<double>(), c->P.as<double>(), nullptr, nullptr);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
