@@ -90,7 +90,9 @@ typedef struct {
 const char *aa_last_error(void);
 int aa_version(void);
 int aa_device_count(int *count);
-/* Process-wide tuning knobs (results are identical up to rounding for every setting):
+/* Process-wide tuning knobs (results are identical up to rounding for every setting).  The names below
+ * are exactly the rows of the table behind aa_set_option (solver.hip); any other name is an error.
+ * A 0|1 knob takes any value and stores value != 0.
  *   "row_local_variant" -1..9  float32 row-local GEMM: -1 (default) chosen by size (from 32768 rows
  *                               per GPU: 9 for k <= 32, 8 for k <= 64; else 4), 0 direct, 1 wave-private
  *                               LDS, 2..7 block-tiled (2: 64-column tiles, 3: 64 double-buffered,
@@ -105,36 +107,24 @@ int aa_device_count(int *count);
  *                               0 = one fp32 chain per column chunk (round 2)
  *   "row_local_split"   0|1    1 (default): block-tiled kernels split the contraction over column
  *                               chunks when there are few row blocks
- *   "row_local_ring"    0|8..12 variant 9: LDS pieces in a wave's ring (default 8; 0: what LDS allows)
- *   "row_local_nt"      0|1    variant 9: non-temporal hint on the X stream (default 0)
  *   "f64_mfma"          0..3   float64 data: pass kernels on the f64 matrix cores (1, default: the
  *                               row-local one wave-streaming from 32768 rows per GPU, else
  *                               block-tiled; 2 / 3 force either) or on the f64 VALU (0)
- *   "row_local_waves"   0..16  waves per block of variant 8 (0: one block per CU)
  *   "proj_mode"         0|1    column simplex projection: 0 candidate lists, 1 iterative full
- *                               passes (also the fallback of a rank whose list overflows)
- *   "proj_small"        0|1    1 (default): columns of at most 8192 entries (single rank) find their
- *                               projection threshold in one kernel instead of four
+ *                               passes (also the fallback of a rank whose list overflows); only 0
+ *                               and 1 are accepted
+ *   "proj_small"        any    1 (default): columns of at most 8192 entries (single rank) find their
+ *                               projection threshold in one kernel, one block each, instead of four
+ *                               launches; 2: up to 16 384 entries (slower at 12 500); 0: never
  *   "proj_list_cap"     1..2048 multi-rank: most candidates per rank and column that travel in
  *                               the list all-reduce of a projection (effective: min(this,
  *                               2048 / ranks), so that the union fits the solver's LDS)
+ *   "proj_check"        0|1    multi-rank, 1: every list projection is checked for overflow at once (a
+ *                               host synchronisation per projection); default 0: the check is deferred
  *   "use_graph"         0|1    1: aa_outer_iterations captures two outer iterations in a
  *                               hipGraph and replays it (single rank, data form, one SPG
  *                               iteration per dictionary update, >= 8 iterations).  Default 0:
  *                               bit-identical and measured neutral on ROCm 7.2
- *   "qp_pass_cap"       >= 1   SPG passes a sample spends in the lane-per-sample QP kernel
- *                               before it moves to the wave-per-sample kernel
- *   "qp_refill_min"     1..64  idle lanes of a wave that trigger pulling new samples (default
- *                               64: a wave works off 64 samples at a time)
- *   "qp_sort"           0|1    1 (default): the lane-per-sample kernel takes the samples in the
- *                               order of their pass counts in the previous weights update,
- *                               longest first
- *   "qp_waves"          >= 1   most waves (64 samples each) the lane-per-sample kernel runs
- *                               at once; samples beyond that are pulled in as lanes free up
- *   "qp_overlap_tail"   0|1    1: the wave-per-sample kernel of the stragglers runs on a side
- *                               stream while Z'X is accumulated (float32 data); the rows it
- *                               changes enter Z'X as a rank-m correction.  Default 0: measured
- *                               neutral, the stragglers run 2x slower next to the GEMM
  *   "qp_mode"           0..4   0 (default), k <= 32: four lanes per sample in the matrix-core operand
  *                               layout (16 samples per wave) followed by the wave-per-sample kernel
  *                               for the stragglers; one lane per sample when max_iterations <= 4
@@ -142,43 +132,36 @@ int aa_device_count(int *count);
  *                               1: one wave per sample; 2: lane-per-sample + wave; 3: row kernel
  *                               (16 lanes per sample, samples run to completion); 4: four lanes per
  *                               sample + wave
+ *   "qp_pass_cap"       >= 1   SPG passes a sample spends in the lane-per-sample QP kernel
+ *                               before it moves to the wave-per-sample kernel
  *   "qp_quad_cap"       >= 0   SPG passes after which the four-lane kernel parks a sample for the
  *                               wave-per-sample kernel (default 0: 32 from 65 536 samples per GPU,
  *                               24 below)
- *   "qp_quad_waves"     >= 1   most waves (16 samples each) of the four-lane kernel (default 8192:
- *                               up to 131 072 samples every wave takes one batch)
- *   "qp_quad_occ"       2..4   register budget of the four-lane kernel in waves per SIMD (default 3)
- *   "qp_quad_refill"    1..16  idle sample slots of a wave that trigger a refill when a wave
- *                               takes several batches (default 16)
- *   "qp_row_waves"      >= 1   most waves the row kernel runs with (default 2048: 2 per SIMD)
- *   "qp_row_hot"        >= 0   SPG passes after which the wave of a sample raises its issue
- *                               priority (also when the previous update needed twice as many)
- *   "qp_row_chunk"      0..4096 0 (default): the row kernel's waves own fixed, interleaved slices of
- *                               the longest-first sample list (no queue); > 0: a global queue,
- *                               this many tickets per atomic
- *   "qp_row_long"       0..63  samples that needed at least this many passes in the previous
- *                               update are solved by the wave-per-sample kernel on a side stream,
- *                               concurrently with the row kernel (default 0: no side stream; measured
- *                               slower -- the two kernels take each other's issue slots)
- *   "qp_row_cap"        >= 1   passes after which the row kernel hands a sample to the
- *                               wave-per-sample kernel (default: never)
- *   "qp_tail_cap"       >= 0   with qp_overlap_tail: only samples beyond this many passes go to the
- *                               side stream (default 96; 0: all parked ones)
- *   "qp_wave_blocks"    1..8192 grid of the wave-per-sample continuation launch (default 1024)
+ *   "qp_sort"           0|1    1 (default): the QP kernels take the samples in the order of their
+ *                               pass counts in the previous weights update, longest first
+ *   "qp_overlap_tail"   0|1    1: the wave-per-sample kernel of the stragglers runs on a side
+ *                               stream while Z'X is accumulated (float32 data); the rows it
+ *                               changes enter Z'X as a rank-m correction.  Default 0: measured
+ *                               neutral, the stragglers run 2x slower next to the GEMM
  *   "qp_live"           0|1    1: the four-lane kernel hands parked samples to a consumer launch of the
  *                               wave-per-sample kernel that is resident beside it on CUs of its own
- *                               (bit-identical results; default 0: measured slower);
- *                               "qp_live_blocks" 1..128 = CUs given to the consumers (default 48),
- *                               "qp_live_occ" 2..4 = register budget of the four-lane kernel beside them
+ *                               (bit-identical results; default 0: measured slower)
  *   "proj_res_side"     0|1    1 (default): the residual projection of a one-iteration dictionary SPG
  *                               (convergence flags only) runs on a side stream beside the weights QP
- *   "outer_nosync"      0|1    measurement only (tools/interleave_probe.py): aa_outer_iterations called
- *                               WITHOUT a cost buffer returns with its work in flight
+ *   "grad_side"         0|1    1 (default): the tail of a one-iteration dictionary SPG (g_new, x += lambda d,
+ *                               BB stage, residual projection) on the side stream beside the weights QP
  *   "fuse_finalize"     0|1    1 (default): fewer, fatter launches in the dictionary update (set-up
  *                               kernel, scalar stages inside the finalize kernels, two-launch line
  *                               search, x update inside the gradient kernel)
- * Round 4 -- none of these changes a bit of any result (tests/test_gpu_longrun.py:
- * test_schedule_knobs_do_not_change_a_bit):
+ *   "pack_comm"         0|1    multi-rank, 1 (default): four small reductions ride in the tail of the
+ *                               all-reduce that follows them (10 collectives per outer iteration, not 14)
+ *   "outer_nosync"      0|1    measurement only (tools/interleave_probe.py): aa_outer_iterations called
+ *                               WITHOUT a cost buffer returns with its work in flight
+ * Changes results at rounding level (another summation order):
+ *   "pq_mfma"           0|1    1 (default): the two wide Grams of the line search on the f64 matrix cores;
+ *                               0: the LDS / VALU kernel
+ * None of the following six changes a bit of any result; tests/test_gpu_longrun.py:
+ * test_schedule_knobs_do_not_change_a_bit pins that:
  *   "qp_fused_order"    0|1    1 (default): the sample order of the NEXT weights update is formed by extra
  *                               blocks of this update's continuation launch instead of two launches in
  *                               front of the four-lane kernel
@@ -189,15 +172,7 @@ int aa_device_count(int *count);
  *                               block of their pass (write-through partials), not by a launch of their own
  *   "setup_in_grad"     0|1    1 (default): the dictionary update's set-up block is block 0 of its first
  *                               gradient launch
- *   "gram_side"         0|1    Z'Z of the refresh after a weights update on the side stream (default 0)
- *   "grad_side"         0|1    1 (default): the tail of a one-iteration dictionary SPG (g_new, x += lambda d,
- *                               BB stage, residual projection) on the side stream beside the weights QP
- *   "pack_comm"         0|1    multi-rank, 1 (default): four small reductions ride in the tail of the
- *                               all-reduce that follows them (10 collectives per outer iteration, not 14)
- *   "pq_mfma"           0|1    1 (default): the two wide Grams of the line search on the f64 matrix cores (another
- *                               summation order than the LDS / VALU kernel: results differ at rounding level)
- *   "proj_small"        0|1|2  1 (default): columns of <= 8192 rows are projected by one block each;
- *                               2: up to 16 384 rows (slower at 12 500) */
+ *   "gram_side"         0|1    Z'Z of the refresh after a weights update on the side stream (default 0) */
 int aa_set_option(const char *name, int value);
 
 /* -------------------------------------------- stateless ops (unit-test surface) */

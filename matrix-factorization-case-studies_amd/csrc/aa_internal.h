@@ -423,35 +423,15 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
 int launch_qp_tail_fixup(Ctx *c, double *Ztall);
 int launch_simplex_rows_generic(hipStream_t s, const double *in, double *out, long rows, long cols);
 
-extern int g_use_graph;           // solver.hip
-extern int g_proj_mode;           // kernels_tall.hip
-extern int g_proj_small, g_pq_blocks;           // kernels_tall.hip
-extern int g_fuse_finalize;       // kernels_tall.hip
-extern int g_proj_check_always;   // kernels_tall.hip
-extern int g_proj_list_cap;       // kernels_tall.hip
-extern int g_row_local_variant;   // kernels_gemm.hip
-extern int g_row_local_waves;     // kernels_gemm.hip
-extern int g_row_local_split, g_row_local_chunk, g_row_local_acc64, g_row_local_ring, g_row_local_nt, g_row_local_prio, g_row_local_early, g_row_local_reverse;     // kernels_gemm.hip
-extern int g_row_local_stagger;   // kernels_gemm.hip
-extern int g_reduce_rows_unroll;  // kernels_gemm.hip
-extern int g_f64_mfma;            // kernels_gemm.hip
-extern int g_reduce_rows_blocks;  // kernels_gemm.hip
-extern int g_qp_pass_cap;         // kernels_qp.hip
-extern int g_qp_mode;             // kernels_qp.hip
-extern int g_qp_wave_blocks;
-extern int g_qp_quad_waves, g_qp_quad_refill, g_qp_quad_cap, g_qp_quad_occ;   // kernels_qp.hip
-extern int g_qp_row_waves;        // kernels_qp.hip
-extern int g_qp_matvec;           // kernels_qp.hip
-extern int g_qp_row_hot;          // kernels_qp.hip
-extern int g_qp_row_chunk;        // kernels_qp.hip
-extern int g_qp_row_long;         // kernels_qp.hip
-extern int g_qp_row_cap;          // kernels_qp.hip
-extern int g_qp_refill_min;       // kernels_qp.hip
-extern int g_qp_waves;            // kernels_qp.hip
-extern int g_qp_sort;             // kernels_qp.hip
-extern int g_qp_profile;          // kernels_qp.hip
-extern int g_qp_wave_mem1, g_qp_fused_order, g_qp_wave_lazy, g_fin_in_last, g_gram_side, g_setup_in_grad, g_pack_comm, g_qp_quad_lazy, g_qp_wave_queue, g_pq_mfma;
-extern int g_qp_overlap_tail, g_qp_tail_cap, g_qp_live, g_qp_live_blocks, g_qp_live_occ;     // kernels_qp.hip
+// process-wide knobs (aa_set_option; the table is in solver.hip)
+extern int g_use_graph;                                                      // solver.hip
+extern int g_proj_mode, g_proj_small, g_proj_list_cap, g_proj_check_always;  // kernels_tall.hip
+extern int g_fuse_finalize, g_fin_in_last, g_gram_side, g_setup_in_grad;     // kernels_tall.hip
+extern int g_pack_comm, g_pq_mfma;                                           // kernels_tall.hip
+extern int g_row_local_variant, g_row_local_split, g_row_local_acc64, g_f64_mfma;   // kernels_gemm.hip
+extern int g_qp_pass_cap, g_qp_mode, g_qp_quad_cap, g_qp_sort;               // kernels_qp.hip
+extern int g_qp_fused_order, g_qp_wave_lazy, g_qp_quad_lazy;                 // kernels_qp.hip
+extern int g_qp_overlap_tail, g_qp_live;                                     // kernels_qp.hip
 
 // ------------------------------------------------------------------ comm.hip
 int comm_unique_id(void *id128);

@@ -738,7 +738,7 @@ template <int NCT, bool ACC64>
 __global__ __launch_bounds__(!ACC64 ? (NCT == 1 ? 1024 : 768) : (NCT == 1 ? 768 : 512)) void k_row_local_f32_ws(const float *__restrict__ X, long ldx,
                                                            const float *__restrict__ B, int p_pad,
                                                            double *__restrict__ out, long n_pad,
-                                                           int W, int stagger)
+                                                           int W)
 {
     constexpr int KP = 32 * NCT;
     constexpr int SB = 128, TC = 64;
@@ -838,20 +838,14 @@ __global__ __launch_bounds__(!ACC64 ? (NCT == 1 ? 1024 : 768) : (NCT == 1 ? 768 
         }
     };
 
-    // blocks start at different column slabs (cyclic order) so that the chip does not
-    // sweep one narrow column band of X -- one set of HBM channels -- at a time
     const int nslab = p_pad / SB;
-    const int s_first = (int)(((long)blockIdx.x * stagger) % nslab);
-    load_b(s_first * SB);
-    load_x(s_first * SB);
+    load_b(0);
+    load_x(0);
     store_b(0);
     __syncthreads();
     for (int s = 0; s < nslab; ++s) {
-        int scur = s_first + s;
-        if (scur >= nslab) scur -= nslab;
-        const int c0 = scur * SB;
-        int snext = s + 1 < nslab ? scur + 1 : scur;       // last slab: harmless reload
-        if (snext >= nslab) snext -= nslab;
+        const int c0 = s * SB;
+        const int snext = s + 1 < nslab ? s + 1 : s;       // last slab: harmless reload
         store_x();                                // wave-private: LDS is in order per wave
         load_x(c0 + TC);
         load_b(snext * SB);
@@ -886,7 +880,7 @@ __global__ __launch_bounds__(!ACC64 ? (NCT == 1 ? 1024 : 768) : (NCT == 1 ? 768 
 // in lane order (a "piece"), so the XOR swizzle that keeps the fragment reads conflict free sits
 // on the SOURCE address: lane l of a piece fetches the chunk whose swizzled position is l.
 //   X: a tile is 32 rows x 32 columns = 4 pieces (8 rows x 128 B each); every wave owns a RING of
-//      R pieces (R = 9..12, whatever 160 KB of LDS allow for W waves): tile t's pieces sit in ring
+//      R = 8 pieces (one tile in flight per wave; longer rings measured no faster): tile t's pieces sit in ring
 //      slots (4t + i) mod R, and R - 4 pieces of the tiles behind it are in flight while it is
 //      multiplied (the register-staged kernel keeps 8 KB per wave in flight).
 //   B: 64-column slabs (8 pieces: 4 components x 256 B each), two buffers shared by the block;
@@ -898,30 +892,24 @@ __global__ __launch_bounds__(!ACC64 ? (NCT == 1 ? 1024 : 768) : (NCT == 1 ? 768 
 // block barrier is the raw s_barrier (a __syncthreads would drain the DMAs in flight).  The fp32
 // accumulation chain ends after every tile (32 columns); the pieces are summed in float64 (see
 // k_row_local_f32_ws).
-template <bool NT>
+constexpr int ROW_LOCAL_RING = 8;   // X pieces in a wave's ring: two tiles, one of them in flight (the launcher sizes the LDS by it)
 __device__ __forceinline__ void dma16(const float *src, float *lds_uniform)
 {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
-                                     (__attribute__((address_space(3))) void *)lds_uniform, 16, 0, NT ? 2 : 0);
+                                     (__attribute__((address_space(3))) void *)lds_uniform, 16, 0, 0);
 }
 
-template <int R, bool NT, bool EARLY = false>
 __global__ __launch_bounds__(1024) void k_row_local_f32_dma(const float *__restrict__ X, long ldx,
                                                             const float *__restrict__ B, int p_pad,
-                                                            double *__restrict__ out, long n_pad, int W, int prio)
+                                                            double *__restrict__ out, long n_pad, int W)
 {
-    constexpr int KP = 32, SB = 64, TC = 32;
-    static_assert(R >= 8 && R <= 12, "ring of 8..12 pieces");
+    constexpr int KP = 32, SB = 64, TC = 32, R = ROW_LOCAL_RING;
     extern __shared__ __attribute__((aligned(16))) float dma_smem[];
     const int t = threadIdx.x, lane = t & 63;
     const int wave = __builtin_amdgcn_readfirstlane(t >> 6);
     float *bs = dma_smem;                                   // [2][KP * SB]
     float *xs = dma_smem + 2 * KP * SB + wave * (R * 256);  // R pieces of 256 floats, wave-private
-    // prio bit 1 (row_local_reverse): the row tiles from the last to the first -- the pass before this one
-    // (reduce-over-rows) walks the rows upwards and leaves the LAST rows in the memory-side cache, the pass
-    // after it starts at the first rows again
-    const long blk = (prio & 2) ? (long)(gridDim.x - 1 - blockIdx.x) : (long)blockIdx.x;
-    const long r0 = (blk * W + wave) * 32;
+    const long r0 = ((long)blockIdx.x * W + wave) * 32;
     const bool active = r0 < n_pad;
     const long r0c = active ? r0 : n_pad - 32;
     const int h = lane >> 5, j = lane & 31;
@@ -947,10 +935,10 @@ __global__ __launch_bounds__(1024) void k_row_local_f32_dma(const float *__restr
         const int i = issued & 3;
         const int slot = issued % R;
         const int off = i == 0 ? xoff[0] : (i == 1 ? xoff[1] : (i == 2 ? xoff[2] : xoff[3]));
-        dma16<NT>(gx + off + tl * TC, xs + slot * 256);
+        dma16(gx + off + tl * TC, xs + slot * 256);
         ++issued;
     };
-    auto issue_b = [&](int sl, int buf) { dma16<false>(B + boff + sl * SB, bs + buf * (KP * SB) + pb * 256); };
+    auto issue_b = [&](int sl, int buf) { dma16(B + boff + sl * SB, bs + buf * (KP * SB) + pb * 256); };
 
     // two fp32 accumulator sets, alternating tile by tile: the float64 flush of one set runs in the
     // shadow of the matrix instructions that fill the other (the flush needs the LAST instruction of
@@ -979,27 +967,6 @@ __global__ __launch_bounds__(1024) void k_row_local_f32_dma(const float *__restr
         slot = slot >= R ? slot - R : slot;
         const float *xb = xs + slot * 256 + (j & 7) * TC;
         const float *bb = bs + (s & 1) * (KP * SB) + j * SB;
-        if constexpr (EARLY) {
-            // all fragments of the tile into registers first (32 VGPRs), the LDS reads waited for, and
-            // the tile's four ring slots handed back to the DMA BEFORE the 16 matrix instructions run:
-            // 8 KB per wave in flight during the arithmetic instead of 4 (experiment, row_local_early)
-            f32x4 av[4], bvv[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                const int pcx = ((2 * q + h) ^ ((j >> 1) & 7)) << 2;
-                const int pcb = ((ts * 8 + 2 * q + h) ^ (j & 15)) << 2;
-                av[q] = *reinterpret_cast<const f32x4 *>(xb + pcx);
-                bvv[q] = *reinterpret_cast<const f32x4 *>(bb + pcb);
-            }
-            asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-#pragma unroll
-            for (int i = 0; i < 4; ++i) issue_piece();
-#pragma unroll
-            for (int q = 0; q < 4; ++q)
-#pragma unroll
-                for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(av[q][m], bvv[q][m], acc, 0, 0, 0);
-            return;
-        }
 #pragma unroll
         for (int q = 0; q < 4; ++q) {
             const int pcx = ((2 * q + h) ^ ((j >> 1) & 7)) << 2;
@@ -1010,12 +977,8 @@ __global__ __launch_bounds__(1024) void k_row_local_f32_dma(const float *__restr
             for (int m = 0; m < 4; ++m) acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m], bv[m], acc, 0, 0, 0);
         }
         // the four slots of this tile are free again (their reads were waited for before the MFMAs)
-        // prio: the wave that is about to put 4 KB in flight goes ahead of the waves that have
-        // matrix instructions and float64 sums to issue (experiment, aa_set_option row_local_prio)
-        if (prio & 1) __builtin_amdgcn_s_setprio(3);
 #pragma unroll
         for (int i = 0; i < 4; ++i) issue_piece();
-        if (prio & 1) __builtin_amdgcn_s_setprio(0);
     };
     auto flush = [&](f32x16 &acc) {
 #pragma unroll
@@ -1235,13 +1198,9 @@ int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *out
 #define RRL(NCTV, UV)                                                                         \
     hipLaunchKernelGGL((k_reduce_rows_f32<NCTV, UV>), grid, block, 0, c->stream, c->X.as<float>(), \
                        c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part)
-        if (c->KP == 32) {
-            if (g_reduce_rows_unroll == 8) RRL(1, 8);
-            else RRL(1, 4);
-        } else {
-            RRL(2, 4);
-        }
-        PASS_NAME(0, "k_reduce_rows_f32<%d,%d>", c->KP / 32, (c->KP == 32 && g_reduce_rows_unroll == 8) ? 8 : 4);
+        if (c->KP == 32) RRL(1, 4);
+        else RRL(2, 4);
+        PASS_NAME(0, "k_reduce_rows_f32<%d,4>", c->KP / 32);
 #undef RRL
     } else {
         dim3 grid((unsigned)((c->p_pad + 255) / 256), (unsigned)c->nslab);
@@ -1601,22 +1560,11 @@ int g_row_local_variant = -1;   // -1: by size (wave-streaming from 32768 rows p
 int g_f64_mfma = 1;            // float64 data: pass kernels on the f64 matrix cores (0: f64 VALU;
                                // row-local: 1 = wave-streaming from 32768 rows, else block-tiled;
                                // 2 / 3 = always wave-streaming / always block-tiled)
-int g_reduce_rows_unroll = 4;  // row pairs per software-pipeline half step (4 or 8; k <= 32)
-int g_reduce_rows_blocks = 512; // target block count of the reduce-over-rows kernel
-int g_row_local_stagger = 0;   // variant 8: column-slab offset between consecutive blocks
-int g_row_local_waves = 0;     // variant 8: waves per block (0 = one block per CU)
 int g_row_local_acc64 = 1;     // float32 row-local kernels: cut the fp32 accumulation chain every 32 columns and sum the
                                // pieces in float64 -- 0: never (row_local_variant 8 for large shards), 1: in the
                                // block-tiled kernel and, for large shards with k <= 32, through the LDS-DMA kernel
                                // (variant 9), 2: in the register-staged wave-streaming kernel too (k > 32; costs
                                // it a wave per SIMD: 0.31 -> 0.6 ms)
-int g_row_local_ring = 8;      // LDS-DMA kernel: pieces in a wave's ring (8: one tile in flight per wave -- measured
-                               // fastest, 0.376 ms back to back against 0.388 at 11; 0: what LDS allows)
-int g_row_local_nt = 0;        // LDS-DMA kernel: non-temporal hint on the X stream
-int g_row_local_early = 0;     // LDS-DMA kernel: fragments to registers first, the next pieces issued before the MFMAs
-int g_row_local_reverse = 0;   // LDS-DMA kernel, experiment: row tiles from the last to the first, so that the rows the previous pass read last come first (memory-side cache reuse between consecutive passes): no effect, 499 / 488 / 493 against 494 / 496 it/s, pass times unchanged
-int g_row_local_prio = 0;      // LDS-DMA kernel: raised wave priority while a wave issues its DMA pieces
-int g_row_local_chunk = 0;     // experiment: force the column chunk of the block-tiled float32 kernel (0: by size)
 int g_row_local_split = 1;     // block-tiled kernels: split the contraction over column chunks when there are few row blocks
 static int row_local_variant(const Ctx *c)
 {
@@ -1636,49 +1584,20 @@ int launch_row_local(Ctx *c, const void *B_wideT, double *out_tall)
         // LDS-DMA wave-streaming kernel with float64 sums
         const float *B = reinterpret_cast<const float *>(B_wideT);
         const long tiles = c->n_pad / 32;
-        int W = g_row_local_waves > 0 ? g_row_local_waves : (int)((tiles + 255) / 256);
+        int W = (int)((tiles + 255) / 256);               // one block per CU where possible
         if (W < 8) W = 8;
         if (W > 16) W = 16;
-        int R = (160 * 1024 - 2 * 32 * 64 * 4) / (W * 1024);      // ring pieces per wave that 160 KB allow
-        if (R > 12) R = 12;
-        if (g_row_local_ring > 0 && g_row_local_ring < R) R = g_row_local_ring;
-        if (R < 8) R = 8;
-        const size_t lds = ((size_t)2 * 32 * 64 + (size_t)W * R * 256) * sizeof(float);
+        const size_t lds = ((size_t)2 * 32 * 64 + (size_t)W * ROW_LOCAL_RING * 256) * sizeof(float);
         dim3 grid((unsigned)((tiles + W - 1) / W)), blk((unsigned)(64 * W));
-#define RLDE()                                                                                     \
-    do {                                                                                           \
-        static bool attr_done_e[64] = {false};                                                     \
-        if (!attr_done_e[c->device & 63]) {                                                        \
-            AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f32_dma<8, false, true>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-            attr_done_e[c->device & 63] = true;                                                    \
-        }                                                                                          \
-        hipLaunchKernelGGL((k_row_local_f32_dma<8, false, true>), grid, blk, lds, c->stream, c->X.as<float>(), \
-                           c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad, W, (g_row_local_prio ? 1 : 0) | (g_row_local_reverse ? 2 : 0));   \
-    } while (0)
-#define RLD(RV, NTV)                                                                               \
-    do {                                                                                           \
-        static bool attr_done[64] = {false};                                                       \
-        if (!attr_done[c->device & 63]) {                                                          \
-            AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f32_dma<RV, NTV>), \
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));     \
-            attr_done[c->device & 63] = true;                                                      \
-        }                                                                                          \
-        hipLaunchKernelGGL((k_row_local_f32_dma<RV, NTV>), grid, blk, lds, c->stream, c->X.as<float>(),   \
-                           c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad, W, (g_row_local_prio ? 1 : 0) | (g_row_local_reverse ? 2 : 0));   \
-    } while (0)
-#define RLD2(RV) do { if (g_row_local_early && RV == 8) RLDE(); else if (g_row_local_nt) RLD(RV, true); else RLD(RV, false); } while (0)
-        PASS_NAME(1, "k_row_local_f32_dma<%d>", R);
-        switch (R) {
-            case 8: RLD2(8); break;
-            case 9: RLD2(9); break;
-            case 10: RLD2(10); break;
-            case 11: RLD2(11); break;
-            default: RLD2(12); break;
+        static bool attr_done[64] = {false};                // the attribute is per device
+        if (!attr_done[c->device & 63]) {
+            AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f32_dma),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+            attr_done[c->device & 63] = true;
         }
-#undef RLD2
-#undef RLD
-#undef RLDE
+        PASS_NAME(1, "k_row_local_f32_dma<%d>", ROW_LOCAL_RING);
+        hipLaunchKernelGGL(k_row_local_f32_dma, grid, blk, lds, c->stream, c->X.as<float>(), c->p_pad, B,
+                           (int)c->p_pad, out_tall, c->n_pad, W);
     } else if (c->dtype == AA_F32 && row_local_variant(c) == 8) {
         // wave-streaming kernel: W waves per block, one block per CU where possible
         const float *B = reinterpret_cast<const float *>(B_wideT);
@@ -1686,7 +1605,7 @@ int launch_row_local(Ctx *c, const void *B_wideT, double *out_tall)
         const long tiles = c->n_pad / 32;
         const bool a64 = g_row_local_acc64 >= 2;
         const int wmax = !a64 ? (nct == 1 ? 16 : 12) : (nct == 1 ? 12 : 8);   // 160 KB of LDS; float64 sums: 3 (2) waves per SIMD
-        int W = g_row_local_waves > 0 ? g_row_local_waves : (int)((tiles + 255) / 256);
+        int W = (int)((tiles + 255) / 256);
         if (W < 8) W = 8;                                 // the B slab loader assumes >= 512 threads
         if (W > wmax) W = wmax;
         const size_t lds = ((size_t)2 * c->KP * 128 + (size_t)W * 32 * 64) * sizeof(float);
@@ -1703,7 +1622,7 @@ int launch_row_local(Ctx *c, const void *B_wideT, double *out_tall)
         dim3 grid((unsigned)((tiles + W - 1) / W)), blk((unsigned)(64 * W));
 #define RLW(NCTV, A64V)                                                                              \
     hipLaunchKernelGGL((k_row_local_f32_ws<NCTV, A64V>), grid, blk, lds, c->stream, c->X.as<float>(), \
-                       c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad, W, g_row_local_stagger)
+                       c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad, W)
         PASS_NAME(1, "k_row_local_f32_ws<%d,%d>", nct, (int)a64);
         if (nct == 1) { if (a64) RLW(1, true); else RLW(1, false); }
         else          { if (a64) RLW(2, true); else RLW(2, false); }
@@ -1723,11 +1642,6 @@ int launch_row_local(Ctx *c, const void *B_wideT, double *out_tall)
         double *dst = out_tall;
         if (nsplit > 1) {
             chunk = (int)round_up((c->p_pad + nsplit - 1) / nsplit, 128);
-            nsplit = (int)((c->p_pad + chunk - 1) / chunk);
-        }
-        if (g_row_local_chunk > 0) {
-            chunk = (int)round_up(g_row_local_chunk, 128);
-            if (row_local_variant(c) == 7 || row_local_variant(c) == 5) chunk = (int)round_up(g_row_local_chunk, 32);
             nsplit = (int)((c->p_pad + chunk - 1) / chunk);
         }
         if (nsplit > 1) {

@@ -18,7 +18,7 @@
 //
 // The lane kernel first.  The whole SPG state of a sample (x, g = Ax + b, d, Ad: 4*KQ
 // doubles) lives in that lane's registers, so there is no cross-lane traffic outside the
-// mat-vec; a lane that finishes waits for its batch (qp_refill_min).
+// mat-vec; a lane that finishes waits for its batch.
 //
 // Restatement notes (each keeps the reference's decisions; differences are rounding):
 //   * f along the search direction is the exact quadratic
@@ -58,8 +58,7 @@ template <> struct QpMask<64> { typedef unsigned long long type; };
 template <int KQ, bool FULL = false>
 __device__ __forceinline__ double qp_project_threshold(const double (&x)[KQ], const double (&g)[KQ],
                                                        double a, int k,
-                                                       typename QpMask<KQ>::type &mask,
-                                                       int *rounds = nullptr)
+                                                       typename QpMask<KQ>::type &mask)
 {
     typedef typename QpMask<KQ>::type M;
     constexpr int NP = KQ >= 4 ? 4 : 1;
@@ -99,7 +98,6 @@ __device__ __forceinline__ double qp_project_threshold(const double (&x)[KQ], co
 #pragma unroll
         for (int i = 0; i < KQ; ++i)
             if ((FULL || i < k) && (x[i] - a * g[i]) * cd > sm1) nm |= (M)1 << i;
-        if (rounds) *rounds += 1;
         if (nm == m || (pass >= 2 && (int)__popcll((unsigned long long)nm) >= c)) break;
         m = nm;
     }
@@ -119,9 +117,8 @@ struct QpHeader {
     unsigned int next_row;        // phase-1 work counter
     unsigned int n_overflow;      // samples handed to phase 2
     unsigned int next_overflow;   // phase-2 work counter
-    unsigned int n_long;          // hybrid row/wave update: head of the sorted list that the
-                                  // wave-per-sample kernel takes (predicted-long samples)
-    unsigned int dbg_rounds, dbg_trips, dbg_waves, pad;   // qp_profile counters of the row kernel
+    unsigned int reserved[4];
+    unsigned int pad;             // second overflow list (qp_overlap_tail, two stages): its length
     unsigned int waves_done;      // live hand-over: producer waves (k_qp_quad) that have exited
     unsigned int pad1, pad2, pad3;
 };
@@ -159,23 +156,6 @@ __device__ __forceinline__ int qp_load_agent(const int *p)
 {
     return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
-
-__device__ __forceinline__ int qp_debug_wave_max(int v)   // maximum of v over the active lanes
-{
-    int m = 0;
-    for (int r = 1; r < 200; ++r) {
-        if (!__any(v >= r)) break;
-        m = r;
-    }
-    return m;
-}
-
-// Optional cycle accounting of the lane-per-sample kernel (aa_set_option("qp_profile", 1));
-// lives at byte 64 of the scratch buffer, printed by the host after the update.
-struct QpDebug {
-    unsigned long long trips, refills, cyc_total, cyc_proj, cyc_matvec, waves, cyc_step, cyc_fin;
-    unsigned long long proj_calls, proj_rounds_wavemax, proj_rounds_lanesum, proj_lanes;
-};
 
 // ---------------------------------------------------------------------------
 // phase 1: one lane per sample, A broadcast from LDS.
@@ -237,7 +217,7 @@ __device__ __forceinline__ void lds_read_x2(unsigned addr, f64x2 (&q)[2])
 // wave-uniform (broadcast) 8*KQ-byte row.  The j loop is a real loop: its loads depend
 // on j, so the compiler cannot hoist the whole matrix into registers.
 template <int KQ>
-__device__ __forceinline__ void qp_matvec(const double *__restrict__ AsT,
+__device__ __forceinline__ void qp_matvec_lds(const double *__restrict__ AsT,
                                           const double *__restrict__ vl, int k, double (&out)[KQ])
 {
 #pragma unroll
@@ -344,61 +324,13 @@ __device__ __forceinline__ void qp_matvec_mfma(const double (&Breg)[KQ / 16][KQ 
     for (int i = 0; i < KQ; ++i) out[i] = abuf[i * QP_AS + lane];
 }
 
-// Mat-vec of the lane kernel through the SCALAR unit (KQ >= 16, default): A is the same for all
-// 64 samples of the wave, so its entries travel as SGPR operands of v_fma_f64 -- s_load_dwordx16
-// from the constant address space, 16 entries per chunk, two chunks in flight ahead of the one
-// being consumed -- and the vector v of this lane's sample never leaves its registers: no LDS
-// round trip, no cross-lane traffic, 1024 FMAs.  7 100 cycles per mat-vec against 17 800 for the
-// MFMA + LDS form above (tools/probes/sgpr_matvec_probe.hip; the VALU floor is 4 096).
-//   * the pointer passes through an empty asm with an SGPR constraint: without it LICM hoists all
-//     1024 scalar loads out of the trip loop and spills 2 000 SGPRs into VGPR lanes;
-//   * the sched_barriers keep the machine scheduler from clustering the loads of all chunks.
-// v_j = x_j for a lane whose sample is starting (g = A x + b), else the search direction
-// d_j = max(x_j - alpha_d g_j - td, 0) - x_j recomputed from the registers it is defined by.
-typedef const __attribute__((address_space(4))) double *qp_cptr_t;
-template <int KQ>
-__device__ __forceinline__ void qp_matvec_sgpr(const double *__restrict__ A, const double (&x)[KQ],
-                                               const double (&g)[KQ], double alpha_d, double td,
-                                               bool use_x, double (&out)[KQ])
-{
-    constexpr int CH = 16, D = 2, NCH = KQ * KQ / CH, CPR = KQ / CH;
-    qp_cptr_t Ap = (qp_cptr_t)(unsigned long long)A;
-    asm volatile("" : "+s"(Ap));
-#pragma unroll
-    for (int i = 0; i < KQ; ++i) out[i] = 0.0;
-    double buf[D + 1][CH];
-#pragma unroll
-    for (int q = 0; q < D; ++q)
-#pragma unroll
-        for (int e = 0; e < CH; ++e) buf[q][e] = Ap[q * CH + e];
-    double vj = 0.0;
-#pragma unroll
-    for (int c = 0; c < NCH; ++c) {
-        if (c + D < NCH) {
-#pragma unroll
-            for (int e = 0; e < CH; ++e) buf[(c + D) % (D + 1)][e] = Ap[(c + D) * CH + e];
-        }
-        __builtin_amdgcn_sched_barrier(0);
-        const int j = c / CPR, i0 = (c % CPR) * CH;
-        if (c % CPR == 0) {
-            const double dj = fmax(x[j] - alpha_d * g[j] - td, 0.0) - x[j];
-            vj = use_x ? x[j] : dj;
-        }
-#pragma unroll
-        for (int e = 0; e < CH; ++e) out[i0 + e] = fma(buf[c % (D + 1)][e], vj, out[i0 + e]);
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
-// PROF: cycle accounting compiled in (aa_set_option("qp_profile", 1)); the counters cost
-// registers, so the production instantiation has none of it.
 // Components k..KQ-1 are padding.  Their x is 0 and their gradient is held at QP_PAD = 1e300
 // (b_i = QP_PAD, the padded rows of A are zero), so x - a g is hugely negative for every step
 // a > 0, they never enter a support, their direction and residual are exactly 0, and the pass
 // loop needs no `component < k` predicate at all (32 wave-uniform predicates that hipcc kept
 // in SGPR pairs, spilled, and branched on).  Only the start-up and the final store test i < k.
 #define QP_PAD 1e300
-template <int KQ, bool FULL, bool PROF, bool SGMV>
+template <int KQ, bool FULL>
 __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][KQ]*/,
                                            const double *__restrict__ B, long stride_j,
                                            long stride_t, const double *__restrict__ bscale,
@@ -406,7 +338,6 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
                                            aa_qp_params p, int pass_cap, int *__restrict__ iters,
                                            QpHeader *__restrict__ hdr,
                                            int *__restrict__ ovf_rows, QpCarry *__restrict__ ovf,
-                                           int g_refill, QpDebug *__restrict__ dbg,
                                            const int *__restrict__ perm, int rst_a = 0, int rst_b = 0,
                                            int rst_z = 0)
 {
@@ -420,11 +351,10 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
         hdr += rst;
         if (iters) iters += (long)rst * n;
     }
-    constexpr bool SG = SGMV && KQ >= 16;              // mat-vec through the scalar unit
-    constexpr bool MFMA = KQ >= 16 && !SG;
+    constexpr bool MFMA = KQ >= 16;                    // mat-vec on the f64 matrix cores
     constexpr int VS = MFMA ? QP_VS : 64;              // row stride of the direction buffer
-    __shared__ __attribute__((aligned(16))) double AsT[(MFMA || SG) ? 2 : KQ * KQ];
-    __shared__ double vbuf[SG ? 64 : KQ * VS];
+    __shared__ __attribute__((aligned(16))) double AsT[MFMA ? 2 : KQ * KQ];
+    __shared__ double vbuf[KQ * VS];
     __shared__ double abuf[MFMA ? KQ * QP_AS : 1];
     const int lane = threadIdx.x;
     double Breg[MFMA ? KQ / 16 : 1][MFMA ? KQ / 4 : 1];
@@ -434,17 +364,14 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
 #pragma unroll
             for (int s = 0; s < KQ / 4; ++s)
                 Breg[nt][s] = A[(16 * nt + (lane & 15)) * KQ + 4 * s + (lane >> 4)];
-    } else if constexpr (!SG) {
-        for (int e = threadIdx.x; e < KQ * KQ; e += 64) AsT[(e % KQ) * KQ + e / KQ] = A[e];
-        Breg[0][0] = 0.0;
     } else {
+        for (int e = threadIdx.x; e < KQ * KQ; e += 64) AsT[(e % KQ) * KQ + e / KQ] = A[e];
         Breg[0][0] = 0.0;
     }
     __syncthreads();
     double *vl = vbuf + threadIdx.x;
 
     double x[KQ], g[KQ], Ad[KQ];
-    const int refill_min = g_refill;
     double f = 0.0, alpha = 1.0, fmem[QP_MAXMEM];
     double delta = 0.0, dd = 0.0, td = 0.0, alpha_d = 0.0;   // direction: d = P(x - alpha_d g) - x
     int n_iter = 0, n_feval = 0;
@@ -454,33 +381,22 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
     // the step: x - alpha g against x - g), each the warm start of the next one of its kind
     typename QpMask<KQ>::type support = 0, support_r = 0;
     const int mem = p.memory < 1 ? 1 : (p.memory > QP_MAXMEM ? QP_MAXMEM : p.memory);
-    if constexpr (!SG) {
 #pragma unroll
-        for (int i = 0; i < KQ; ++i) vl[i * VS] = 0.0;
-    }
-    bool starting_mv = false;                          // this lane's mat-vec input is x (start-up)
+    for (int i = 0; i < KQ; ++i) vl[i * VS] = 0.0;
 
     auto matvec = [&](double (&out)[KQ]) {            // out = A v, v = this lane's LDS column
-        if constexpr (SG) qp_matvec_sgpr<KQ>(A, x, g, alpha_d, td, starting_mv, out);
-        else if constexpr (MFMA) qp_matvec_mfma<KQ>(Breg, vbuf, abuf, lane, out);
-        else qp_matvec<KQ>(AsT, vl, k, out);
+        if constexpr (MFMA) qp_matvec_mfma<KQ>(Breg, vbuf, abuf, lane, out);
+        else qp_matvec_lds<KQ>(AsT, vl, k, out);
     };
 
     unsigned long long st_total = 0ull;
     int st_max = 0;
-    long long pc_proj = 0, pc_mv = 0, pc_refills = 0, pc_trips = 0, pc_step = 0, pc_fin = 0;
-    long long pc_lane_rounds = 0, pc_lane_calls = 0, pc_wavemax = 0;
-    const long long pc_start = PROF ? clock64() : 0;
-#define QP_TIC(var) const long long var = PROF ? clock64() : 0
-#define QP_TOC(acc, var) if constexpr (PROF) acc += clock64() - var
     // the trip bound is a watchdog only (each sample needs <= max_iterations trips)
     for (long trip = 0; trip < (1L << 24); ++trip) {
-        if constexpr (PROF) pc_trips = trip;
         // Refill idle lanes in batches: the start-up of a sample (strided loads, a
         // projection and a mat-vec) is executed by the whole wave, so it is only entered
         // when enough lanes are waiting (or nothing else is left to do).
-        const int n_idle = __popcll(__ballot(!active && !exhausted));
-        const bool refill = n_idle >= refill_min || !__any(active);
+        const bool refill = !__any(active);
         bool starting = false;
         if (refill && !active && !exhausted) {
             const unsigned int nxt = atomicAdd(&hdr->next_row, 1u);
@@ -498,10 +414,8 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
                 support_r = support;
 #pragma unroll
                 for (int i = 0; i < KQ; ++i) x[i] = (FULL || i < k) ? fmax(x[i] - t0, 0.0) : 0.0;
-                if constexpr (!SG) {
 #pragma unroll
-                    for (int i = 0; i < KQ; ++i) vl[i * VS] = x[i];
-                }
+                for (int i = 0; i < KQ; ++i) vl[i * VS] = x[i];
             } else {
                 exhausted = true;   // queue drained: this lane idles
             }
@@ -510,7 +424,6 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
         // direction there: ONE collective mat-vec per trip serves both (g = A x + b for the
         // former, A d for the latter), so pulling in new samples costs no extra mat-vec.
         if (!__any(active || starting)) break;
-        QP_TIC(tp0);
         if (active) {
             // ---- one pass of the loop at spg.py:318-396, up to the search direction
             if (n_iter == 0) {
@@ -526,32 +439,21 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
                     alpha = fmin(fmax(p.alpha_min, 1.0 / ainv), p.alpha_max);
                 }
             }
-            int rd_d = 0;
-            td = qp_project_threshold<KQ, true>(x, g, alpha, k, support, PROF ? &rd_d : nullptr);
-            if constexpr (PROF) {
-                pc_lane_rounds += rd_d;
-                pc_lane_calls += 1;
-            }
+            td = qp_project_threshold<KQ, true>(x, g, alpha, k, support);
             alpha_d = alpha;
             delta = 0.0;
             dd = 0.0;
 #pragma unroll
             for (int i = 0; i < KQ; ++i) {
                 const double di = fmax(x[i] - alpha_d * g[i] - td, 0.0) - x[i];
-                if constexpr (!SG) vl[i * VS] = di;   // to LDS for the mat-vec; recomputed below
+                vl[i * VS] = di;   // to LDS for the mat-vec; recomputed below
                 delta = fma(di, g[i], delta);
                 dd = fma(di, di, dd);
             }
         }
-        QP_TOC(pc_proj, tp0);
-        QP_TIC(tm1);
-        starting_mv = starting;
         matvec(Ad);                                    // collective (idle lanes: stale columns)
-        QP_TOC(pc_mv, tm1);
-        QP_TIC(ts0);
         if (starting) {
             // ---- rest of the start-up: g = A x + b; f = x'(g + b)/2      (spg.py:298-315)
-            if constexpr (PROF) pc_refills += 1;
             double xg = 0.0, xb = 0.0;
 #pragma unroll
             for (int i = 0; i < KQ; ++i) {
@@ -610,17 +512,7 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
             f = f_new;
             n_feval += 1;
 
-            QP_TOC(pc_step, ts0);
-            QP_TIC(tp1);
-            int rd_r = 0;
-            const double tr = qp_project_threshold<KQ, true>(x, g, 1.0, k, support_r, PROF ? &rd_r : nullptr);
-            if constexpr (PROF) {
-                pc_lane_rounds += rd_r;
-                pc_lane_calls += 1;
-                pc_wavemax += qp_debug_wave_max(rd_r);
-            }
-            QP_TOC(pc_proj, tp1);
-            QP_TIC(tf0);
+            const double tr = qp_project_threshold<KQ, true>(x, g, 1.0, k, support_r);
             double r2 = 0.0, rinf = 0.0;
 #pragma unroll
             for (int i = 0; i < KQ; ++i)
@@ -654,7 +546,6 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
                 }
                 active = false;
             }
-            QP_TOC(pc_fin, tf0);
         }
     }
     {   // wave totals (fixed-order butterfly), one atomic pair per wave
@@ -671,24 +562,6 @@ __global__ __launch_bounds__(64) void k_qp(const double *__restrict__ A /*[KQ][K
             atomicMax(&hdr->max_passes, (unsigned long long)mx);
         }
     }
-    if constexpr (PROF) {
-        atomicAdd(&dbg->proj_rounds_lanesum, (unsigned long long)pc_lane_rounds);
-        atomicAdd(&dbg->proj_lanes, (unsigned long long)pc_lane_calls);
-    }
-    if (PROF && threadIdx.x == 0) {
-        atomicAdd(&dbg->proj_calls, (unsigned long long)pc_trips + 1);
-        atomicAdd(&dbg->proj_rounds_wavemax, (unsigned long long)pc_wavemax);
-        atomicAdd(&dbg->cyc_step, (unsigned long long)pc_step);
-        atomicAdd(&dbg->cyc_fin, (unsigned long long)pc_fin);
-        atomicAdd(&dbg->trips, (unsigned long long)(pc_trips + 1));
-        atomicAdd(&dbg->refills, (unsigned long long)pc_refills);
-        atomicAdd(&dbg->cyc_total, (unsigned long long)(clock64() - pc_start));
-        atomicAdd(&dbg->cyc_proj, (unsigned long long)pc_proj);
-        atomicAdd(&dbg->cyc_matvec, (unsigned long long)pc_mv);
-        atomicAdd(&dbg->waves, 1ull);
-    }
-#undef QP_TIC
-#undef QP_TOC
 }
 
 // ---------------------------------------------------------------------------
@@ -960,7 +833,6 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
                                                  const int *__restrict__ ovf_rows,
                                                  const QpCarry *__restrict__ ovf,
                                                  double *__restrict__ zslot /*[slot][KQ] or null*/,
-                                                 const int *__restrict__ fresh_list = nullptr,
                                                  const unsigned int *__restrict__ count_ptr = nullptr,
                                                  int park_at = 1 << 30, unsigned int *__restrict__ n_parked = nullptr,
                                                  int *__restrict__ park_rows = nullptr,
@@ -1006,10 +878,8 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
     const double sq_lim = qp_sq_limit(p.epsilon_two, &sq_ok);
     const int mem = MEM1 ? 1 : (p.memory < 1 ? 1 : (p.memory > QW_MAXMEM ? QW_MAXMEM : p.memory));
     // n_fresh >= 0: process rows [0, n_fresh) from scratch; otherwise the overflow list
-    // fresh_list: the first hdr->n_long entries of the sorted sample list, from scratch
-    const bool fresh = n_fresh >= 0 || fresh_list != nullptr;
-    const unsigned int count = count_ptr ? *count_ptr
-                                         : (fresh_list ? hdr->n_long : (fresh ? (unsigned int)n_fresh : hdr->n_overflow));
+    const bool fresh = n_fresh >= 0;
+    const unsigned int count = count_ptr ? *count_ptr : (fresh ? (unsigned int)n_fresh : hdr->n_overflow);
 
     const unsigned int wave_id =
         (unsigned int)__builtin_amdgcn_readfirstlane((int)((blockIdx.x - blk0) * (blockDim.x >> 6) + (threadIdx.x >> 6)));
@@ -1019,12 +889,6 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
     unsigned int static_slot = wave_id;
     // next slot of this wave, or 0xffffffff: static stride (mode 0 / 2), tickets (mode 1)
     auto next_slot = [&]() -> unsigned int {
-        if (lv.mode == 3) {                            // plain tickets (qp_wave_queue): a wave takes the next slot when it is free
-            unsigned int tk = 0u;
-            if (lane == 0) tk = atomicAdd(&hdr->next_overflow, 1u);
-            tk = (unsigned int)__builtin_amdgcn_readfirstlane((int)tk);
-            return tk < count ? tk : 0xffffffffu;
-        }
         if (lv.mode != 1) {
             while (static_slot < count) {
                 const unsigned int sl = static_slot;
@@ -1059,8 +923,7 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
     };
     for (unsigned int slot = next_slot(); slot != 0xffffffffu; slot = next_slot()) {
         const bool shared = lv.mode == 1;           // the producer kernel is still running: coherent loads
-        const long row = fresh_list ? (long)fresh_list[slot]
-                                    : (fresh ? (long)slot : (long)(shared ? qp_load_agent(&ovf_rows[slot]) : ovf_rows[slot]));
+        const long row = fresh ? (long)slot : (long)(shared ? qp_load_agent(&ovf_rows[slot]) : ovf_rows[slot]);
 
         double x = live ? (shared ? qp_load_agent(&Z[row * ldz + comp]) : Z[row * ldz + comp]) : 0.0;
         const double b = live ? -B[comp * stride_j + row * stride_t] * (bscale ? bscale[comp] : 1.0) : 0.0;
@@ -1222,12 +1085,12 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
                 const double *__restrict__ bscale, double *__restrict__ Z, int ldz, long n_fresh, int k,            \
                 aa_qp_params p, int *__restrict__ iters, QpHeader *__restrict__ hdr,                                \
                 const int *__restrict__ ovf_rows, const QpCarry *__restrict__ ovf, double *__restrict__ zslot,      \
-                const int *__restrict__ fresh_list = nullptr, const unsigned int *__restrict__ count_ptr = nullptr, \
+                const unsigned int *__restrict__ count_ptr = nullptr,                                               \
                 int park_at = 1 << 30, unsigned int *__restrict__ n_parked = nullptr,                               \
                 int *__restrict__ park_rows = nullptr, QpCarry *__restrict__ park = nullptr,                        \
                 QpLive lv = QpLive{0, 0, 0u, 0u, nullptr, nullptr}, int rst_b = 0, long rst_n = 0
 #define QW_PASS A, B, stride_j, stride_t, bscale, Z, ldz, n_fresh, k, p, iters, hdr, ovf_rows, ovf, zslot,           \
-                fresh_list, count_ptr, park_at, n_parked, park_rows, park, lv, rst_b, rst_n
+                count_ptr, park_at, n_parked, park_rows, park, lv, rst_b, rst_n
 template <int KQ, bool MEM1 = false, bool LAZY = true>
 __global__ __launch_bounds__(256) void k_qp_wave(QW_ARGS) { qp_wave_body<KQ, MEM1, LAZY>(QW_PASS); }
 // the live consumers (QpLive mode 1): blocks of 16 waves that are launched with a whole CU's LDS
@@ -1238,12 +1101,11 @@ __global__ __launch_bounds__(256) void k_qp_wave(QW_ARGS) { qp_wave_body<KQ, MEM
 __global__ __launch_bounds__(1024) void k_qp_wave_live(QW_ARGS) { qp_wave_body<32, true>(QW_PASS); }
 #undef QW_ARGS
 #undef QW_PASS
-// continuation launches (memory == 1 by construction of the callers)
+// continuation launches (memory == 1 by construction of the callers: the memory-1 instantiation)
 #define QW32_LAUNCH(...)                                                              \
     do {                                                                              \
-        if (g_qp_wave_mem1 && g_qp_wave_lazy) hipLaunchKernelGGL((k_qp_wave<32, true, true>), __VA_ARGS__);  \
-        else if (g_qp_wave_mem1) hipLaunchKernelGGL((k_qp_wave<32, true, false>), __VA_ARGS__);   \
-        else hipLaunchKernelGGL((k_qp_wave<32, false>), __VA_ARGS__);                 \
+        if (g_qp_wave_lazy) hipLaunchKernelGGL((k_qp_wave<32, true, true>), __VA_ARGS__);  \
+        else hipLaunchKernelGGL((k_qp_wave<32, true, false>), __VA_ARGS__);           \
     } while (0)
 
 // max_iterations <= 0: the reference's loop body never runs and x = P(x0) is returned.
@@ -1281,9 +1143,9 @@ __global__ __launch_bounds__(256) void k_qp_project_only(const double *__restric
 // partners add the same two numbers, so all 16 lanes end with identical bits and every
 // row-uniform decision is taken identically by every lane of the row) -- while a wave
 // carries four samples and a SIMD several waves, so the issue slots one latency-bound
-// chain leaves empty are filled by others.  Rows pull samples from the global queue
-// independently (longest first, k_qp_order_*), run them to completion (no pass cap, no
-// second kernel), and waves that hold a long-running sample raise their issue priority, so
+// chain leaves empty are filled by others.  Every wave owns a static slice of the sample list
+// (longest first, k_qp_order_*) that its four rows share, samples run to completion (no pass
+// cap, no second kernel), and waves that hold a long-running sample raise their issue priority, so
 // the longest chain of the update runs at its own latency from t = 0 while the short
 // samples fill the machine around it.
 //
@@ -1344,14 +1206,12 @@ __device__ __forceinline__ bool qr_any(bool p, int rowshift)
 // rule and the same closed form as qp_project_threshold / qw_threshold; `mask` holds the
 // support bits of this lane's own components.  Rows leave the loop independently.
 template <int CPL>
-__device__ __forceinline__ double qr_threshold(const double (&w)[CPL], unsigned &mask, int rowshift,
-                                               unsigned int &rounds)
+__device__ __forceinline__ double qr_threshold(const double (&w)[CPL], unsigned &mask, int rowshift)
 {
     unsigned m = mask;
     int c = qr_sum_i(__popc(m));
     double s = 0.0;
     for (int pass = 0; pass < 32 * CPL + 8; ++pass) {
-        rounds += 1u;
         if (c == 0) {                              // cold start, or the warm guess emptied
             double mx = w[0];
 #pragma unroll
@@ -1390,15 +1250,10 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
                                                double *__restrict__ Z, int ldz, long n, int k,
                                                aa_qp_params p, int *__restrict__ iters,
                                                QpHeader *__restrict__ hdr,
-                                               const int *__restrict__ perm, int hot_passes, int prof, int QR_CHUNK,
-                                               int pass_cap, int *__restrict__ ovf_rows,
-                                               QpCarry *__restrict__ ovf)
+                                               const int *__restrict__ perm)
 {
     constexpr int KQ = 16 * CPL;
-    // hybrid update: the first n_long samples of the sorted list (predicted long) are being
-    // solved by the wave-per-sample kernel on the side stream; this kernel takes the rest
-    const long list0 = perm ? (long)hdr->n_long : 0;
-    const long nq = n - list0;                     // entries of the list this kernel works off
+    constexpr int hot_passes = 24;                 // passes after which a sample's wave takes issue priority
     __shared__ __attribute__((aligned(16))) double vb[4][KQ];
     const int lane = threadIdx.x, r = lane & 15, rowid = lane >> 4, rowshift = lane & 48;
     const int comp0 = r * CPL;                     // this lane owns components comp0 .. comp0 + CPL - 1
@@ -1427,30 +1282,25 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
     bool active = false;
     unsigned sup = 0u, sup_r = 0u;                 // supports of the latest direction / residual projection
     int prio = 0;
-    unsigned int dbg_rounds = 0u, dbg_trips = 0u;  // qp_profile: Michelot rounds / trips of this lane
     unsigned long long st_total = 0ull;            // pass statistics of this row, one atomic per wave at exit
     int st_max = 0;
 
-    // Work distribution.  The queue is the sample list in longest-first order; a wave takes
-    // QR_CHUNK tickets per atomic and always has the NEXT chunk's atomic in flight, and every
-    // row holds, next to the sample it works on, the one it will work on next with its z0 and
-    // b already loaded -- so neither the atomic's round trip nor the two global loads of a
-    // start-up sit on the critical path of the three other rows of the wave.
+    // Work distribution, no atomics at all: wave w owns the positions w, w + W, w + 2W, ... (W waves)
+    // of the sample list.  The list is in longest-first order, so every wave gets the same mix of
+    // long and short samples (its first one from the W longest, its second from the next W, ...),
+    // and the four rows of the wave share that slice dynamically.  Every row holds, next to the
+    // sample it works on, the one it will work on next with its z0 and b already loaded -- so the
+    // two global loads of a start-up do not sit on the critical path of the three other rows.
     long nxt = -1;                                 // this row's next sample (prefetched), -1: none
     double zn[CPL], bn[CPL];
     int npred = 0;
 #pragma unroll
     for (int q = 0; q < CPL; ++q) zn[q] = bn[q] = 0.0;
-    long q_base = 0;                               // wave-uniform: local chunk [q_base, q_base + q_left)
-    int q_left = 0;
-    unsigned int q_ahead = 0u;                     // ticket of the chunk whose atomic is in flight
-    bool have_ahead = false, drained = false;      // wave-uniform
-    int s_next = 0;                                // static assignment: next position of this wave's list
-    const long long t_start = prof ? clock64() : 0;
+    bool drained = false;                          // wave-uniform
+    int s_next = 0;                                // next position of this wave's slice
 
     for (long trip = 0; trip < (1L << 26); ++trip) {       // watchdog bound only
-        // a wave that carries a long-running sample stops pulling work (its remaining rows idle
-        // once their local entries are used up) and takes issue priority: the longest chains of
+        // a wave that carries a long-running sample takes issue priority: the longest chains of
         // the update then advance at one pass per ~1500 cycles while short samples fill the
         // rest of the machine
         const bool hot_wave = __any(active && (n_iter >= hot_passes || predicted >= 2 * hot_passes));
@@ -1469,7 +1319,6 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
         }
         const bool busy = __any(active || starting);
         if (busy) {
-        dbg_trips += 1u;
 
         if (starting) {
             // ---- start-up: x = P(z0)                                   (spg.py:298-300)
@@ -1480,7 +1329,7 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
                 w0[q] = live[q] ? zn[q] : -QP_PAD;
                 if (live[q] && zn[q] > 0.0) m0 |= 1u << q;     // z0 is (nearly) feasible: warm support
             }
-            const double t0 = qr_threshold<CPL>(w0, m0, rowshift, dbg_rounds);
+            const double t0 = qr_threshold<CPL>(w0, m0, rowshift);
             sup = m0;
             sup_r = m0;
 #pragma unroll
@@ -1497,7 +1346,7 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
                     double w1[CPL];
 #pragma unroll
                     for (int q = 0; q < CPL; ++q) w1[q] = x[q] - g[q];
-                    const double t1 = qr_threshold<CPL>(w1, sup_r, rowshift, dbg_rounds);
+                    const double t1 = qr_threshold<CPL>(w1, sup_r, rowshift);
                     double am = 0.0;
 #pragma unroll
                     for (int q = 0; q < CPL; ++q) am = fmax(am, fabs(fmax(w1[q] - t1, 0.0) - x[q]));
@@ -1509,7 +1358,7 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
             double w[CPL];
 #pragma unroll
             for (int q = 0; q < CPL; ++q) w[q] = x[q] - alpha * g[q];
-            const double td = qr_threshold<CPL>(w, sup, rowshift, dbg_rounds);
+            const double td = qr_threshold<CPL>(w, sup, rowshift);
             double pg = 0.0, pd = 0.0;
 #pragma unroll
             for (int q = 0; q < CPL; ++q) {
@@ -1604,7 +1453,7 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
             double wr[CPL];
 #pragma unroll
             for (int q = 0; q < CPL; ++q) wr[q] = x[q] - g[q];
-            const double tr = qr_threshold<CPL>(wr, sup_r, rowshift, dbg_rounds);
+            const double tr = qr_threshold<CPL>(wr, sup_r, rowshift);
             double pr2 = 0.0;
             bool big = false;
 #pragma unroll
@@ -1618,73 +1467,25 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
             n_iter += 1;
             const bool conv = (sqrt(r2) < p.epsilon_two) || rinf_small;
             const bool finished = conv || n_feval > p.max_feval || n_iter >= p.max_iterations;
-            if (finished || n_iter >= pass_cap) {
+            if (finished) {
 #pragma unroll
                 for (int q = 0; q < CPL; ++q)
                     if (live[q]) Z[row * ldz + comp0 + q] = x[q];
-                if (finished) {
-                    if (r == 0 && iters) iters[row] = n_iter;
-                    st_total += (unsigned long long)n_iter;
-                    st_max = n_iter > st_max ? n_iter : st_max;
-                } else if (r == 0) {
-                    // an unexpectedly long sample: hand it, with its SPG state, to the
-                    // wave-per-sample kernel (1 us per pass instead of ~3)
-                    const unsigned int slot = atomicAdd(&hdr->n_overflow, 1u);
-                    ovf_rows[slot] = (int)row;
-                    QpCarry cr;
-                    cr.alpha = alpha;
-                    cr.f = f;
-                    cr.n_iter = n_iter;
-                    cr.n_feval = n_feval;
-                    ovf[slot] = cr;
-                }
+                if (r == 0 && iters) iters[row] = n_iter;
+                st_total += (unsigned long long)n_iter;
+                st_max = n_iter > st_max ? n_iter : st_max;
                 active = false;
             }
         }
         }   // busy
-        // ---- rows without a prefetched sample pop the local chunk
+        // ---- rows without a prefetched sample take the next positions of the wave's slice
         {
             const bool need = nxt < 0 && !drained;
             const unsigned long long nbm = __ballot(need && r == 0);
             if (nbm != 0ull) {
-                if (QR_CHUNK == 0) {
-                    // static assignment, no atomics at all: wave w owns the list positions
-                    // w, w + W, w + 2W, ... (W waves).  The list is in longest-first order, so
-                    // every wave gets the same mix of long and short samples (its first one from
-                    // the W longest, its second from the next W, ...), and the four rows of the
-                    // wave share that list dynamically.
-                    q_base = 0;
-                    q_left = 4;
-                } else
-                if (q_left == 0) {
-                    if (have_ahead) {                       // the chunk requested a while ago
-                        const long t0 = (long)(unsigned int)__builtin_amdgcn_readfirstlane((int)q_ahead);
-                        have_ahead = false;
-                        q_base = t0;
-                        q_left = t0 >= nq ? 0 : (nq - t0 < QR_CHUNK ? (int)(nq - t0) : QR_CHUNK);
-                        if (q_left == 0) drained = true;
-                    }
-                    if (q_left == 0 && !drained && !hot_wave) {   // first trip (or after a hot phase)
-                        unsigned int t1 = 0u;
-                        if (lane == 0) t1 = atomicAdd(&hdr->next_row, (unsigned int)QR_CHUNK);
-                        const long t0 = (long)(unsigned int)__builtin_amdgcn_readfirstlane((int)t1);
-                        q_base = t0;
-                        q_left = t0 >= nq ? 0 : (nq - t0 < QR_CHUNK ? (int)(nq - t0) : QR_CHUNK);
-                        if (q_left == 0) drained = true;
-                    }
-                    if (q_left > 0 && !hot_wave) {          // request the chunk after this one
-                        if (lane == 0) q_ahead = atomicAdd(&hdr->next_row, (unsigned int)QR_CHUNK);
-                        have_ahead = true;
-                    }
-                }
                 const int rank = __popcll(nbm & ((1ull << rowshift) - 1ull));
-                long idx = list0 + q_base + rank;
-                bool take = need && rank < q_left;
-                if (QR_CHUNK == 0) {
-                    idx = list0 + (long)blockIdx.x + (long)(s_next + rank) * (long)gridDim.x;
-                    take = need && idx < n;
-                }
-                if (take) {
+                const long idx = (long)blockIdx.x + (long)(s_next + rank) * (long)gridDim.x;
+                if (need && idx < n) {
                     nxt = perm ? (long)perm[idx] : idx;
 #pragma unroll
                     for (int q = 0; q < CPL; ++q) {
@@ -1693,17 +1494,12 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
                     }
                     npred = (perm && iters) ? iters[nxt] : 0;      // pass count of the previous update
                 }
-                const int served = __popcll(nbm) < q_left ? __popcll(nbm) : q_left;
-                q_base += served;
-                q_left -= served;
-                if (QR_CHUNK == 0) {
-                    s_next += __popcll(nbm);
-                    q_left = 0;
-                    if (list0 + (long)blockIdx.x + (long)s_next * (long)gridDim.x >= n) drained = true;
-                }
+                s_next += __popcll(nbm);
+                if ((long)blockIdx.x + (long)s_next * (long)gridDim.x >= n) drained = true;
             }
         }
-        if (!__any(active || nxt >= 0) && (drained || (q_left == 0 && !have_ahead && hot_wave))) break;
+        // (no active row and no prefetched sample implies that the slice is used up)
+        if (!__any(active || nxt >= 0) && drained) break;
     }
     {   // statistics: the four rows' totals combined in lane 0, one atomic pair per wave
         unsigned long long tot = 0ull;
@@ -1719,22 +1515,6 @@ __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[l
         if (lane == 0 && tot) {
             atomicAdd(&hdr->total_passes, tot);
             atomicMax(&hdr->max_passes, (unsigned long long)mx);
-        }
-    }
-    if (prof && r == 0) {                          // per row: Michelot rounds, trips of its wave
-        atomicAdd(&hdr->dbg_rounds, dbg_rounds);
-        if (lane == 0) atomicAdd(&hdr->dbg_trips, dbg_trips);
-        if (lane == 0) atomicAdd(&hdr->dbg_waves, 1u);
-        if (lane == 0) {
-            // QpDebug area (byte 64 of the scratch): [0] max cycles of a wave, [1] its trips packed,
-            // [2] max trips of a wave, [3] sum of cycles, [4] cycles of the wave with most trips
-            unsigned long long *dbg = reinterpret_cast<unsigned long long *>(reinterpret_cast<unsigned char *>(hdr) + 64);
-            const unsigned long long cyc = (unsigned long long)(clock64() - t_start);
-            atomicMax(&dbg[0], cyc);
-            atomicMax(&dbg[2], (unsigned long long)dbg_trips);
-            atomicAdd(&dbg[3], cyc);
-            atomicMax(&dbg[4], ((unsigned long long)dbg_trips << 40) | (cyc & ((1ull << 40) - 1ull)));
-            atomicMax(&dbg[1], (cyc << 20) | (unsigned long long)(dbg_trips & 0xfffffu));
         }
     }
 }
@@ -1853,7 +1633,7 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
                                              double *__restrict__ Z, int ldz, long n, int k,
                                              const aa_qp_params &p, int pass_cap, int *__restrict__ iters,
                                              QpHeader *__restrict__ hdr, int *__restrict__ ovf_rows,
-                                             QpCarry *__restrict__ ovf, int refill_min,
+                                             QpCarry *__restrict__ ovf,
                                              const int *__restrict__ perm, long max_trips,
                                              int live_epoch, int *__restrict__ ovf_ready, int rst_b, long rst_n)
 {
@@ -1879,7 +1659,6 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
     // 4 max(eps2^2, k eps1^2) passes neither stopping test
     const double cert = 4.0 * fmax(p.epsilon_two * p.epsilon_two, (double)k * p.epsilon_one * p.epsilon_one);
     bool pending = false;                           // the test behind this sample's latest pass is still owed
-    unsigned int lz_trips = 0u, lz_skipped = 0u;    // LAZYQ: trips with an owed test, and those that skipped it (qp_profile)
     double H[MT][J];                                // A's operand tiles (constant)
 #pragma unroll
     for (int mt = 0; mt < MT; ++mt)
@@ -1908,8 +1687,7 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
 
     for (long trip = 0; trip < max_trips; ++trip) {
         const bool idle = !active && !exhausted;
-        const int n_idle = (int)__popcll(__ballot(idle));
-        const bool refill = n_idle >= 4 * refill_min || !__any(active);
+        const bool refill = !__any(active);             // a wave takes its next batch of 16 when the whole batch is done
         bool starting = false;
         if (refill && idle) {
             if (next_idx < n) {
@@ -2091,10 +1869,6 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
             // direction does not rule it out -- for none of them in most trips of a batch of similar samples
             const double am = fmax(1.0, alpha);
             const bool need = was_active && pending && !(r1 > cert * am * am);
-            if (__any(was_active && pending)) {
-                lz_trips += 1u;
-                if (!__any(need)) lz_skipped += 1u;
-            }
             if (__any(need)) {
                 residual(need);
                 if (need && ((sq_ok ? q2 < sq_lim : sqrt(q2) < p.epsilon_two) || (qinf < p.epsilon_one))) {
@@ -2160,12 +1934,6 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
             }
         }
     }
-    if constexpr (LAZYQ) {
-        if (threadIdx.x == 0 && lz_trips) {
-            atomicAdd(&hdr->dbg_trips, lz_trips);
-            atomicAdd(&hdr->dbg_rounds, lz_skipped);
-        }
-    }
     {   // wave totals (fixed-order butterfly), one atomic pair per wave
         unsigned long long tot = st_total;
         int mx = st_max;
@@ -2186,72 +1954,45 @@ __device__ __forceinline__ void qp_quad_body(const double *__restrict__ A /*[lda
     }
 }
 
-// The same body at three register budgets: OCC waves per SIMD (2: whatever the compiler likes,
-// 3: <= 168 registers, 4: <= 128 with a little scratch).
-#define QQ_ARGS const double *__restrict__ A, int lda, const double *__restrict__ B, long stride_j, long stride_t,   \
-                const double *__restrict__ bscale, double *__restrict__ Z, int ldz, long n, int k, aa_qp_params p, \
-                int pass_cap, int *__restrict__ iters, QpHeader *__restrict__ hdr, int *__restrict__ ovf_rows,      \
-                QpCarry *__restrict__ ovf, int refill_min, const int *__restrict__ perm, long max_trips,           \
-                int live_epoch, int *__restrict__ ovf_ready, int rst_b, long rst_n
-#define QQ_PASS A, lda, B, stride_j, stride_t, bscale, Z, ldz, n, k, p, pass_cap, iters, hdr, ovf_rows, ovf,        \
-                refill_min, perm, max_trips, live_epoch, ovf_ready, rst_b, rst_n
+// The body at a budget of 3 waves per SIMD (<= 168 registers): measured ahead of 2 and of 4 (128
+// registers with a little scratch), alone and beside the live consumers.
 template <int MT, bool MEM1, bool LAZYQ = false>
-__global__ __launch_bounds__(64) void k_qp_quad(QQ_ARGS) { qp_quad_body<MT, MEM1, LAZYQ>(QQ_PASS); }
-template <int MT, bool MEM1, bool LAZYQ = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3))) void k_qp_quad_w3(QQ_ARGS)
+__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(3, 3)))
+void k_qp_quad_w3(const double *__restrict__ A, int lda, const double *__restrict__ B, long stride_j, long stride_t,
+                  const double *__restrict__ bscale, double *__restrict__ Z, int ldz, long n, int k, aa_qp_params p,
+                  int pass_cap, int *__restrict__ iters, QpHeader *__restrict__ hdr, int *__restrict__ ovf_rows,
+                  QpCarry *__restrict__ ovf, const int *__restrict__ perm, long max_trips, int live_epoch,
+                  int *__restrict__ ovf_ready, int rst_b, long rst_n)
 {
-    qp_quad_body<MT, MEM1, LAZYQ>(QQ_PASS);
+    qp_quad_body<MT, MEM1, LAZYQ>(A, lda, B, stride_j, stride_t, bscale, Z, ldz, n, k, p, pass_cap, iters, hdr, ovf_rows,
+                                  ovf, perm, max_trips, live_epoch, ovf_ready, rst_b, rst_n);
 }
-template <int MT, bool MEM1, bool LAZYQ = false>
-__global__ __launch_bounds__(64) __attribute__((amdgpu_waves_per_eu(4, 4))) void k_qp_quad_w4(QQ_ARGS)
-{
-    qp_quad_body<MT, MEM1, LAZYQ>(QQ_PASS);
-}
-#undef QQ_ARGS
-#undef QQ_PASS
 
 // Passes a sample may spend in the lane-per-sample kernel before it is handed to the
 // wave-per-sample kernel.
 int g_qp_pass_cap = 24;        // settable with aa_set_option("qp_pass_cap", v)
-int g_qp_matvec = 0;           // lane kernel mat-vec: 0 f64 MFMA + LDS (default), 1 scalar-unit broadcast (SGPR
-                               // operands; 7 100 against 17 800 cycles in isolation, but 2 % slower inside the
-                               // kernel: 256 VGPRs + 97 AGPRs + spilled SGPRs)
-int g_qp_row_waves = 2048;     // most waves of the row kernel (k_qp_row): 2 per SIMD, all resident
-int g_qp_row_hot = 24;         // passes after which a sample's wave takes issue priority
-int g_qp_row_chunk = 0;        // queue tickets a wave takes per atomic; 0: static strided assignment, no queue
-int g_qp_row_long = 0;         // hybrid: samples with >= this many passes in the previous update go to the
-                               // wave-per-sample kernel on the side stream (0: no side stream)
-int g_qp_row_cap = 1 << 30;        // passes after which the row kernel hands a sample to the wave-per-sample kernel
-int g_qp_refill_min = 64;      // idle lanes of a wave that trigger a refill (1..64); 64 = only
-                               // when the whole wave is idle: a sample's start-up (strided row
-                               // loads, a cold projection) is executed by the whole wave, and
-                               // mid-flight refills cost more than the idle lanes they fill
-                               // (2.64 ms per outer iteration against 2.83 at 24)
 int g_qp_mode = 0;             // 0: by size (see launch_qp), 1: wave-per-sample only,
                                // 2: lane-per-sample then wave-per-sample, 3: row kernel,
                                // 4: four lanes per sample (matrix-core layout) then wave-per-sample
-int g_qp_quad_waves = 8192;    // most waves of k_qp_quad: up to 131 072 samples every wave takes ONE batch of 16
-                               // and the hardware hands the batches (longest first) to SIMDs as they free up
-int g_qp_quad_refill = 16;     // idle sample slots (of 16) of a wave that trigger a refill
 int g_qp_quad_cap = 0;         // passes after which k_qp_quad parks a sample for the wave kernel; 0: by size --
                                // 32 from 65 536 samples per GPU (100 000: 1.985 against 2.010 ms per outer
                                // iteration), 24 below (12 500: 0.572 against 0.582)
-int g_qp_wave_queue = 0;        // continuation launch, experiment: waves take the parked samples by ticket instead of fixed strides (slower: 492-494 against 496-499 it/s; the chains are latency-bound and four waves share a SIMD at almost no cost)
-int g_qp_wave_blocks = 1024;   // blocks (4 waves each) of the wave-per-sample kernel when it finishes parked samples
 int g_qp_live = 0;             // k_qp_quad hands parked samples to a concurrent k_qp_wave launch (QpLive)
-int g_qp_live_occ = 3;         // register budget of k_qp_quad beside the consumers (waves per SIMD)
-int g_qp_live_blocks = 48;     // CUs given to the consumers (one block of 16 waves each)
 #define QP_LIVE_LDS 163840     // a CU's LDS
-int g_qp_quad_occ = 3;         // register budget of k_qp_quad: waves per SIMD (2, 3 or 4)
-int g_qp_quad_lazy = 0;        // four-lane QP, opt-in: the stopping test of a pass decided in the next trip (LAZYQ) -- same results; 497/497/494 it/s with, 503/498 without at the driver's flags, 524/523 against 522 at the default flags: a third of the trips skip the test for the whole wave (qp_profile: 32 % in iterations 8-14, 31 % around 30), which saves less than the extra partial trip per batch and the 22 VGPR spills (7 without) cost
+// Launch shapes; the measurements behind the values are in DESIGN.md sections 8.2 and 9.
+constexpr int QP_WAVES = 1024;        // most waves of the lane-per-sample kernel: one per SIMD
+constexpr int QP_QUAD_WAVES = 8192;   // most waves of k_qp_quad_w3: up to 131 072 samples every wave takes ONE batch of 16
+                                      // and the hardware hands the batches (longest first) to SIMDs as they free up
+constexpr int QP_ROW_WAVES = 2048;    // most waves of the row kernel (k_qp_row): 2 per SIMD, all resident
+constexpr int QP_WAVE_BLOCKS = 1024;  // blocks (4 waves each) of the wave-per-sample kernel when it finishes parked samples
+constexpr int QP_QUAD_OCC = 3;        // waves per SIMD of k_qp_quad_w3 (its LDS share beside the live consumers follows)
+constexpr int QP_LIVE_BLOCKS = 48;    // CUs given to the live consumers (one block of 16 waves each)
+constexpr int QP_TAIL_CAP = 96;       // qp_overlap_tail: only samples beyond this many passes go to the side stream
+int g_qp_quad_lazy = 0;        // four-lane QP, opt-in: the stopping test of a pass decided in the next trip (LAZYQ) -- same results; 497/497/494 it/s with, 503/498 without at the driver's flags, 524/523 against 522 at the default flags: a third of the trips skip the test for the whole wave (counted: 32 % in iterations 8-14, 31 % around 30), which saves less than the extra partial trip per batch and the 22 VGPR spills (7 without) cost
 int g_qp_fused_order = 1;   // four-lane QP: the sample order of the NEXT update is formed by extra blocks of this update's continuation launch (k_qp_wave_ord)
 int g_qp_wave_lazy = 1;        // wave-per-sample kernel: stopping test of a pass decided at the top of the next one, skipped when <d, d> proves it negative (0: after every pass)
-int g_qp_wave_mem1 = 1;        // continuation launches of the wave-per-sample kernel: 1 = the memory-1 instantiation (no f_mem array: 311 fewer SGPR spills), 0 = the generic one (A/B)
 int g_qp_overlap_tail = 0;     // 1: stragglers on a side stream, overlapped with the Z'X pass
-int g_qp_tail_cap = 96;        // with qp_overlap_tail: only samples beyond this many passes go to the side stream (0: all parked ones)
-int g_qp_profile = 0;          // cycle accounting of k_qp (printed when stats are requested)
 int g_qp_sort = 1;             // order the samples by the previous update's pass counts
-int g_qp_waves = 1024;         // most waves the lane-per-sample kernel is launched with
 static int qp_pass_cap() { return g_qp_pass_cap < 1 ? 1 : g_qp_pass_cap; }
 
 // Order of the samples for the lane kernel: by the pass count of the PREVIOUS weights update,
@@ -2290,18 +2031,10 @@ __global__ __launch_bounds__(256) void k_qp_order_hist(const int *__restrict__ p
 __global__ __launch_bounds__(256) void k_qp_order_scatter(const int *__restrict__ prev_iters, long n,
                                                           const int *__restrict__ ghist,
                                                           int *__restrict__ gcursor,
-                                                          int *__restrict__ perm,
-                                                          QpHeader *__restrict__ hdr, int long_from)
+                                                          int *__restrict__ perm)
 {
     __shared__ int hist[QP_SORT_BUCKETS], cursor[QP_SORT_BUCKETS];
     const int t = threadIdx.x;
-    // samples whose previous update needed >= long_from passes: the head of the sorted list
-    if (hdr && blockIdx.x == 0 && t == 0) {
-        int m = 0;
-        if (long_from > 0)
-            for (int b = QP_SORT_BUCKETS - 1; b >= long_from && b >= 0; --b) m += ghist[b];
-        hdr->n_long = (unsigned int)m;
-    }
     if (t < QP_SORT_BUCKETS) hist[t] = 0;
     __syncthreads();
     const long r0 = (long)blockIdx.x * QP_SORT_ROWS_PER_BLOCK;
@@ -2401,16 +2134,16 @@ __global__ __launch_bounds__(256) void k_qp_wave_ord(QpOrder od, const double *_
                                                      const QpCarry *__restrict__ ovf, int park_at = 1 << 30,
                                                      unsigned int *__restrict__ n_parked = nullptr,
                                                      int *__restrict__ park_rows = nullptr,
-                                                     QpCarry *__restrict__ park = nullptr, int queue = 0)
+                                                     QpCarry *__restrict__ park = nullptr)
 {
     if ((int)blockIdx.x < od.blocks) {
         qp_order_block(od);
         return;
     }
     qp_wave_body<32, true, LAZY>(A, B, stride_j, stride_t, bscale, Z, ldz, (long)-1, k, p, iters, hdr, ovf_rows, ovf,
-                                 (double *)nullptr, (const int *)nullptr, (const unsigned int *)nullptr, park_at,
+                                 (double *)nullptr, (const unsigned int *)nullptr, park_at,
                                  n_parked, park_rows, park,
-                                 QpLive{queue ? 3 : 0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, (unsigned int)od.blocks);
+                                 QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, (unsigned int)od.blocks);
 }
 
 // device-side set-up of the QP scratch: header zeroed, A = D G D padded to KQ and KW,
@@ -2437,8 +2170,6 @@ __global__ __launch_bounds__(256) void k_qp_setup(QpHeader *__restrict__ hdr, do
         hdr->next_row = 0u;
         hdr->n_overflow = 0u;
         hdr->next_overflow = 0u;
-        hdr->n_long = 0u;
-        hdr->dbg_rounds = hdr->dbg_trips = hdr->dbg_waves = 0u;
         hdr->pad = 0u;
         hdr->waves_done = 0u;
     }
@@ -2454,8 +2185,7 @@ __global__ __launch_bounds__(256) void k_qp_setup(QpHeader *__restrict__ hdr, do
 }
 
 // counting sort of the samples by their previous pass counts, longest first -> *perm_out
-static int qp_order_rows(Ctx *c, const int *iters_dev, long n, const int **perm_out,
-                         QpHeader *hdr = nullptr, int long_from = 0, bool zeroed = false)
+static int qp_order_rows(Ctx *c, const int *iters_dev, long n, const int **perm_out, bool zeroed)
 {
     AA_CHECK(c->qpPerm.alloc((size_t)n * sizeof(int) + QP_ORDER_AREA * sizeof(int)));
     int *pm = c->qpPerm.as<int>();
@@ -2464,7 +2194,7 @@ static int qp_order_rows(Ctx *c, const int *iters_dev, long n, const int **perm_
     const unsigned nblk = (unsigned)((n + QP_SORT_ROWS_PER_BLOCK - 1) / QP_SORT_ROWS_PER_BLOCK);
     hipLaunchKernelGGL(k_qp_order_hist, dim3(nblk), dim3(256), 0, c->stream, iters_dev, n, ghist);
     hipLaunchKernelGGL(k_qp_order_scatter, dim3(nblk), dim3(256), 0, c->stream, iters_dev, n,
-                       (const int *)ghist, gcursor, pm, hdr, long_from);
+                       (const int *)ghist, gcursor, pm);
     *perm_out = pm;
     return AA_OK;
 }
@@ -2485,8 +2215,6 @@ __global__ __launch_bounds__(256) void k_qp_setup_slots(QpHeader *__restrict__ h
         h->next_row = 0u;
         h->n_overflow = 0u;
         h->next_overflow = 0u;
-        h->n_long = 0u;
-        h->dbg_rounds = h->dbg_trips = h->dbg_waves = 0u;
         h->pad = 0u;
         h->waves_done = 0u;
     }
@@ -2513,16 +2241,15 @@ int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_pa
     static_assert(sizeof(QpHeader) == 64, "one header per 64 bytes");
     hipLaunchKernelGGL(k_qp_setup_slots, dim3((unsigned)R), dim3(256), 0, c->stream, hdr, Ad, gram_dev, k, KQ, c->KP);
     long waves = (n + 63) / 64;
-    if (waves > g_qp_waves) waves = g_qp_waves;
+    if (waves > QP_WAVES) waves = QP_WAVES;
     const dim3 grid((unsigned)waves, (unsigned)R);
     const int cap = p->max_iterations;
     double *Zt = c->Zt.as<double>();
     const double *Bt = c->Gr.as<double>();
 #define QPS(KQV, FULLV)                                                                                  \
-    hipLaunchKernelGGL((k_qp<KQV, FULLV, false, false>), grid, dim3(64), 0, c->stream, (const double *)Ad, Bt, \
+    hipLaunchKernelGGL((k_qp<KQV, FULLV>), grid, dim3(64), 0, c->stream, (const double *)Ad, Bt,                \
                        (long)1, (long)c->KP, (const double *)nullptr, Zt, c->KP, n, k, *p, cap, (int *)nullptr,  \
-                       hdr, (int *)nullptr, (QpCarry *)nullptr, g_qp_refill_min, (QpDebug *)nullptr,              \
-                       (const int *)nullptr, KQV * KQV, k, k)
+                       hdr, (int *)nullptr, (QpCarry *)nullptr, (const int *)nullptr, KQV * KQV, k, k)
 #define QPSK(KQV) do { if (k == KQV) QPS(KQV, true); else QPS(KQV, false); } while (0)
     switch (KQ) { case 4: QPSK(4); break; case 8: QPSK(8); break; case 16: QPSK(16); break; default: QPSK(32); break; }
 #undef QPSK
@@ -2547,8 +2274,6 @@ __global__ __launch_bounds__(256) void k_qp_setup_slots_aa(QpHeader *__restrict_
         h->next_row = 0u;
         h->n_overflow = 0u;
         h->next_overflow = 0u;
-        h->n_long = 0u;
-        h->dbg_rounds = h->dbg_trips = h->dbg_waves = 0u;
         h->pad = 0u;
         h->waves_done = 0u;
     }
@@ -2588,31 +2313,25 @@ int launch_qp_slots_aa(Ctx *c, const aa_qp_params *p)
     // (a single fit orders its samples by their previous pass counts from 4097 samples on: which wave
     // takes a sample does not enter its arithmetic, so the slots go without)
     long waves = (n + 15) / 16;
-    if (waves > g_qp_quad_waves) waves = g_qp_quad_waves;
+    if (waves > QP_QUAD_WAVES) waves = QP_QUAD_WAVES;
     const long rounds = (n + 16 * waves - 1) / (16 * waves);
     const long max_trips = 16 * rounds * ((long)cap + 2) + 16;
-    const int refill = g_qp_quad_refill < 1 ? 1 : (g_qp_quad_refill > 16 ? 16 : g_qp_quad_refill);
     const double *Bt = c->Gr.as<double>();
     double *Zt = c->Zt.as<double>();
     const dim3 grid((unsigned)waves, (unsigned)R);
-#define QQS(KERN)                                                                                         \
-    hipLaunchKernelGGL((KERN<1, true>), grid, dim3(64), 0, c->stream, (const double *)A2d, 32, Bt, (long)1,      \
-                       (long)c->KP, (const double *)bsd, Zt, c->KP, n, k, *p, cap, (int *)nullptr, hdr, ovf_rows, \
-                       ovf, refill, (const int *)nullptr, max_trips, 0, (int *)nullptr, k, n_al)
-    if (g_qp_quad_occ >= 4) QQS(k_qp_quad_w4);
-    else if (g_qp_quad_occ == 3) QQS(k_qp_quad_w3);
-    else QQS(k_qp_quad);
-#undef QQS
+    hipLaunchKernelGGL((k_qp_quad_w3<1, true>), grid, dim3(64), 0, c->stream, (const double *)A2d, 32, Bt, (long)1,
+                       (long)c->KP, (const double *)bsd, Zt, c->KP, n, k, *p, cap, (int *)nullptr, hdr, ovf_rows,
+                       ovf, (const int *)nullptr, max_trips, 0, (int *)nullptr, k, n_al);
     // (a wave per parked sample: no more blocks per slot than a quarter of its samples -- which block
     // continues a sample does not enter its arithmetic, and R x 1024 mostly idle blocks cost 49 us)
     long wblocks = (n + 3) / 4;
     if (wblocks < 64) wblocks = 64;
-    if (wblocks > g_qp_wave_blocks) wblocks = g_qp_wave_blocks;
+    if (wblocks > QP_WAVE_BLOCKS) wblocks = QP_WAVE_BLOCKS;
     if (cap < p->max_iterations)
         QW32_LAUNCH(dim3((unsigned)wblocks, (unsigned)R), dim3(256), 0, c->stream,
                            (const double *)A2d, Bt, (long)1, (long)c->KP, (const double *)bsd, Zt, c->KP, (long)-1, k,
                            *p, (int *)nullptr, hdr, (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                           (const int *)nullptr, (const unsigned int *)nullptr, 1 << 30, (unsigned int *)nullptr,
+                           (const unsigned int *)nullptr, 1 << 30, (unsigned int *)nullptr,
                            (int *)nullptr, (QpCarry *)nullptr, QpLive{0, 0, 0u, 0u, nullptr, nullptr}, k, n_al);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
@@ -2646,12 +2365,12 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
     AA_REQUIRE(p->memory <= QW_MAXMEM, AA_ERR_ARG,
                "QP: memory = %d exceeds the HIP backend limit of %d", p->memory, QW_MAXMEM);
     // scratch layout: QpHeader | A[KQ*KQ] | A2[KW*KW] | bscale[64] | ovf_rows[n] | ovf[n]
-    const size_t off_A = 192;             // QpHeader at 0, QpDebug at 64 (96 bytes)
+    const size_t off_A = 192;             // QpHeader at 0
     const size_t off_A2 = off_A + (size_t)KQ * KQ * sizeof(double);
     const size_t off_bs = off_A2 + (size_t)KW * KW * sizeof(double);
     const size_t off_rows = off_bs + 64 * sizeof(double);
     const size_t off_ovf = off_rows + round_up((long)n * sizeof(int), 16);
-    const size_t off_rows2 = off_ovf + (size_t)n * sizeof(QpCarry);          // second overflow list (qp_tail_cap)
+    const size_t off_rows2 = off_ovf + (size_t)n * sizeof(QpCarry);          // second overflow list (QP_TAIL_CAP)
     const size_t off_ovf2 = off_rows2 + round_up((long)n * sizeof(int), 16);
     const size_t bytes = off_ovf2 + (size_t)n * sizeof(QpCarry);
     AA_CHECK(c->qpStats.alloc(bytes));
@@ -2671,9 +2390,9 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
     // (deferred stragglers: only the two-stage form, whose first stage is an ordinary launch on the main stream)
     const bool defer_ok = defer_tail && !stats && c->stream2 && ldz == c->KP && KW == 32 && c->dtype == AA_F32 &&
                           c->tmpTall.bytes >= (size_t)n * 32 * sizeof(double);
-    const bool two_stage = defer_ok && g_qp_tail_cap > quad_cap && g_qp_tail_cap < p->max_iterations;
+    const bool two_stage = defer_ok && QP_TAIL_CAP > quad_cap && QP_TAIL_CAP < p->max_iterations;
     const bool fused_order = g_qp_fused_order && g_qp_sort && quad_mode && !A_host && KW == 32 && p->memory <= 1 &&
-                             g_qp_wave_mem1 && !g_qp_live && (!defer_ok || two_stage) && quad_cap < p->max_iterations &&
+                             !g_qp_live && (!defer_ok || two_stage) && quad_cap < p->max_iterations &&
                              p->max_iterations > 2 && n > 4096 &&
                              n <= (long)QP_ORDER_MAX_BLOCKS * QP_SORT_ROWS_PER_BLOCK && iters_dev &&
                              iters_dev == c->qpIters.as<int>();
@@ -2725,54 +2444,28 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
 #undef QPP
     } else if (row_mode) {
         // samples ordered by their previous pass count, longest first (iters_dev still holds the
-        // counts of the previous update of this context).  Hybrid: the head of the list -- the
-        // samples that needed >= g_qp_row_long passes last time, ~2 % of them but the whole
-        // critical path -- goes to the wave-per-sample kernel (1 us per pass) on the side stream,
-        // started at once; the row kernel (four samples per wave, ~3 us per pass but four times
-        // the throughput) works off the rest concurrently and hands samples that unexpectedly
-        // reach the pass cap to a second wave-per-sample launch.
+        // counts of the previous update of this context); every sample runs to completion
         const int *perm = nullptr;
-        if (g_qp_profile) AA_CHECK_HIP(hipMemsetAsync(base + 64, 0, 64, c->stream));
-        const bool sorted = will_sort;
-        const bool hybrid = sorted && g_qp_row_long > 0 && c->stream2 && KW == 32 && p->memory <= 1;
-        if (sorted) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, hdr, hybrid ? g_qp_row_long : 0, sort_hist != nullptr));
-        int cap = g_qp_row_cap < 1 ? 1 : g_qp_row_cap;
-        if (p->memory > 1 || p->max_iterations <= cap || KW != 32) cap = p->max_iterations;
-        if (hybrid) {
-            AA_CHECK_HIP(hipEventRecord(c->evFork, c->stream));
-            AA_CHECK_HIP(hipStreamWaitEvent(c->stream2, c->evFork, 0));
-            QW32_LAUNCH(dim3(512), dim3(256), 0, c->stream2, A2d, Btall, stride_j,
-                               stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                               (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr, perm);
-            AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
-        }
+        if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
         long waves = (n + 3) / 4;
-        if (waves > g_qp_row_waves) waves = g_qp_row_waves;
+        if (waves > QP_ROW_WAVES) waves = QP_ROW_WAVES;
         if (k <= 16)
             hipLaunchKernelGGL(k_qp_row<1>, dim3((unsigned)waves), dim3(64), 0, c->stream, A2d, KW, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm,
-                               g_qp_row_hot, g_qp_profile, g_qp_row_chunk, cap, ovf_rows, ovf);
+                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm);
         else
             hipLaunchKernelGGL(k_qp_row<2>, dim3((unsigned)waves), dim3(64), 0, c->stream, A2d, KW, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm,
-                               g_qp_row_hot, g_qp_profile, g_qp_row_chunk, cap, ovf_rows, ovf);
-        if (hybrid) AA_CHECK_HIP(hipStreamWaitEvent(c->stream, c->evJoin, 0));
-        if (cap < p->max_iterations)
-            QW32_LAUNCH(dim3((unsigned)g_qp_wave_blocks), dim3(256), 0, c->stream, A2d, Btall, stride_j,
-                               stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                               (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr);
+                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm);
     } else if (quad_mode) {
         int cap = g_qp_quad_cap > 0 ? g_qp_quad_cap : (n >= 65536 ? 32 : 24);
         if (p->memory > 1 || p->max_iterations <= cap) cap = p->max_iterations;
         long waves = (n + 15) / 16;
-        if (waves > g_qp_quad_waves) waves = g_qp_quad_waves;
+        if (waves > QP_QUAD_WAVES) waves = QP_QUAD_WAVES;
         const int *perm = nullptr;
         hipStream_t s_main = c->stream;
         // watchdog only: a wave's slots take their samples one after the other, each at most
         // cap passes and a start-up trip
         const long rounds = (n + 16 * waves - 1) / (16 * waves);
         const long max_trips = 16 * rounds * ((long)cap + 2) + 16;
-        const int refill = g_qp_quad_refill < 1 ? 1 : (g_qp_quad_refill > 16 ? 16 : g_qp_quad_refill);
         // live hand-over (qp_live): the consumer launch of k_qp_wave goes out FIRST, on the side stream,
         // so that its waves (80 VGPRs) are resident when k_qp_quad fills the rest of every SIMD --
         // the quad kernel then runs at the four-waves-per-SIMD budget (128 VGPRs: 80 + 3 x 128 <= 512)
@@ -2804,39 +2497,26 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                                                  hipFuncAttributeMaxDynamicSharedMemorySize, QP_LIVE_LDS));
                 lds_attr_set = true;
             }
-            hipLaunchKernelGGL(k_qp_wave_live, dim3((unsigned)g_qp_live_blocks), dim3(1024), QP_LIVE_LDS, c->stream3, A2d, Btall,
+            hipLaunchKernelGGL(k_qp_wave_live, dim3((unsigned)QP_LIVE_BLOCKS), dim3(1024), QP_LIVE_LDS, c->stream3, A2d, Btall,
                                stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                               (const int *)nullptr, (const unsigned int *)nullptr, 1 << 30,
+                               (const unsigned int *)nullptr, 1 << 30,
                                (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
             AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream3));
         }
         // (the ordering kernels run while the cross-stream dependency of the consumers resolves: the
         // consumers are resident on their CUs before k_qp_quad fills the chip)
         if (fused_order) perm = use_prefetched ? c->qpPerm.as<int>() : nullptr;   // (the kernel checks QpHeader::pad1)
-        else if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, nullptr, 0, sort_hist != nullptr));
-        const int quad_occ = live ? g_qp_live_occ : g_qp_quad_occ;
+        else if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
         // beside live consumers every wave of k_qp_quad asks for its share of a CU's LDS (see k_qp_wave_live)
-        const unsigned quad_lds = live ? (unsigned)((QP_LIVE_LDS / (4 * quad_occ)) & ~511) : 0u;
+        const unsigned quad_lds = live ? (unsigned)((QP_LIVE_LDS / (4 * QP_QUAD_OCC)) & ~511) : 0u;
         const int live_epoch = lv.epoch;
         int *ovf_ready = lv.ready;
-#define QQK(KERN, MTV, M1V)                                                                         \
-    do {                                                                                            \
-        if (g_qp_quad_lazy && !live)                                                                \
-            hipLaunchKernelGGL((KERN<MTV, M1V, true>), dim3((unsigned)waves), dim3(64), quad_lds, s_main, A2d, KW, Btall, \
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf,   \
-                               refill, perm, max_trips, live_epoch, ovf_ready, 0, 0L);                              \
-        else                                                                                        \
-            hipLaunchKernelGGL((KERN<MTV, M1V, false>), dim3((unsigned)waves), dim3(64), quad_lds, s_main, A2d, KW, Btall, \
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf,   \
-                               refill, perm, max_trips, live_epoch, ovf_ready, 0, 0L);                              \
-    } while (0)
-#define QQL(MTV, M1V)                                                                               \
-    do {                                                                                            \
-        if (quad_occ >= 4) QQK(k_qp_quad_w4, MTV, M1V);                                             \
-        else if (quad_occ == 3) QQK(k_qp_quad_w3, MTV, M1V);                                        \
-        else QQK(k_qp_quad, MTV, M1V);                                                              \
-    } while (0)
+#define QQK(MTV, M1V, LZV)                                                                          \
+    hipLaunchKernelGGL((k_qp_quad_w3<MTV, M1V, LZV>), dim3((unsigned)waves), dim3(64), quad_lds, s_main, A2d, KW, Btall, \
+                       stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf,           \
+                       perm, max_trips, live_epoch, ovf_ready, 0, 0L)
+#define QQL(MTV, M1V) do { if (g_qp_quad_lazy && !live) QQK(MTV, M1V, true); else QQK(MTV, M1V, false); } while (0)
         if (k <= 16) { if (p->memory <= 1) QQL(1, true); else QQL(1, false); }
         else         { if (p->memory <= 1) QQL(2, true); else QQL(2, false); }
 #undef QQL
@@ -2848,7 +2528,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
             QW32_LAUNCH(dim3(64), dim3(256), 0, c->stream, A2d, Btall,
                                stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                               (const int *)nullptr, (const unsigned int *)nullptr, 1 << 30,
+                               (const unsigned int *)nullptr, 1 << 30,
                                (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
         } else if (cap < p->max_iterations) {
             // the parked samples, one wave each.  defer_tail: on the side stream, results to
@@ -2857,13 +2537,13 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
             // dependent chain of the longest sample (100-450 passes at ~0.9 us) hides behind an
             // HBM-bound pass instead of idling the chip
             const bool defer = defer_ok;
-            const int tail_cap = g_qp_tail_cap;
+            const int tail_cap = QP_TAIL_CAP;
             if (defer && tail_cap > cap && tail_cap < p->max_iterations) {
                 // two stages: everything up to tail_cap passes here, at full speed on the whole chip;
                 // the few samples beyond it on the side stream beside the caller's Z'X pass
                 if (fused_order) {
                     const QpOrder od{iters_dev, c->qpPerm.as<int>(), c->qpPerm.as<int>() + n, n, order_blocks};
-                    const dim3 og((unsigned)(g_qp_wave_blocks + order_blocks));
+                    const dim3 og((unsigned)(QP_WAVE_BLOCKS + order_blocks));
                     if (g_qp_wave_lazy)
                         hipLaunchKernelGGL(k_qp_wave_ord<true>, og, dim3(256), 0, c->stream, od, A2d, Btall, stride_j,
                                            stride_t, bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
@@ -2875,10 +2555,10 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                     c->qp_perm_ready = true;
                     c->qp_perm_n = n;
                 } else
-                QW32_LAUNCH(dim3((unsigned)g_qp_wave_blocks), dim3(256), 0, c->stream, A2d, Btall,
+                QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, c->stream, A2d, Btall,
                                    stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                                   (const int *)nullptr, (const unsigned int *)nullptr, tail_cap, &hdr->pad, ovf2_rows, ovf2);
+                                   (const unsigned int *)nullptr, tail_cap, &hdr->pad, ovf2_rows, ovf2);
                 // the handful beyond tail_cap on the side stream.  (Tried: a CU-masked stream pair,
                 // hipExtStreamCreateWithCUMask -- 8 or 16 CUs for these chains alone, the rest of the chip for
                 // the caller's pass, so that the two share no SIMD.  With masked queues alive EVERY launch of the
@@ -2890,7 +2570,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                 QW32_LAUNCH(dim3(64), dim3(256), 0, ss, A2d, Btall,
                                    stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf2_rows, (const QpCarry *)ovf2, c->tmpTall.as<double>(),
-                                   (const int *)nullptr, (const unsigned int *)&hdr->pad);
+                                   (const unsigned int *)&hdr->pad);
                 AA_CHECK_HIP(hipEventRecord(c->evJoin, ss));
                 c->qp_tail_pending = true;
                 c->qp_tail_rows = ovf2_rows;
@@ -2906,21 +2586,21 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                 }
                 if (fused_order && !defer) {
                     const QpOrder od{iters_dev, c->qpPerm.as<int>(), c->qpPerm.as<int>() + n, n, order_blocks};
-                    const dim3 og((unsigned)(g_qp_wave_blocks + order_blocks));
+                    const dim3 og((unsigned)(QP_WAVE_BLOCKS + order_blocks));
                     if (g_qp_wave_lazy)
                         hipLaunchKernelGGL(k_qp_wave_ord<true>, og, dim3(256), 0, s2, od, A2d, Btall, stride_j, stride_t,
                                            bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
                                            (const QpCarry *)ovf, 1 << 30, (unsigned int *)nullptr, (int *)nullptr,
-                                           (QpCarry *)nullptr, g_qp_wave_queue);
+                                           (QpCarry *)nullptr);
                     else
                         hipLaunchKernelGGL(k_qp_wave_ord<false>, og, dim3(256), 0, s2, od, A2d, Btall, stride_j, stride_t,
                                            bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
                                            (const QpCarry *)ovf, 1 << 30, (unsigned int *)nullptr, (int *)nullptr,
-                                           (QpCarry *)nullptr, g_qp_wave_queue);
+                                           (QpCarry *)nullptr);
                     c->qp_perm_ready = true;
                     c->qp_perm_n = n;
                 } else
-                QW32_LAUNCH(dim3((unsigned)g_qp_wave_blocks), dim3(256), 0, s2, A2d, Btall, stride_j,
+                QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
                                    stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
                 if (defer) {
@@ -2948,32 +2628,19 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         // one wave per SIMD: lanes that finish early pull further samples, so a wave's
         // trip count is the sum over ~n/65536 samples per lane instead of two full rounds
         long waves = (n + 63) / 64;
-        if (waves > g_qp_waves) waves = g_qp_waves;
+        if (waves > QP_WAVES) waves = QP_WAVES;
         dim3 grid((unsigned)waves);
         // samples ordered by their previous pass count (iters_dev still holds the counts of
         // the previous update of this context; the kernels below overwrite them)
         const int *perm = nullptr;
-        if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, nullptr, 0, sort_hist != nullptr));
-        QpDebug *dbgp = g_qp_profile ? reinterpret_cast<QpDebug *>(base + 64) : (QpDebug *)nullptr;
-        if (dbgp) AA_CHECK_HIP(hipMemsetAsync(dbgp, 0, sizeof(QpDebug), c->stream));
-#define QPL4(KQV, FULLV, PROFV, SGV)                                                          \
-    hipLaunchKernelGGL((k_qp<KQV, FULLV, PROFV, SGV>), grid, dim3(64), 0, c->stream, Ad, Btall, stride_j,  \
-                       stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf,  \
-                       g_qp_refill_min, dbgp, perm)
-#define QPL3(KQV, FULLV, PROFV)                                                               \
-    do {                                                                                      \
-        if (g_qp_matvec == 1 && KQV >= 16) QPL4(KQV, FULLV, PROFV, true);                     \
-        else QPL4(KQV, FULLV, PROFV, false);                                                  \
-    } while (0)
-#define QPL(KQV)                                                                              \
-    do {                                                                                      \
-        if (dbgp) { if (k == KQV) QPL3(KQV, true, true); else QPL3(KQV, false, true); }       \
-        else      { if (k == KQV) QPL3(KQV, true, false); else QPL3(KQV, false, false); }     \
-    } while (0)
+        if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
+#define QPL2(KQV, FULLV)                                                                       \
+    hipLaunchKernelGGL((k_qp<KQV, FULLV>), grid, dim3(64), 0, c->stream, Ad, Btall, stride_j,  \
+                       stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf, perm)
+#define QPL(KQV) do { if (k == KQV) QPL2(KQV, true); else QPL2(KQV, false); } while (0)
         switch (KQ) { case 4: QPL(4); break; case 8: QPL(8); break; case 16: QPL(16); break;
                       default: QPL(32); break; }
-#undef QPL4
-#undef QPL3
+#undef QPL2
 #undef QPL
         if (cap < p->max_iterations) {
             // phase 2: the stragglers, one wave each (grid is fixed; the count is read on
@@ -2989,7 +2656,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                 s2 = c->stream2;
                 zslot = c->tmpTall.as<double>();
             }
-            QW32_LAUNCH(dim3((unsigned)g_qp_wave_blocks), dim3(256), 0, s2, A2d, Btall, stride_j,
+            QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
                                stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
             if (defer) {
@@ -3008,39 +2675,6 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         stats->total_passes = (long)h.total_passes;
         stats->max_passes = (int)h.max_passes;
         stats->reserved = (int)h.n_overflow;
-        if (g_qp_profile && row_mode && h.dbg_waves) {
-            unsigned long long d5[5];
-            AA_CHECK_HIP(ctx_memcpy(c, d5, base + 64, sizeof(d5), hipMemcpyDeviceToHost));
-            fprintf(stderr, "[qp_profile] row kernel waves: slowest %.0f kcycles (its trips %llu), mean %.0f kcycles; "
-                    "most trips %llu (that wave: %.0f kcycles = %.0f cycles per trip)\n",
-                    (double)(d5[1] >> 20) / 1e3, d5[1] & 0xfffffull, (double)d5[3] / h.dbg_waves / 1e3,
-                    d5[4] >> 40, (double)(d5[4] & ((1ull << 40) - 1ull)) / 1e3,
-                    (double)(d5[4] & ((1ull << 40) - 1ull)) / (double)(d5[4] >> 40));
-        }
-        if (g_qp_profile && row_mode && h.dbg_waves)
-            fprintf(stderr, "[qp_profile] row kernel: %u waves, %.1f trips per wave, %.2f Michelot rounds per "
-                    "row and trip, %.2f passes per sample, %u predicted-long samples on the side stream, "
-                    "%u handed over at the pass cap\n", h.dbg_waves, (double)h.dbg_trips / h.dbg_waves,
-                    (double)h.dbg_rounds / (4.0 * h.dbg_trips), (double)h.total_passes / (double)n, h.n_long,
-                    h.n_overflow);
-        if (g_qp_profile && quad_mode && h.dbg_trips)
-            fprintf(stderr, "[qp_profile] four-lane kernel, lazy stopping test: %u trips owed a test, %u of them (%.1f %%) "
-                    "skipped it for the whole wave\n", h.dbg_trips, h.dbg_rounds, 100.0 * h.dbg_rounds / h.dbg_trips);
-        if (g_qp_profile && !row_mode) {
-            QpDebug d;
-            AA_CHECK_HIP(ctx_memcpy(c, &d, base + 64, sizeof(d), hipMemcpyDeviceToHost));
-            if (d.waves)
-                fprintf(stderr, "[qp_profile] waves %llu trips/wave %.1f refills/wave %.1f cycles/wave %.0f "
-                        "(projection part %.1f%%, mat-vec %.1f%%, step %.1f%%, residual+finish %.1f%%) cycles/trip %.0f\n",
-                        d.waves, (double)d.trips / d.waves, (double)d.refills / d.waves,
-                        (double)d.cyc_total / d.waves, 100.0 * d.cyc_proj / d.cyc_total,
-                        100.0 * d.cyc_matvec / d.cyc_total, 100.0 * d.cyc_step / d.cyc_total,
-                        100.0 * d.cyc_fin / d.cyc_total, (double)d.cyc_total / d.trips);
-            if (d.waves && d.proj_lanes)
-                fprintf(stderr, "[qp_profile] Michelot rounds per projection: lane mean %.2f, wave max (residual "
-                        "projection) %.2f\n", (double)d.proj_rounds_lanesum / d.proj_lanes,
-                        (double)d.proj_rounds_wavemax / d.proj_calls);
-        }
     }
     return AA_OK;
 }

@@ -2235,8 +2235,6 @@ int g_proj_check_always = 0; // multi-rank: 1 = every list projection is checked
                              // polls (seen: the residual projection a few iterations after a FurthestSum start) then
                              // ends the fit with an error instead of being handled
 int g_pq_mfma = 1;              // the line search's two wide Grams on the f64 matrix cores (k_gram_wide_pq_mfma)
-int g_pq_blocks = 128;          // most blocks of k_gram_wide_pq (their partial Grams are summed by ONE block; 64 -> 128:
-                                // C2, p = 25 000, 0.553 -> 0.537 ms per iteration; 256: 0.548)
 int g_pack_comm = 1;            // multi-rank: small reductions ride in the tail of the next all-reduce (Ctx::ride*)
 int g_setup_in_grad = 1;        // the dictionary update's set-up block inside its first gradient launch (DictSetup)
 int g_gram_side = 0;            // Z'Z of the refresh after a weights update on the side stream, beside the Z'X pass
@@ -3697,8 +3695,10 @@ int launch_gram_wide(Ctx *c, const double *A, const double *B, double *out_dev)
 int launch_linesearch_fused(Ctx *c, const aa_spg_params *sp, double *cost_out, int *cost_slot)
 {
     const long chunks = c->p_pad / 128;
-    const int mb = g_pq_blocks < 1 ? 1 : g_pq_blocks;
-    const int cpb = (int)((chunks + mb - 1) / mb) * 128;      // columns per block: <= g_pq_blocks blocks
+    // most blocks of k_gram_wide_pq: their partial Grams are summed by ONE block (64 -> 128: C2,
+    // p = 25 000, 0.553 -> 0.537 ms per iteration; 256: 0.548)
+    constexpr int PQ_BLOCKS = 128;
+    const int cpb = (int)((chunks + PQ_BLOCKS - 1) / PQ_BLOCKS) * 128;      // columns per block
     const int nb = (int)((c->p_pad + cpb - 1) / cpb);
     double *part = c->redPartial.as<double>();
     double *ckct = c->gramState.as<double>() + (size_t)c->KP * c->KP;

@@ -17,6 +17,7 @@
 // sigma_one is an absolute bound (spg.py:28).
 #include "aa_internal.h"
 
+#include <climits>
 #include <mutex>
 
 namespace aa {
@@ -73,7 +74,8 @@ static int ensure_problem(Ctx *c, int k)
     }
     // split-row decomposition of the reduce-over-rows GEMM
     const long colgroups = c->dtype == AA_F32 ? (c->p_pad + 511) / 512 : (c->p_pad + 255) / 256;
-    long nslab = (g_reduce_rows_blocks + colgroups - 1) / colgroups;   // 2 blocks per CU: 64 slabs at p = 4096
+    constexpr long REDUCE_ROWS_BLOCKS = 512;      // target block count, 2 per CU: 64 slabs at p = 4096
+    long nslab = (REDUCE_ROWS_BLOCKS + colgroups - 1) / colgroups;
     if (nslab > 256) nslab = 256;
     if (nslab < 1) nslab = 1;
     long rps = round_up((c->n_pad + nslab - 1) / nslab, 32);
@@ -538,156 +540,55 @@ extern "C" {
 const char *aa_last_error(void) { return g_err.c_str(); }
 int aa_version(void) { return 100; }
 
+// One row per knob.  flag: any value is accepted and stored as value != 0; otherwise the value must lie
+// in lo..hi.  The option comment of include/aa_hip.h lists exactly these names (tests/test_cpu_host.py).
+struct AaOption {
+    const char *name;
+    int *target;
+    int lo, hi;
+    bool flag;
+};
+static const AaOption kOptions[] = {
+    {"row_local_variant", &g_row_local_variant, -1, 9, false},
+    {"row_local_acc64", &g_row_local_acc64, 0, 2, false},
+    {"row_local_split", &g_row_local_split, 0, 1, true},
+    {"f64_mfma", &g_f64_mfma, 0, 3, false},
+    {"proj_mode", &g_proj_mode, 0, 1, false},
+    {"proj_small", &g_proj_small, INT_MIN, INT_MAX, false},
+    {"proj_list_cap", &g_proj_list_cap, 1, 2048, false},
+    {"proj_check", &g_proj_check_always, 0, 1, true},
+    {"proj_res_side", &g_proj_res_side, 0, 1, true},   // takes effect at the next aa_set_state of a new problem size
+    {"fuse_finalize", &g_fuse_finalize, 0, 1, true},
+    {"use_graph", &g_use_graph, 0, 1, true},
+    {"outer_nosync", &g_outer_nosync, 0, 1, true},
+    {"pq_mfma", &g_pq_mfma, 0, 1, true},
+    {"qp_mode", &g_qp_mode, 0, 4, false},
+    {"qp_pass_cap", &g_qp_pass_cap, 1, INT_MAX, false},
+    {"qp_quad_cap", &g_qp_quad_cap, 0, INT_MAX, false},
+    {"qp_sort", &g_qp_sort, 0, 1, true},
+    {"qp_live", &g_qp_live, 0, 1, true},
+    {"qp_overlap_tail", &g_qp_overlap_tail, 0, 1, true},
+    {"qp_fused_order", &g_qp_fused_order, 0, 1, true},
+    {"qp_wave_lazy", &g_qp_wave_lazy, 0, 1, true},
+    {"qp_quad_lazy", &g_qp_quad_lazy, 0, 1, true},
+    {"fin_in_last", &g_fin_in_last, 0, 1, true},
+    {"setup_in_grad", &g_setup_in_grad, 0, 1, true},
+    {"gram_side", &g_gram_side, 0, 1, true},
+    {"grad_side", &g_grad_side, 0, 1, true},
+    {"pack_comm", &g_pack_comm, 0, 1, true},
+};
+
 int aa_set_option(const char *name, int value)
 {
     AA_REQUIRE(name != nullptr, AA_ERR_ARG, "null option name");
-    if (!strcmp(name, "row_local_variant")) {
-        AA_REQUIRE(value >= -1 && value <= 9, AA_ERR_ARG, "row_local_variant must be in -1..9");
-        g_row_local_variant = value;
-    } else if (!strcmp(name, "qp_pass_cap")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "qp_pass_cap must be >= 1");
-        g_qp_pass_cap = value;
-    } else if (!strcmp(name, "qp_refill_min")) {
-        AA_REQUIRE(value >= 1 && value <= 64, AA_ERR_ARG, "qp_refill_min must be in 1..64");
-        g_qp_refill_min = value;
-    } else if (!strcmp(name, "row_local_waves")) {
-        AA_REQUIRE(value == 0 || (value >= 8 && value <= 16), AA_ERR_ARG, "row_local_waves must be 0 or 8..16");
-        g_row_local_waves = value;
-    } else if (!strcmp(name, "row_local_acc64")) {
-        AA_REQUIRE(value >= 0 && value <= 2, AA_ERR_ARG, "row_local_acc64 must be 0, 1 or 2");
-        g_row_local_acc64 = value;
-    } else if (!strcmp(name, "row_local_ring")) {
-        AA_REQUIRE(value == 0 || (value >= 8 && value <= 12), AA_ERR_ARG, "row_local_ring must be 0 or 8..12");
-        g_row_local_ring = value;
-    } else if (!strcmp(name, "row_local_nt")) {
-        g_row_local_nt = value != 0;
-    } else if (!strcmp(name, "row_local_early")) {
-        g_row_local_early = value != 0;
-    } else if (!strcmp(name, "row_local_prio")) {
-        g_row_local_prio = value != 0;
-    } else if (!strcmp(name, "row_local_reverse")) {
-        g_row_local_reverse = value != 0;
-    } else if (!strcmp(name, "row_local_chunk")) {
-        AA_REQUIRE(value >= 0, AA_ERR_ARG, "row_local_chunk must be >= 0");
-        g_row_local_chunk = value;
-    } else if (!strcmp(name, "row_local_split")) {
-        g_row_local_split = value != 0;
-    } else if (!strcmp(name, "f64_mfma")) {
-        AA_REQUIRE(value >= 0 && value <= 3, AA_ERR_ARG, "f64_mfma must be in 0..3");
-        g_f64_mfma = value;
-    } else if (!strcmp(name, "reduce_rows_unroll")) {
-        AA_REQUIRE(value == 4 || value == 8, AA_ERR_ARG, "reduce_rows_unroll must be 4 or 8");
-        g_reduce_rows_unroll = value;
-    } else if (!strcmp(name, "reduce_rows_blocks")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "reduce_rows_blocks must be >= 1");
-        g_reduce_rows_blocks = value;      // takes effect at the next aa_set_state
-    } else if (!strcmp(name, "row_local_stagger")) {
-        AA_REQUIRE(value >= 0, AA_ERR_ARG, "row_local_stagger must be >= 0");
-        g_row_local_stagger = value;
-    } else if (!strcmp(name, "proj_list_cap")) {
-        AA_REQUIRE(value >= 1 && value <= 2048, AA_ERR_ARG, "proj_list_cap must be in 1..2048");
-        g_proj_list_cap = value;
-    } else if (!strcmp(name, "proj_mode")) {
-        AA_REQUIRE(value == 0 || value == 1, AA_ERR_ARG, "proj_mode must be 0 or 1");
-        g_proj_mode = value;
-    } else if (!strcmp(name, "proj_check")) {
-        g_proj_check_always = value != 0;
-    } else if (!strcmp(name, "fuse_finalize")) {
-        g_fuse_finalize = value != 0;
-    } else if (!strcmp(name, "qp_wave_queue")) {
-        g_qp_wave_queue = value != 0;
-    } else if (!strcmp(name, "qp_quad_lazy")) {
-        g_qp_quad_lazy = value != 0;
-    } else if (!strcmp(name, "pack_comm")) {
-        g_pack_comm = value != 0;
-    } else if (!strcmp(name, "setup_in_grad")) {
-        g_setup_in_grad = value != 0;
-    } else if (!strcmp(name, "gram_side")) {
-        g_gram_side = value != 0;
-    } else if (!strcmp(name, "fin_in_last")) {
-        g_fin_in_last = value != 0;
-    } else if (!strcmp(name, "qp_fused_order")) {
-        g_qp_fused_order = value != 0;
-    } else if (!strcmp(name, "grad_side")) {
-        g_grad_side = value != 0;
-    } else if (!strcmp(name, "qp_wave_lazy")) {
-        g_qp_wave_lazy = value != 0;
-    } else if (!strcmp(name, "qp_wave_mem1")) {
-        g_qp_wave_mem1 = value != 0;
-    } else if (!strcmp(name, "qp_overlap_tail")) {
-        g_qp_overlap_tail = value != 0;
-    } else if (!strcmp(name, "qp_tail_cap")) {
-        AA_REQUIRE(value >= 0, AA_ERR_ARG, "qp_tail_cap must be >= 0");
-        g_qp_tail_cap = value;
-    } else if (!strcmp(name, "use_graph")) {
-        g_use_graph = value != 0;
-    } else if (!strcmp(name, "pq_mfma")) {
-        g_pq_mfma = value != 0;
-    } else if (!strcmp(name, "pq_blocks")) {
-        AA_REQUIRE(value >= 1 && value <= 1024, AA_ERR_ARG, "pq_blocks must be in 1..1024");
-        g_pq_blocks = value;
-    } else if (!strcmp(name, "proj_res_side")) {
-        g_proj_res_side = value != 0;      // takes effect at the next aa_set_state of a new problem size
-    } else if (!strcmp(name, "proj_small")) {
-        g_proj_small = value;
-    } else if (!strcmp(name, "qp_profile")) {
-        g_qp_profile = value != 0;
-    } else if (!strcmp(name, "qp_sort")) {
-        g_qp_sort = value != 0;
-    } else if (!strcmp(name, "qp_waves")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "qp_waves must be >= 1");
-        g_qp_waves = value;
-    } else if (!strcmp(name, "qp_mode")) {
-        AA_REQUIRE(value >= 0 && value <= 4, AA_ERR_ARG, "qp_mode must be in 0..4");
-        g_qp_mode = value;
-    } else if (!strcmp(name, "qp_quad_waves")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "qp_quad_waves must be >= 1");
-        g_qp_quad_waves = value;
-    } else if (!strcmp(name, "qp_quad_refill")) {
-        AA_REQUIRE(value >= 1 && value <= 16, AA_ERR_ARG, "qp_quad_refill must be in 1..16");
-        g_qp_quad_refill = value;
-    } else if (!strcmp(name, "qp_wave_blocks")) {
-        AA_REQUIRE(value >= 1 && value <= 8192, AA_ERR_ARG, "qp_wave_blocks must be in 1..8192");
-        g_qp_wave_blocks = value;
-    } else if (!strcmp(name, "outer_nosync")) {
-        g_outer_nosync = value != 0;
-    } else if (!strcmp(name, "qp_live")) {
-        g_qp_live = value ? 1 : 0;
-    } else if (!strcmp(name, "qp_live_occ")) {
-        AA_REQUIRE(value >= 2 && value <= 4, AA_ERR_ARG, "qp_live_occ must be 2, 3 or 4");
-        g_qp_live_occ = value;
-    } else if (!strcmp(name, "qp_live_blocks")) {
-        AA_REQUIRE(value >= 1 && value <= 128, AA_ERR_ARG, "qp_live_blocks must be in 1..128");
-        g_qp_live_blocks = value;
-    } else if (!strcmp(name, "qp_quad_occ")) {
-        AA_REQUIRE(value >= 2 && value <= 4, AA_ERR_ARG, "qp_quad_occ must be 2, 3 or 4");
-        g_qp_quad_occ = value;
-    } else if (!strcmp(name, "qp_quad_cap")) {
-        AA_REQUIRE(value >= 0, AA_ERR_ARG, "qp_quad_cap must be >= 0");
-        g_qp_quad_cap = value;
-    } else if (!strcmp(name, "qp_row_waves")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "qp_row_waves must be >= 1");
-        g_qp_row_waves = value;
-    } else if (!strcmp(name, "qp_row_chunk")) {
-        AA_REQUIRE(value >= 0 && value <= 4096, AA_ERR_ARG, "qp_row_chunk must be in 0..4096");
-        g_qp_row_chunk = value;
-    } else if (!strcmp(name, "qp_matvec")) {
-        AA_REQUIRE(value == 0 || value == 1, AA_ERR_ARG, "qp_matvec must be 0 or 1");
-        g_qp_matvec = value;
-    } else if (!strcmp(name, "qp_row_long")) {
-        AA_REQUIRE(value >= 0 && value < 64, AA_ERR_ARG, "qp_row_long must be in 0..63");
-        g_qp_row_long = value;
-    } else if (!strcmp(name, "qp_row_cap")) {
-        AA_REQUIRE(value >= 1, AA_ERR_ARG, "qp_row_cap must be >= 1");
-        g_qp_row_cap = value;
-    } else if (!strcmp(name, "qp_row_hot")) {
-        AA_REQUIRE(value >= 0, AA_ERR_ARG, "qp_row_hot must be >= 0");
-        g_qp_row_hot = value;
-    } else {
-        set_error("unknown option '%s'", name);
-        return AA_ERR_ARG;
+    for (const AaOption &o : kOptions) {
+        if (strcmp(name, o.name)) continue;
+        AA_REQUIRE(o.flag || (value >= o.lo && value <= o.hi), AA_ERR_ARG, "%s must be in %d..%d", o.name, o.lo, o.hi);
+        *o.target = o.flag ? (value != 0) : value;
+        return AA_OK;
     }
-    return AA_OK;
+    set_error("unknown option '%s'", name);
+    return AA_ERR_ARG;
 }
 
 int aa_device_count(int *count)
@@ -2339,10 +2240,9 @@ int aa_quad_simplex_spg_batch(int device, const double *A, const double *B, long
             rc = AA_ERR_HIP;
         }
     }
-    aa_qp_stats prof_stats;
     if (rc == AA_OK)
         rc = launch_qp(c, A, dB.as<double>(), stride_j, stride_t, nullptr, dZ.as<double>(), k, n, k, params,
-                       dI.as<int>(), g_qp_profile ? &prof_stats : (aa_qp_stats *)nullptr);
+                       dI.as<int>(), (aa_qp_stats *)nullptr);
     if (rc == AA_OK) {
         hipError_t e = hipStreamSynchronize(c->stream);
         if (e == hipSuccess) e = ctx_memcpy(c, Zout, dZ.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost);

@@ -37,6 +37,30 @@ def test_library_exports_every_declared_symbol():
     assert _backend.load_library().aa_version() >= 100
 
 
+@needs_lib
+def test_option_comment_lists_exactly_the_dispatcher_table():
+    """The option comment of include/aa_hip.h and the table behind aa_set_option name the same knobs,
+    a retired knob is an unknown option, and a listed one is accepted."""
+    header = open(HEADER).read()
+    comment = re.search(r"/\* Process-wide tuning knobs.*?\*/\s*int aa_set_option", header, flags=re.S).group(0)
+    quoted = re.findall(r'"([a-z_0-9]+)"', comment)
+    assert len(quoted) == len(set(quoted)), sorted(n for n in set(quoted) if quoted.count(n) > 1)
+    solver = open(os.path.join(os.path.dirname(LIB), "csrc", "solver.hip")).read()
+    table = re.search(r"static const AaOption kOptions\[\] = \{(.*?)\n\};", solver, flags=re.S).group(1)
+    rows = re.findall(r'^\s*\{"([a-z_0-9]+)",\s*&g_', table, flags=re.M)
+    assert len(rows) >= 20 and len(rows) == len(set(rows))
+    assert set(quoted) == set(rows)
+
+    lib = _backend.load_library()
+    for gone in ("qp_matvec", "row_local_ring"):
+        assert gone not in rows
+        assert lib.aa_set_option(gone.encode(), 0) != 0
+        assert "unknown option" in lib.aa_last_error().decode()
+    assert lib.aa_set_option(b"qp_mode", 0) == 0
+    assert lib.aa_set_option(b"qp_mode", 5) != 0                 # the range check of the same loop
+    assert "qp_mode must be in 0..4" in lib.aa_last_error().decode()
+
+
 def _gpu_present():
     try:
         _backend.require_gpu()

@@ -35,7 +35,6 @@ print("lane kernel: n=65536 (1024 waves), 16 extra forced passes: %.3f ms -> %.2
       % (1e3 * (t - t1), 1e6 * (t - t1) / 16), flush=True)
 
 _backend.set_option("qp_mode", 3)
-_backend.set_option("qp_profile", 1)
 for nn in (4, 8192, 65536):
     A, B, Z0 = problem(nn, k)
     t1, _ = timed(A, B, Z0, max_iterations=1, epsilon_two=0.0, epsilon_one=0.0)

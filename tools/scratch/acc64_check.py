@@ -22,18 +22,16 @@ want = X[rows].astype(np.float64).dot(B.T)
 scale = np.abs(X[rows]).astype(np.float64).dot(np.abs(B).T)
 with _backend.Context(dtype="float32") as ctx:
     ctx.set_data(X)
-    for a64, waves in ((0, 0), (1, 0), (1, 12), (1, 11), (1, 10), (0, 12), (0, 0), (1, 0)):
+    for a64 in (0, 1, 0, 1):
         _backend.set_option("row_local_acc64", a64)
-        _backend.set_option("row_local_waves", waves)
         got = ctx.pass_row_local(B)[rows]
         err = np.abs(got - want) / scale
         ctx.set_state(C0, Z0, np.ones(k))
         ctx.prepare()
         ctx.time_kernel(1, 5)
         ms = ctx.time_kernel(1, 40)
-        print("acc64 %d waves %2d: %.4f ms  %.2f TB/s | err / sum|x||b|: rms %.2e max %.2e" %
-              (a64, waves, ms, n * p * 4 / ms / 1e9, np.sqrt((err ** 2).mean()), err.max()), flush=True)
-    _backend.set_option("row_local_waves", 0)
+        print("acc64 %d: %.4f ms  %.2f TB/s | err / sum|x||b|: rms %.2e max %.2e" %
+              (a64, ms, n * p * 4 / ms / 1e9, np.sqrt((err ** 2).mean()), err.max()), flush=True)
     for a64 in (0, 1, 0, 1):
         _backend.set_option("row_local_acc64", a64)
         ctx.set_state(C0, Z0, np.ones(k))

@@ -107,12 +107,11 @@ def main():
         return hC, hZ, costs
 
     DEFAULTS = dict(qp_mode=0, qp_quad_cap=0, qp_pass_cap=24, row_local_split=1, row_local_variant=-1, f64_mfma=1,
-                    proj_small=1, proj_mode=0, qp_sort=1, fuse_finalize=1, pq_blocks=128, qp_quad_occ=3)
+                    proj_small=1, proj_mode=0, qp_sort=1, fuse_finalize=1)
     configs = [{}, dict(qp_mode=1), dict(qp_mode=2), dict(qp_mode=3), dict(qp_mode=4),
                dict(qp_quad_cap=1), dict(qp_quad_cap=8), dict(qp_quad_cap=1000),
                dict(qp_mode=2, qp_pass_cap=1000), dict(row_local_split=0), dict(f64_mfma=0), dict(f64_mfma=3),
-               dict(proj_small=0), dict(proj_mode=1), dict(qp_sort=0), dict(fuse_finalize=0), dict(pq_blocks=16),
-               dict(qp_quad_occ=2)]
+               dict(proj_small=0), dict(proj_mode=1), dict(qp_sort=0), dict(fuse_finalize=0)]
     # oracle cost curve in trace form for the first-departure search: use residual-form checkpoints instead
     o_curve = np.array(o_costs)
     for dtype in ("float64", "float32"):

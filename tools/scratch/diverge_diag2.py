@@ -95,10 +95,8 @@ def main():
             ("f32_split0_qpmode1", "float32", dict(row_local_split=0, qp_mode=1)),
             ("f32_split1_qpmode2", "float32", dict(row_local_split=1, qp_mode=2)),
             ("f32_split0_qpmode2", "float32", dict(row_local_split=0, qp_mode=2)),
-            ("f32_split1_rr256", "float32", dict(row_local_split=1, reduce_rows_blocks=256)),
-            ("f32_split0_rr256", "float32", dict(row_local_split=0, reduce_rows_blocks=256)),
             ("f64", "float64", {})]
-    defaults = dict(row_local_split=1, qp_mode=0, reduce_rows_blocks=512)
+    defaults = dict(row_local_split=1, qp_mode=0)
     for tag, dtype, opts in runs:
         for name, v in opts.items():
             _backend.set_option(name, v)

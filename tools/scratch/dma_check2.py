@@ -22,11 +22,9 @@ res = {}
 with _backend.Context(dtype="float32") as ctx:
     ctx.set_data(X)
     for tag, opts in (("ws (variant 8)", dict(row_local_variant=8)),
-                      ("dma ring 8", dict(row_local_variant=9, row_local_ring=8)),
-                      ("dma ring 8 nt", dict(row_local_variant=9, row_local_ring=8, row_local_nt=1)),
-                      ("dma ring 11", dict(row_local_variant=9, row_local_ring=11)),
+                      ("dma (variant 9)", dict(row_local_variant=9)),
                       ("ws (variant 8)", dict(row_local_variant=8)),
-                      ("dma ring 8", dict(row_local_variant=9, row_local_ring=8))):
+                      ("dma (variant 9)", dict(row_local_variant=9))):
         for name, v in opts.items():
             _backend.set_option(name, v)
         ctx.set_state(C0, Z0, np.ones(k))
