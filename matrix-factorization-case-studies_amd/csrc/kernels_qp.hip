@@ -2146,6 +2146,32 @@ __global__ __launch_bounds__(256) void k_qp_wave_ord(QpOrder od, const double *_
                                  QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, (unsigned int)od.blocks);
 }
 
+// The set-up kernels' shared pieces (k_qp_setup, k_qp_setup_slots, k_qp_setup_slots_aa).  One thread: the
+// header's counters to zero (pad1 is k_qp_setup's own).
+__device__ __forceinline__ void qp_header_reset(QpHeader *__restrict__ h)
+{
+    h->total_passes = 0ull;
+    h->max_passes = 0ull;
+    h->next_row = 0u;
+    h->n_overflow = 0u;
+    h->next_overflow = 0u;
+    h->pad = 0u;
+    h->waves_done = 0u;
+}
+
+// dst [K][K] = D G D for the k x k block at `gram` (row stride KP) and its k entries of alpha, zero padding;
+// 256 threads.  A null alpha means unscaled, dst = G (the GPNH slots): the same bits as scaling by 1.0, since
+// a multiplication by 1 is exact and there is no addition to contract with.
+__device__ __forceinline__ void qp_fill_hessian(double *__restrict__ dst, int K, const double *__restrict__ gram,
+                                                const double *__restrict__ alpha, int k, int KP)
+{
+    for (int e = threadIdx.x; e < K * K; e += 256) {
+        const int i = e / K, j = e % K;
+        if (alpha) dst[e] = (i < k && j < k) ? alpha[i] * gram[i * KP + j] * alpha[j] : 0.0;
+        else dst[e] = (i < k && j < k) ? gram[i * KP + j] : 0.0;
+    }
+}
+
 // device-side set-up of the QP scratch: header zeroed, A = D G D padded to KQ and KW,
 // b-scale = D.  One block.
 __global__ __launch_bounds__(256) void k_qp_setup(QpHeader *__restrict__ hdr, double *__restrict__ Ad,
@@ -2165,22 +2191,10 @@ __global__ __launch_bounds__(256) void k_qp_setup(QpHeader *__restrict__ hdr, do
     if (sort_hist && t < QP_ORDER_AREA) sort_hist[t] = 0;   // histogram + cursors (+ flags) of the ordering
     if (t == 0) {
         hdr->pad1 = (unsigned int)order_ok;
-        hdr->total_passes = 0ull;
-        hdr->max_passes = 0ull;
-        hdr->next_row = 0u;
-        hdr->n_overflow = 0u;
-        hdr->next_overflow = 0u;
-        hdr->pad = 0u;
-        hdr->waves_done = 0u;
+        qp_header_reset(hdr);
     }
-    for (int e = t; e < KQ * KQ; e += 256) {
-        const int i = e / KQ, j = e % KQ;
-        Ad[e] = (i < k && j < k) ? alpha[i] * gram[i * KP + j] * alpha[j] : 0.0;
-    }
-    for (int e = t; e < KW * KW; e += 256) {
-        const int i = e / KW, j = e % KW;
-        A2d[e] = (i < k && j < k) ? alpha[i] * gram[i * KP + j] * alpha[j] : 0.0;
-    }
+    qp_fill_hessian(Ad, KQ, gram, alpha, k, KP);
+    qp_fill_hessian(A2d, KW, gram, alpha, k, KP);
     if (t < 64) bsd[t] = t < k ? alpha[t] : 1.0;
 }
 
@@ -2208,21 +2222,8 @@ __global__ __launch_bounds__(256) void k_qp_setup_slots(QpHeader *__restrict__ h
                                                         const double *__restrict__ gram, int k, int KQ, int KP)
 {
     const int t = threadIdx.x, r = blockIdx.x, o = r * k;
-    if (t == 0) {
-        QpHeader *h = hdr + r;
-        h->total_passes = 0ull;
-        h->max_passes = 0ull;
-        h->next_row = 0u;
-        h->n_overflow = 0u;
-        h->next_overflow = 0u;
-        h->pad = 0u;
-        h->waves_done = 0u;
-    }
-    double *A = Ad + (size_t)r * KQ * KQ;
-    for (int e = t; e < KQ * KQ; e += 256) {
-        const int i = e / KQ, j = e % KQ;
-        A[e] = (i < k && j < k) ? 1.0 * gram[(o + i) * KP + o + j] * 1.0 : 0.0;
-    }
+    if (t == 0) qp_header_reset(hdr + r);
+    qp_fill_hessian(Ad + (size_t)r * KQ * KQ, KQ, gram + (size_t)o * KP + o, nullptr, k, KP);
 }
 
 int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_params *p)
@@ -2267,21 +2268,8 @@ __global__ __launch_bounds__(256) void k_qp_setup_slots_aa(QpHeader *__restrict_
                                                            const double *__restrict__ alpha, int k, int KP)
 {
     const int t = threadIdx.x, r = blockIdx.x, o = r * k;
-    if (t == 0) {
-        QpHeader *h = hdr + r;
-        h->total_passes = 0ull;
-        h->max_passes = 0ull;
-        h->next_row = 0u;
-        h->n_overflow = 0u;
-        h->next_overflow = 0u;
-        h->pad = 0u;
-        h->waves_done = 0u;
-    }
-    double *A2 = A2d + (size_t)r * 32 * 32;
-    for (int e = t; e < 32 * 32; e += 256) {
-        const int i = e / 32, j = e % 32;
-        A2[e] = (i < k && j < k) ? alpha[o + i] * gram[(o + i) * KP + o + j] * alpha[o + j] : 0.0;
-    }
+    if (t == 0) qp_header_reset(hdr + r);
+    qp_fill_hessian(A2d + (size_t)r * 32 * 32, 32, gram + (size_t)o * KP + o, alpha + o, k, KP);
     if (t < 64) bsd[r * 64 + t] = t < k ? alpha[o + t] : 1.0;
 }
 

@@ -737,6 +737,42 @@ __global__ void k_proj_fallback_init(ProjState *__restrict__ ps, int k)
 }
 
 // ---------------------------------------------------------------- finalize
+__device__ __forceinline__ double wave_sum(double v)
+{
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
+    return v;
+}
+
+// The scalar part of POST_FIN on one wave, shared by post_step (a single fit: idx = lane) and
+// post_step_slots (slot r: idx = r kslot + lane): the column results red[a KP + idx] of the lanes
+// with `col` set -> xor tree -> the scalars that `mode` names, written to sc by lane 0.
+__device__ __forceinline__ void fin_wave_scalars(int mode, const double *__restrict__ red, int KP, int idx, bool col,
+                                                 double *__restrict__ sc)
+{
+    double s0 = col ? red[idx] : 0.0, s1 = col ? red[KP + idx] : 0.0;
+    double s2 = col ? red[2 * KP + idx] : 0.0, m3 = col ? red[3 * KP + idx] : 0.0;
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        s0 += __shfl_xor(s0, o, 64);
+        s1 += __shfl_xor(s1, o, 64);
+        s2 += __shfl_xor(s2, o, 64);
+        m3 = fmax(m3, __shfl_xor(m3, o, 64));
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (mode == PROJ_DIR) {
+            sc[SC_DELTA] = s0;
+            sc[SC_DD] = s1;
+            sc[SC_S1D] = s2;
+        } else if (mode == PROJ_RES) {
+            sc[SC_RES2] = s0;
+            sc[SC_RESINF] = m3;
+        } else if (mode == PROJ_ALPHA) {
+            sc[SC_AINV] = m3;
+        }
+    }
+}
+
 // partial [nb][NV][KP] -> red [NV][KP] (fixed order), then (single rank) the post step
 // in the same launch.  One block of 256 threads.
 __device__ void post_step(int kind, int mode, const double *__restrict__ red, int KP, int k,
@@ -806,28 +842,11 @@ __device__ void post_step(int kind, int mode, const double *__restrict__ red, in
         if (i < k && mode > 0 && mode < 4) ps->warm[mode][i] = ps->t[i];
         if (i < 64) {                       // wave 0: the k column results -> scalars (xor tree)
             const bool col = i < k;
-            double s0 = col ? red[i] : 0.0, s1 = col ? red[KP + i] : 0.0;
-            double s2 = col ? red[2 * KP + i] : 0.0, m3 = col ? red[3 * KP + i] : 0.0;
             const bool conv_all = __ballot(col && !ps->shrunk[i]) == 0ull;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s0 += __shfl_xor(s0, o, 64);
-                s1 += __shfl_xor(s1, o, 64);
-                s2 += __shfl_xor(s2, o, 64);
-                m3 = fmax(m3, __shfl_xor(m3, o, 64));
-            }
+            fin_wave_scalars(mode, red, KP, i, col, scal);
             if (i == 0) {
+                // its own: iterative passes leave their verdict in ps->done, list mode derives it here
                 if (ps->passes < 0) ps->done = conv_all ? 1 : 0;
-                if (mode == PROJ_DIR) {
-                    scal[SC_DELTA] = s0;
-                    scal[SC_DD] = s1;
-                    scal[SC_S1D] = s2;
-                } else if (mode == PROJ_RES) {
-                    scal[SC_RES2] = s0;
-                    scal[SC_RESINF] = m3;
-                } else if (mode == PROJ_ALPHA) {
-                    scal[SC_AINV] = m3;
-                }
                 const bool done = ps->passes < 0 ? conv_all : (ps->done != 0);
                 if (!done)
                     scal[SC_FLAGS] = (double)((int)scal[SC_FLAGS] | AA_SPG_FLAG_PROJ_UNCONV);
@@ -835,9 +854,7 @@ __device__ void post_step(int kind, int mode, const double *__restrict__ red, in
         }
     } else if (kind == POST_SCALAR_SUM) {
         if (i < 64) {
-            double s = i < k ? red[i] : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const double s = wave_sum(i < k ? red[i] : 0.0);
             if (i == 0) scal[slot] = s;
         }
     }
@@ -858,33 +875,12 @@ __device__ void post_step_slots(int kind, int mode, const double *__restrict__ r
         const bool col = lane < kslot;
         const int idx = r * kslot + lane;
         if (kind == POST_FIN) {
-            double s0 = col ? red[idx] : 0.0, s1 = col ? red[KP + idx] : 0.0;
-            double s2 = col ? red[2 * KP + idx] : 0.0, m3 = col ? red[3 * KP + idx] : 0.0;
             const bool conv_all = __ballot(col && !ps->shrunk[col ? idx : 0]) == 0ull;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) {
-                s0 += __shfl_xor(s0, o, 64);
-                s1 += __shfl_xor(s1, o, 64);
-                s2 += __shfl_xor(s2, o, 64);
-                m3 = fmax(m3, __shfl_xor(m3, o, 64));
-            }
-            if (lane == 0) {
-                if (mode == PROJ_DIR) {
-                    sc[SC_DELTA] = s0;
-                    sc[SC_DD] = s1;
-                    sc[SC_S1D] = s2;
-                } else if (mode == PROJ_RES) {
-                    sc[SC_RES2] = s0;
-                    sc[SC_RESINF] = m3;
-                } else if (mode == PROJ_ALPHA) {
-                    sc[SC_AINV] = m3;
-                }
-                if (!conv_all) sc[SC_FLAGS] = (double)((int)sc[SC_FLAGS] | AA_SPG_FLAG_PROJ_UNCONV);
-            }
+            fin_wave_scalars(mode, red, KP, idx, col, sc);
+            // its own: the slot's verdict is conv_all alone (ps->done is shared by all slots, set below)
+            if (lane == 0 && !conv_all) sc[SC_FLAGS] = (double)((int)sc[SC_FLAGS] | AA_SPG_FLAG_PROJ_UNCONV);
         } else if (kind == POST_SCALAR_SUM) {
-            double s = col ? red[idx] : 0.0;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o, 64);
+            const double s = wave_sum(col ? red[idx] : 0.0);
             if (lane == 0) sc[slot] = s;
         }
         if (stage_after >= 0 && lane == 0) scalar_stage_simple(stage_after, sc, sp);
@@ -1020,6 +1016,35 @@ struct DictSetup {
     double *Mout, *gram, *sc;
     aa_spg_params sp;
 };
+// tr(C H D) = sum_i alpha_i (C K Z)_ii of one k x k block (row stride KP) -> sm[0]; 256 threads, fixed tree
+__device__ __forceinline__ void dict_setup_s1(const double *__restrict__ alpha, const double *__restrict__ CKZ,
+                                              int k, int KP, double *sm /* 256 */)
+{
+    const int t = threadIdx.x;
+    sm[t] = t < k ? alpha[t] * CKZ[t * KP + t] : 0.0;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) sm[t] += sm[t + o];
+        __syncthreads();
+    }
+}
+
+// the scalar block at the start of an SPG run (spg.py:153-157), one thread
+__device__ __forceinline__ void dict_setup_scalars(double *__restrict__ sc, double trace, double fnorm, double s1,
+                                                   double a0, const aa_spg_params &sp)
+{
+    sc[SC_TRACE] = trace;
+    sc[SC_FNORM] = fnorm;
+    sc[SC_S1] = s1;
+    sc[SC_A0] = a0;
+    sc[SC_F_OLD] = 0.5 * (trace - 2.0 * s1 + a0) / fnorm;
+    sc[SC_NFEVAL] = 1.0;
+    sc[SC_FLAGS] = 0.0;
+    for (int i = 0; i < 16; ++i) sc[SC_FMEM0 + i] = 0.0;   // f_mem = zeros (spg.py:153)
+    sc[SC_ALPHA_SET] = (sp.alpha0 >= 0.0) ? 1.0 : 0.0;
+    sc[SC_ALPHA] = sp.alpha0;
+}
+
 __device__ __forceinline__ void dict_setup_body(const double *__restrict__ state, const double *__restrict__ alpha,
                                                 int k, int KP, double trace, double fnorm, double *__restrict__ Mout,
                                                 double *__restrict__ gram, double *__restrict__ sc,
@@ -1034,24 +1059,8 @@ __device__ __forceinline__ void dict_setup_body(const double *__restrict__ state
     }
     __syncthreads();
     const double a0 = block_trace_MG(Mout, gram, k, KP, false, sm);
-    sm[t] = t < k ? alpha[t] * CKZ[t * KP + t] : 0.0;
-    __syncthreads();
-    for (int o = 128; o > 0; o >>= 1) {
-        if (t < o) sm[t] += sm[t + o];
-        __syncthreads();
-    }
-    if (t == 0) {
-        sc[SC_TRACE] = trace;
-        sc[SC_FNORM] = fnorm;
-        sc[SC_S1] = sm[0];
-        sc[SC_A0] = a0;
-        sc[SC_F_OLD] = 0.5 * (trace - 2.0 * sm[0] + a0) / fnorm;
-        sc[SC_NFEVAL] = 1.0;
-        sc[SC_FLAGS] = 0.0;
-        for (int i = 0; i < 16; ++i) sc[SC_FMEM0 + i] = 0.0;   // f_mem = zeros (spg.py:153)
-        sc[SC_ALPHA_SET] = (sp.alpha0 >= 0.0) ? 1.0 : 0.0;
-        sc[SC_ALPHA] = sp.alpha0;
-    }
+    dict_setup_s1(alpha, CKZ, k, KP, sm);
+    if (t == 0) dict_setup_scalars(sc, trace, fnorm, sm[0], a0, sp);
 }
 
 // ---------------------------------------------------------------- gradient
@@ -1754,6 +1763,103 @@ __device__ __forceinline__ void sum_pq_partials(const double *__restrict__ parti
     }
 }
 
+// ---------------------------------------------------------------- R restarts side by side
+// (SURVEY 8(f1)).  The drivers fit the same matrix n_init times (bin/run_jra55_pca_gpnh.py:112-138);
+// one GPNH iteration on the C3 shape is 11 dependent launches of a few microseconds, which several
+// streams do not overlap (DESIGN.md section 5).  The tall and wide arrays have KP = 32 component
+// slots of which a k = 10 fit uses ten, so R = floor(KP / k) restarts sit SIDE BY SIDE in one set
+// of arrays: Z (n x KP) holds restart r in columns [r k, (r + 1) k), W' (KP x p) in the same rows.
+// The passes over X (X W, Z'X), Z'Z and W'W are the kernels of the single fit, unchanged -- an
+// output element of theirs depends on its own column / row only, so every restart gets the bits
+// it gets alone.  The steps that couple components read the diagonal blocks only, restart by
+// restart, and every `_slots` kernel and its single-fit twin are thin wrappers around ONE device
+// function that takes the base pointers of a k x k block (or of k rows) and the row stride: the
+// single fit passes offset 0, slot r passes o = r k, so "the same arithmetic" holds by
+// construction -- gpnh_solve_body, gpnh_cost_body, linesearch_traces / aa_cost_from_scalars /
+// accepted_gram, dict_setup_s1 / dict_setup_scalars, aa_cost_body, fin_wave_scalars (and
+// qp_header_reset / qp_fill_hessian in kernels_qp.hip).  What differs stays in the wrappers: where
+// a result is reported, and the zero padding that only the single fit writes.  Every slot has its
+// own cost record, slot counter and status record (slot_record), and takes its iteration index
+// from its slot counter: slots start and stop independently (a stopped slot keeps iterating until
+// the host replaces it; its factors were saved at the stopping iteration).
+struct GpnhSlots {
+    int R, k;
+    double *costs;        // [R][stride]
+    int stride;
+    int *counters;        // [R]
+    IterState *st;        // [R]
+    double *cost0;        // [R]
+    int max_outer;
+};
+
+__device__ __forceinline__ void iter_judge_thread0(int it, double cost0, const double *__restrict__ costs,
+                                                   IterState *__restrict__ st, double tol, double mono_tol,
+                                                   int criterion, int require, int upd_dict, int upd_w,
+                                                   const double *__restrict__ scal, int track_spg);
+
+// One thread: `cost` into slot r's record at the slot's counter.  what = 1: the cost after the dictionary
+// update; what = 2: the cost after the weights update, then the slot's judge (the iteration index is the
+// record's; scal_r: the slot's scalar block when an SPG run is behind it) and the iteration cap.
+__device__ __forceinline__ void slot_record(const GpnhSlots &sl, int r, double cost, int what, double tol,
+                                            double mono_tol, int criterion, int require,
+                                            const double *__restrict__ scal_r, int track_spg)
+{
+    double *rec = sl.costs + (size_t)r * sl.stride;
+    int idx = sl.counters[r];
+    if (idx >= sl.stride) idx = sl.stride - 1;        // a finished slot waiting to be replaced
+    rec[idx] = cost;
+    sl.counters[r] = idx + 1;
+    if (what == 2) {
+        const int it = idx / 2;
+        iter_judge_thread0(it, sl.cost0[r], rec, &sl.st[r], tol, mono_tol, criterion, require, 1, 1, scal_r, track_spg);
+        // the iteration cap ends a slot like the stopping rule does (not converged)
+        if (!sl.st[r].stop && it + 1 >= sl.max_outer) {
+            sl.st[r].stop = 1;
+            sl.st[r].stop_iter = it;
+        }
+    }
+}
+
+// tr(M (PQ' + QP')) -> smt[0] and tr(M QQ') -> smt2[0] for one k x k block (row stride KP) of M, gram[1] and
+// gram[2], in one sweep and one tree (fixed order): the first 256 threads accumulate, all join the barriers
+__device__ __forceinline__ void linesearch_traces(const double *__restrict__ M, const double *G1, const double *G2,
+                                                  int k, int KP, double *smt, double *smt2 /* 256 each */)
+{
+    const int t = threadIdx.x;
+    double a1 = 0.0, a2 = 0.0;
+    if (t < 256)
+        for (int e = t; e < k * k; e += 256) {
+            const int i = e / k, j = e % k;
+            const double m = M[i * KP + j];
+            a1 += m * (G1[j * KP + i] + G1[i * KP + j]);
+            a2 += m * G2[j * KP + i];
+        }
+    if (t < 256) {
+        smt[t] = a1;
+        smt2[t] = a2;
+    }
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if (t < o) {
+            smt[t] += smt[t + o];
+            smt2[t] += smt2[t + o];
+        }
+        __syncthreads();
+    }
+}
+
+// cost of the point the scalar block describes (archetypal_analysis.py:553-556)
+__device__ __forceinline__ double aa_cost_from_scalars(const double *__restrict__ sc, double n_global)
+{
+    return 0.5 * (sc[SC_TRACE] - 2.0 * sc[SC_S1] + sc[SC_A0]) / n_global;
+}
+
+// element e = (r, q) of the Gram of the accepted point x + lam d, from gram[0 .. 2] (GS = KP * KP apart)
+__device__ __forceinline__ double accepted_gram(const double *gram, int GS, int KP, int e, int r, int q, double lam)
+{
+    return gram[e] + lam * (gram[GS + e] + gram[GS + q * KP + r]) + lam * lam * gram[2 * GS + e];
+}
+
 // one block of 1024 threads: partials -> gram[1], gram[2], line search, Gram of the accepted
 // point, cost
 __global__ __launch_bounds__(1024) void k_linesearch_fin(const double *__restrict__ partial, int nb,
@@ -1769,45 +1875,20 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin(const double *__restric
     // the order of k_gram_finalize: four interleaved chains over the blocks, then ((0+1)+2)+3
     sum_pq_partials(partial, nb, GS, gram);
     __syncthreads();
-    // tr(M (PQ' + QP')) and tr(M QQ') in one sweep and one tree (fixed order)
     __shared__ double smt2[256];
-    double tr1 = 0.0, tr2 = 0.0;
-    {
-        double a1 = 0.0, a2 = 0.0;
-        if (t < 256)
-            for (int e = t; e < k * k; e += 256) {
-                const int i = e / k, j = e % k;
-                const double m = M[i * KP + j];
-                a1 += m * (gram[GS + j * KP + i] + gram[GS + i * KP + j]);
-                a2 += m * gram[2 * GS + j * KP + i];
-            }
-        if (t < 256) {
-            smt[t] = a1;
-            smt2[t] = a2;
-        }
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (t < o) {
-                smt[t] += smt[t + o];
-                smt2[t] += smt2[t + o];
-            }
-            __syncthreads();
-        }
-        tr1 = smt[0];
-        tr2 = smt2[0];
-    }
+    linesearch_traces(M, gram + GS, gram + 2 * GS, k, KP, smt, smt2);
     if (t == 0) {
-        linesearch_thread0(sc, sp, tr1, tr2);
+        linesearch_thread0(sc, sp, smt[0], smt2[0]);
         if (cost_out) {
             const int idx = cost_slot ? (*cost_slot)++ : 0;
-            cost_out[idx] = 0.5 * (sc[SC_TRACE] - 2.0 * sc[SC_S1] + sc[SC_A0]) / n_global;
+            cost_out[idx] = aa_cost_from_scalars(sc, n_global);
         }
     }
     __syncthreads();
     const double lam = sc[SC_LAMBDA];
     for (int e = t; e < GS; e += 1024) {
         const int r = e / KP, q = e % KP;
-        const double v = gram[e] + lam * (gram[GS + e] + gram[GS + q * KP + r]) + lam * lam * gram[2 * GS + e];
+        const double v = accepted_gram(gram, GS, KP, e, r, q, lam);
         gram[e] = v;
         if (ckct_state) ckct_state[e] = v;
     }
@@ -1815,17 +1896,12 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin(const double *__restric
 
 // restarts side by side: k_linesearch_fin with the traces, the line search, the cost and the Gram of
 // the accepted point once per slot, on the slot's diagonal blocks and scalar block
-struct SlotRecords {        // per-slot cost records (aa_slots_*, aa_gpnh_slots_*)
-    double *costs;          // [R][stride]
-    int stride;
-    int *counters;          // [R]
-};
 __global__ __launch_bounds__(1024) void k_linesearch_fin_slots(const double *__restrict__ partial, int nb,
                                                                int KP, double *__restrict__ gram,
                                                                const double *__restrict__ M,
                                                                double *__restrict__ scal, aa_spg_params sp,
                                                                int k, int R, double *__restrict__ ckct_state,
-                                                               double n_global, SlotRecords rec)
+                                                               double n_global, GpnhSlots sl)
 {
     __shared__ double smt[256];
     __shared__ double smt2[256];
@@ -1836,33 +1912,10 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin_slots(const double *__r
         const size_t off = (size_t)(r * k) * KP + r * k;
         const double *Mr = M + off, *G1 = gram + GS + off, *G2 = gram + 2 * GS + off;
         double *sc = scal + (size_t)r * AA_SC_STRIDE;
-        double a1 = 0.0, a2 = 0.0;
-        if (t < 256)
-            for (int e = t; e < k * k; e += 256) {
-                const int i = e / k, j = e % k;
-                const double m = Mr[i * KP + j];
-                a1 += m * (G1[j * KP + i] + G1[i * KP + j]);
-                a2 += m * G2[j * KP + i];
-            }
-        if (t < 256) {
-            smt[t] = a1;
-            smt2[t] = a2;
-        }
-        __syncthreads();
-        for (int o = 128; o > 0; o >>= 1) {
-            if (t < o) {
-                smt[t] += smt[t + o];
-                smt2[t] += smt2[t + o];
-            }
-            __syncthreads();
-        }
+        linesearch_traces(Mr, G1, G2, k, KP, smt, smt2);
         if (t == 0) {
             linesearch_thread0(sc, sp, smt[0], smt2[0]);
-            double *cr = rec.costs + (size_t)r * rec.stride;
-            int idx = rec.counters[r];
-            if (idx >= rec.stride) idx = rec.stride - 1;          // a finished slot waiting to be replaced
-            cr[idx] = 0.5 * (sc[SC_TRACE] - 2.0 * sc[SC_S1] + sc[SC_A0]) / n_global;
-            rec.counters[r] = idx + 1;
+            slot_record(sl, r, aa_cost_from_scalars(sc, n_global), 1, 0.0, 0.0, 0, 0, nullptr, 0);
         }
         __syncthreads();
     }
@@ -1871,7 +1924,7 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin_slots(const double *__r
         const int r = row / k;
         if (r >= R || q / k != r) continue;                       // diagonal blocks only
         const double lam = scal[(size_t)r * AA_SC_STRIDE + SC_LAMBDA];
-        const double v = gram[e] + lam * (gram[GS + e] + gram[GS + q * KP + row]) + lam * lam * gram[2 * GS + e];
+        const double v = accepted_gram(gram, GS, KP, e, row, q, lam);
         gram[e] = v;
         if (ckct_state) ckct_state[e] = v;
     }
@@ -1892,7 +1945,7 @@ __global__ __launch_bounds__(256) void k_dict_setup(const double *__restrict__ s
 }
 
 // restarts side by side: block r sets up slot r from the diagonal blocks of the Gram state -- the
-// arithmetic of k_dict_setup on its k x k block (the off-diagonal blocks of M stay zero since
+// trace, S1 and scalar helpers of dict_setup_body on its k x k block (the off-diagonal blocks of M stay zero since
 // aa_slots_begin: the gradient kernel then sees a block-diagonal M and the slots do not mix)
 __global__ __launch_bounds__(256) void k_dict_setup_slots(const double *__restrict__ state /*ZtZ|CKCt|CKZ*/,
                                                           const double *__restrict__ alpha, int k, int KP,
@@ -1907,6 +1960,7 @@ __global__ __launch_bounds__(256) void k_dict_setup_slots(const double *__restri
     const double *ZtZ = state + off, *CKCt = state + GS + off, *CKZ = state + 2 * GS + off;
     const double *al = alpha + o;
     double *M = Mout + off, *G = gram + off, *sc = scal + (size_t)r * AA_SC_STRIDE;
+    // its own: the slot's k x k block only, no zero padding (dict_setup_body fills all of KP x KP)
     for (int e = t; e < k * k; e += 256) {
         const int i = e / k, j = e % k;
         M[i * KP + j] = al[i] * ZtZ[i * KP + j] * al[j];
@@ -1914,24 +1968,8 @@ __global__ __launch_bounds__(256) void k_dict_setup_slots(const double *__restri
     }
     __syncthreads();
     const double a0 = block_trace_MG(M, G, k, KP, false, sm);
-    sm[t] = t < k ? al[t] * CKZ[t * KP + t] : 0.0;
-    __syncthreads();
-    for (int q = 128; q > 0; q >>= 1) {
-        if (t < q) sm[t] += sm[t + q];
-        __syncthreads();
-    }
-    if (t == 0) {
-        sc[SC_TRACE] = trace;
-        sc[SC_FNORM] = fnorm;
-        sc[SC_S1] = sm[0];
-        sc[SC_A0] = a0;
-        sc[SC_F_OLD] = 0.5 * (trace - 2.0 * sm[0] + a0) / fnorm;
-        sc[SC_NFEVAL] = 1.0;
-        sc[SC_FLAGS] = 0.0;
-        for (int i = 0; i < 16; ++i) sc[SC_FMEM0 + i] = 0.0;   // f_mem = zeros (spg.py:153)
-        sc[SC_ALPHA_SET] = (sp.alpha0 >= 0.0) ? 1.0 : 0.0;
-        sc[SC_ALPHA] = sp.alpha0;
-    }
+    dict_setup_s1(al, CKZ, k, KP, sm);
+    if (t == 0) dict_setup_scalars(sc, trace, fnorm, sm[0], a0, sp);
 }
 
 // ---------------------------------------------------------------- data-matrix reductions
@@ -1970,13 +2008,6 @@ __global__ __launch_bounds__(256) void k_diag_sum(const T *__restrict__ K, long 
         __syncthreads();
     }
     if (threadIdx.x == 0) partial[blockIdx.x] = sm[0];
-}
-
-__device__ __forceinline__ double wave_sum(double v)
-{
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
 }
 
 // d[i] = sqrt(max(0, <xi,xi> - 2 <xi,xj> + <xj,xj>)), one wave per row; the three dot
@@ -2593,19 +2624,10 @@ __global__ __launch_bounds__(256) void k_scale_gram(double *__restrict__ dst,
 
 // 0.5 (tr K - 2 tr(D C K Z) + tr(D Z'Z D C K C')) / n   (archetypal_analysis.py:553-556),
 // one block, fixed summation tree; state = [Z'Z | C K C' | C K Z]
-__device__ __forceinline__ void iter_judge_thread0(int it, double cost0, const double *__restrict__ costs,
-                                                   IterState *__restrict__ st, double tol, double mono_tol,
-                                                   int criterion, int require, int upd_dict, int upd_w,
-                                                   const double *__restrict__ scal, int track_spg);
-
-__global__ __launch_bounds__(256) void k_aa_cost(const double *__restrict__ state,
-                                                 const double *__restrict__ alpha, int k, int KP,
-                                                 double trace, double n_global,
-                                                 double *__restrict__ out,
-                                                 int *__restrict__ slot_counter,
-                                                 const double *__restrict__ scal, GpnhJudge jd)
+// the cost from one k x k block of the Gram state (at `state`, row stride KP) and its k entries of alpha
+__device__ __forceinline__ double aa_cost_body(const double *__restrict__ state, const double *__restrict__ alpha,
+                                               int k, int KP, double trace, double n_global, double *sm /* 256 */)
 {
-    __shared__ double sm[256];
     const double *ZtZ = state, *CKCt = state + KP * KP, *CKZ = state + 2 * KP * KP;
     const int t = threadIdx.x;
     double acc = 0.0;
@@ -2620,11 +2642,23 @@ __global__ __launch_bounds__(256) void k_aa_cost(const double *__restrict__ stat
         if (t < o) sm[t] += sm[t + o];
         __syncthreads();
     }
+    return 0.5 * (trace + sm[0]) / n_global;
+}
+
+__global__ __launch_bounds__(256) void k_aa_cost(const double *__restrict__ state,
+                                                 const double *__restrict__ alpha, int k, int KP,
+                                                 double trace, double n_global,
+                                                 double *__restrict__ out,
+                                                 int *__restrict__ slot_counter,
+                                                 const double *__restrict__ scal, GpnhJudge jd)
+{
+    __shared__ double sm[256];
+    const double cost = aa_cost_body(state, alpha, k, KP, trace, n_global, sm);
     // slot_counter: consecutive calls fill consecutive slots (the launch arguments stay
     // constant, so the call can sit in a captured graph)
-    if (t == 0) {
+    if (threadIdx.x == 0) {
         const int idx = slot_counter ? (*slot_counter)++ : 0;
-        out[idx] = 0.5 * (trace + sm[0]) / n_global;
+        out[idx] = cost;
         // the outer iteration's judge rides along with the iteration's last cost (aa_iterate)
         if (jd.on)
             iter_judge_thread0(jd.it, jd.cost0, out, jd.st, jd.tol, jd.mono_tol, jd.criterion, jd.require,
@@ -3033,34 +3067,32 @@ int launch_cost_carry(Ctx *c, double *costs, int *slot, double cost0)
 // right-hand side, one column per thread.  ok[0] = 1 when a pivot is not safely positive.
 // KM >= k: the substitution loops are unrolled over KM with `i < k` predicates, so the column's
 // solution vector stays in registers (indexed by a run-time k it lived in scratch: 25 us a launch)
+// gpnh_solve_body: the system of one fit from the k x k block at ZtZ (row stride KP) and the k rows at ZtX,
+// solved into the k rows at Wt / WtF (row stride ld); returns `bad` (no row is written then)
 template <int KM>
-__global__ __launch_bounds__(256) void k_gpnh_solve(const double *__restrict__ ZtZ /*[KP][KP]*/,
-                                                    const double *__restrict__ ZtX /*[KP][ld]*/,
-                                                    int ld, int p, int k, int KP, double n_samples,
-                                                    double lambda, double *__restrict__ Wt,
-                                                    float *__restrict__ WtF, int *__restrict__ ok)
+__device__ __forceinline__ bool gpnh_solve_body(const double *__restrict__ ZtZ, const double *__restrict__ ZtX,
+                                                int ld, int p, int k, int KP, double n_samples, double lambda,
+                                                double *__restrict__ Wt, float *__restrict__ WtF,
+                                                double *L /* k x k */, double *dmax_s, int *bad)
 {
-    extern __shared__ double L[];                 // k x k, row-major, lower triangle
-    __shared__ double dmax_s;
-    __shared__ int bad;
     const int t = threadIdx.x;
     const double pref = k > 1 ? 4.0 / ((double)p * k * (k - 1)) : 0.0;
     for (int e = t; e < k * k; e += 256) {
         const int i = e / k, j = e % k;
         L[e] = ZtZ[i * KP + j] / n_samples + lambda * pref * ((i == j ? (double)k : 0.0) - 1.0);
     }
-    if (t == 0) bad = 0;
+    if (t == 0) *bad = 0;
     __syncthreads();
     if (t == 0) {
         double m = 0.0;
         for (int i = 0; i < k; ++i) m = fmax(m, fabs(L[i * k + i]));
-        dmax_s = m;
+        *dmax_s = m;
     }
     __syncthreads();
     for (int j = 0; j < k; ++j) {                 // right-looking Cholesky
         if (t == 0) {
             const double d = L[j * k + j];
-            if (!(d > 1e-13 * dmax_s)) bad = 1;
+            if (!(d > 1e-13 * *dmax_s)) *bad = 1;
             L[j * k + j] = sqrt(d > 0.0 ? d : 1.0);
         }
         __syncthreads();
@@ -3073,12 +3105,9 @@ __global__ __launch_bounds__(256) void k_gpnh_solve(const double *__restrict__ Z
         }
         __syncthreads();
     }
-    if (bad) {
-        if (t == 0 && blockIdx.x == 0) ok[0] = 1;     // flag: not positive definite
-        return;
-    }
+    if (*bad) return true;
     const int c = blockIdx.x * 256 + t;
-    if (c >= ld) return;
+    if (c >= ld) return false;
     double y[KM];
 #pragma unroll
     for (int i = 0; i < KM; ++i) {                // L y = b
@@ -3103,12 +3132,31 @@ __global__ __launch_bounds__(256) void k_gpnh_solve(const double *__restrict__ Z
     }
 #pragma unroll
     for (int i = 0; i < KM; ++i) {
-        if (i < KP) {
+        if (i < k) {
             Wt[(long)i * ld + c] = y[i];
             if (WtF) WtF[(long)i * ld + c] = (float)y[i];
         }
     }
-    for (int i = KM; i < KP; ++i) {               // padding rows of the k x p factor stay zero
+    return false;
+}
+
+template <int KM>
+__global__ __launch_bounds__(256) void k_gpnh_solve(const double *__restrict__ ZtZ /*[KP][KP]*/,
+                                                    const double *__restrict__ ZtX /*[KP][ld]*/,
+                                                    int ld, int p, int k, int KP, double n_samples,
+                                                    double lambda, double *__restrict__ Wt,
+                                                    float *__restrict__ WtF, int *__restrict__ ok)
+{
+    extern __shared__ double L[];                 // k x k, row-major, lower triangle
+    __shared__ double dmax_s;
+    __shared__ int bad;
+    if (gpnh_solve_body<KM>(ZtZ, ZtX, ld, p, k, KP, n_samples, lambda, Wt, WtF, L, &dmax_s, &bad)) {
+        if (threadIdx.x == 0 && blockIdx.x == 0) ok[0] = 1;     // flag: not positive definite
+        return;
+    }
+    const int c = blockIdx.x * 256 + threadIdx.x;
+    if (c >= ld) return;
+    for (int i = k; i < KP; ++i) {                // its own: padding rows of the k x p factor stay zero
         Wt[(long)i * ld + c] = 0.0;
         if (WtF) WtF[(long)i * ld + c] = 0.f;
     }
@@ -3119,23 +3167,19 @@ __global__ __launch_bounds__(256) void k_gpnh_solve(const double *__restrict__ Z
 //   phi(W) = 2 / (k p (k - 1)) sum_{i<j} ||w_i - w_j||^2,  ||w_i - w_j||^2 = G_ii + G_jj - 2 G_ij
 // ZtX / Wt given (the device loop): tr(W'X'Z) = <Z'X, W'> is summed here from the two k x p
 // arrays -- 1670 terms on the C3 shape -- instead of <XW, Z> over n rows in two launches of their own.
-__global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ ZtZ,
-                                                   const double *WtW /* = WtW_out when that is set */,
-                                                   const double *__restrict__ scal, int slot, int k,
-                                                   int KP, int p, double trace, double n_samples,
-                                                   double lambda, double *__restrict__ out,
-                                                   int *__restrict__ slot_counter,
-                                                   const double *__restrict__ ZtX,
-                                                   const double *__restrict__ Wt, int ld,
-                                                   double *WtW_out, GpnhJudge jd)
+// gpnh_cost_body: one fit's sums from the k x k blocks at ZtZ and WtW (row stride KP) and the k rows at ZtX
+// and Wt (row stride ld): tr(Z'Z W'W) -> sm[0], the penalty's sum -> sm2[0], <Z'X, W'> -> sm3[0] (0 without
+// ZtX).  WtW_out (= WtW when set): the k x k block of W'W is formed here first.
+__device__ __forceinline__ void gpnh_cost_body(const double *__restrict__ ZtZ, const double *WtW, int k, int KP,
+                                               const double *__restrict__ ZtX, const double *__restrict__ Wt, int ld,
+                                               double *WtW_out, double *sm, double *sm2, double *sm3 /* 256 each */,
+                                               double *wl /* 4096 + 64 */)
 {
-    __shared__ double sm[256], sm2[256], sm3[256];
     const int t = threadIdx.x;
     if (WtW_out) {
         // W'W (k x k <= 256 outputs, k * ld <= 4096: the launcher checks) right here instead of two
         // launches of the wide Gram kernel: W' goes through LDS (coalesced in, row stride ld + 1
-        // out), one output per thread; zero padding as k_gram_finalize leaves it
-        __shared__ double wl[4096 + 64];
+        // out), one output per thread
         for (int e = t; e < k * ld; e += 256) wl[(e / ld) * (ld + 1) + e % ld] = Wt[e];
         __syncthreads();
         // `parts` threads per output, each over its share of the columns, combined in a fixed order
@@ -3152,12 +3196,11 @@ __global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ Zt
         }
         sm[t] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
         __syncthreads();
-        for (int e = t; e < KP * KP; e += 256) {
-            const int i = e / KP, j = e % KP;
+        for (int e = t; e < k * k; e += 256) {
+            const int i = e / k, j = e % k;
             double v = 0.0;
-            if (i < k && j < k)
-                for (int q = 0; q < parts; ++q) v += sm[q * kk + i * k + j];
-            WtW_out[e] = v;
+            for (int q = 0; q < parts; ++q) v += sm[q * kk + i * k + j];
+            WtW_out[i * KP + j] = v;
         }
         __syncthreads();
     }
@@ -3191,12 +3234,38 @@ __global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ Zt
         }
         __syncthreads();
     }
+}
+
+// the cost from gpnh_cost_body's sums (s1 = tr(W'X'Z), quad = tr(Z'Z W'W), pen = the penalty's sum)
+__device__ __forceinline__ double gpnh_cost_value(double trace, double s1, double quad, double pen, int k, int p,
+                                                  double n_samples, double lambda)
+{
+    double penalty = 0.0;
+    if (lambda != 0.0 && k > 1) penalty = lambda * (2.0 / ((double)k * p * (k - 1.0))) * pen;
+    return 0.5 * (trace - 2.0 * s1 + quad) / n_samples + penalty;
+}
+
+__global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ ZtZ,
+                                                   const double *WtW /* = WtW_out when that is set */,
+                                                   const double *__restrict__ scal, int slot, int k,
+                                                   int KP, int p, double trace, double n_samples,
+                                                   double lambda, double *__restrict__ out,
+                                                   int *__restrict__ slot_counter,
+                                                   const double *__restrict__ ZtX,
+                                                   const double *__restrict__ Wt, int ld,
+                                                   double *WtW_out, GpnhJudge jd)
+{
+    __shared__ double sm[256], sm2[256], sm3[256];
+    __shared__ double wl[4096 + 64];
+    const int t = threadIdx.x;
+    if (WtW_out)                                   // its own: zero padding as k_gram_finalize leaves it
+        for (int e = t; e < KP * KP; e += 256)
+            if (e / KP >= k || e % KP >= k) WtW_out[e] = 0.0;
+    gpnh_cost_body(ZtZ, WtW, k, KP, ZtX, Wt, ld, WtW_out, sm, sm2, sm3, wl);
     if (t == 0) {
-        double penalty = 0.0;
-        if (lambda != 0.0 && k > 1) penalty = lambda * (2.0 / ((double)k * p * (k - 1.0))) * sm2[0];
         const int idx = slot_counter ? (*slot_counter)++ : 0;
-        const double s1 = ZtX ? sm3[0] : scal[slot];
-        out[idx] = 0.5 * (trace - 2.0 * s1 + sm[0]) / n_samples + penalty;
+        const double s1 = ZtX ? sm3[0] : scal[slot];    // its own: without ZtX, tr(W'X'Z) was left in scal[slot]
+        out[idx] = gpnh_cost_value(trace, s1, sm[0], sm2[0], k, p, n_samples, lambda);
         // the outer iteration's judge (monotonicity, stopping rule) rides along with its last cost
         if (jd.on)
             iter_judge_thread0(jd.it, jd.cost0, out, jd.st, jd.tol, jd.mono_tol, jd.criterion, jd.require,
@@ -3215,29 +3284,8 @@ __global__ __launch_bounds__(256) void k_copy2(const IterState *__restrict__ st,
 }
 
 // ---------------------------------------------------------------- GPNH, R restarts side by side
-// (SURVEY 8(f1)).  The drivers fit the same matrix n_init times (bin/run_jra55_pca_gpnh.py:112-138);
-// one GPNH iteration on the C3 shape is 11 dependent launches of a few microseconds, which several
-// streams do not overlap (DESIGN.md section 5).  The tall and wide arrays have KP = 32 component
-// slots of which a k = 10 fit uses ten, so R = floor(KP / k) restarts sit SIDE BY SIDE in one set
-// of arrays: Z (n x KP) holds restart r in columns [r k, (r + 1) k), W' (KP x p) in the same rows.
-// The passes over X (X W, Z'X), Z'Z and W'W are the kernels of the single fit, unchanged -- an
-// output element of theirs depends on its own column / row only, so every restart gets the bits
-// it gets alone -- and the steps that couple components (the k x k solve, the cost, the QP, the
-// judge, the snapshot) read the diagonal blocks only, restart by restart, with the arithmetic of
-// the single-fit kernels.  Every slot has its own cost record, slot counter and status record, and
-// takes its iteration index from its slot counter: slots start and stop independently (a stopped
-// slot keeps iterating until the host replaces it; its factors were saved at the stopping
-// iteration).
-struct GpnhSlots {
-    int R, k;
-    double *costs;        // [R][stride]
-    int stride;
-    int *counters;        // [R]
-    IterState *st;        // [R]
-    double *cost0;        // [R]
-    int max_outer;
-};
-
+// (the layout, GpnhSlots and slot_record: above k_linesearch_fin)
+// gpnh_solve_body on the slot's block of Z'Z and its rows of Z'X and W'; `bad` goes to the slot's status record
 template <int KM>
 __global__ __launch_bounds__(256) void k_gpnh_solve_slots(const double *__restrict__ ZtZ /*[KP][KP]*/,
                                                           const double *__restrict__ ZtX /*[KP][ld]*/,
@@ -3248,79 +3296,16 @@ __global__ __launch_bounds__(256) void k_gpnh_solve_slots(const double *__restri
     extern __shared__ double L[];                 // k x k, row-major, lower triangle
     __shared__ double dmax_s;
     __shared__ int bad;
-    const int t = threadIdx.x, k = sl.k;
-    const double pref = k > 1 ? 4.0 / ((double)p * k * (k - 1)) : 0.0;
-    const int c = blockIdx.x * 256 + t;
-    {
-        const int r = blockIdx.y;                     // one slot per block row
-        const int o = r * k;
-        for (int e = t; e < k * k; e += 256) {
-            const int i = e / k, j = e % k;
-            L[e] = ZtZ[(o + i) * KP + o + j] / n_samples + lambda * pref * ((i == j ? (double)k : 0.0) - 1.0);
-        }
-        if (t == 0) bad = 0;
-        __syncthreads();
-        if (t == 0) {
-            double m = 0.0;
-            for (int i = 0; i < k; ++i) m = fmax(m, fabs(L[i * k + i]));
-            dmax_s = m;
-        }
-        __syncthreads();
-        for (int j = 0; j < k; ++j) {                 // right-looking Cholesky
-            if (t == 0) {
-                const double d = L[j * k + j];
-                if (!(d > 1e-13 * dmax_s)) bad = 1;
-                L[j * k + j] = sqrt(d > 0.0 ? d : 1.0);
-            }
-            __syncthreads();
-            const double piv = L[j * k + j];
-            for (int i = j + 1 + t; i < k; i += 256) L[i * k + j] /= piv;
-            __syncthreads();
-            for (int e = t; e < (k - j - 1) * (k - j - 1); e += 256) {
-                const int i = j + 1 + e / (k - j - 1), q = j + 1 + e % (k - j - 1);
-                if (q <= i) L[i * k + q] -= L[i * k + j] * L[q * k + j];
-            }
-            __syncthreads();
-        }
-        if (bad) {                                    // this slot only: its dictionary stays as it is
-            if (t == 0 && blockIdx.x == 0) sl.st[r].pad0 = 1;
-            return;
-        }
-        if (c >= ld) return;
-        double y[KM];
-#pragma unroll
-        for (int i = 0; i < KM; ++i) {                // L y = b
-            if (i < k) {
-                double v = c < p ? ZtX[(long)(o + i) * ld + c] / n_samples : 0.0;
-#pragma unroll
-                for (int q = 0; q < i; ++q) v -= L[i * k + q] * y[q];
-                y[i] = v / L[i * k + i];
-            } else {
-                y[i] = 0.0;
-            }
-        }
-#pragma unroll
-        for (int i = KM - 1; i >= 0; --i) {           // L' w = y
-            if (i < k) {
-                double v = y[i];
-#pragma unroll
-                for (int q = i + 1; q < KM; ++q)
-                    if (q < k) v -= L[q * k + i] * y[q];
-                y[i] = v / L[i * k + i];
-            }
-        }
-#pragma unroll
-        for (int i = 0; i < KM; ++i) {
-            if (i < k) {
-                Wt[(long)(o + i) * ld + c] = y[i];
-                if (WtF) WtF[(long)(o + i) * ld + c] = (float)y[i];
-            }
-        }
+    const int k = sl.k, r = blockIdx.y, o = r * k;    // one slot per block row
+    if (gpnh_solve_body<KM>(ZtZ + (size_t)o * KP + o, ZtX + (long)o * ld, ld, p, k, KP, n_samples, lambda,
+                            Wt + (long)o * ld, WtF ? WtF + (long)o * ld : nullptr, L, &dmax_s, &bad)) {
+        // its own: this slot only, its dictionary stays as it is
+        if (threadIdx.x == 0 && blockIdx.x == 0) sl.st[r].pad0 = 1;
     }
-    // (component slots beyond R k are zero since aa_gpnh_slots_begin and are never written)
+    // (no padding rows: component slots beyond R k are zero since aa_gpnh_slots_begin and are never written)
 }
 
-// cost of every slot in `mask` (k_gpnh_cost's arithmetic on the slot's diagonal blocks and rows):
+// cost of every slot in `mask` (gpnh_cost_body on the slot's diagonal blocks and rows):
 //   what = 0: initial cost of a freshly loaded slot -> cost0[r]
 //   what = 1: cost after the dictionary update -> the slot's record
 //   what = 2: cost after the weights update -> the record, then the slot's judge
@@ -3336,92 +3321,15 @@ __global__ __launch_bounds__(256) void k_gpnh_cost_slots(const double *__restric
 {
     __shared__ double sm[256], sm2[256], sm3[256];
     __shared__ double wl[4096 + 64];
-    const int t = threadIdx.x, k = sl.k;
-    {
-        const int r = blockIdx.x;                     // one slot per block
-        if (!((mask >> r) & 1u)) return;
-        const int o = r * k;
-        const double *Wr = Wt + (long)o * ld, *Xr = ZtX + (long)o * ld;
-        if (form_gram) {
-            // W'W of this slot (k x k), k_gpnh_cost's in-kernel Gram: W' through LDS, `parts` threads
-            // per output, combined in a fixed order
-            for (int e = t; e < k * ld; e += 256) wl[(e / ld) * (ld + 1) + e % ld] = Wr[e];
-            __syncthreads();
-            const int kk = k * k, parts = 256 / kk >= 4 ? 4 : (256 / kk >= 2 ? 2 : 1);
-            const int span = ld / parts;
-            double a4[4] = {0.0, 0.0, 0.0, 0.0};
-            if (t < kk * parts) {
-                const int e = t % kk, part = t / kk;
-                const double *wi = wl + (e / k) * (ld + 1) + part * span, *wj = wl + (e % k) * (ld + 1) + part * span;
-                for (int cc = 0; cc < span; cc += 4) {
-#pragma unroll
-                    for (int u = 0; u < 4; ++u) a4[u] = fma(wi[cc + u], wj[cc + u], a4[u]);
-                }
-            }
-            sm[t] = (a4[0] + a4[1]) + (a4[2] + a4[3]);
-            __syncthreads();
-            for (int e = t; e < k * k; e += 256) {
-                const int i = e / k, j = e % k;
-                double v = 0.0;
-                for (int q = 0; q < parts; ++q) v += sm[q * kk + i * k + j];
-                WtW[(o + i) * KP + o + j] = v;
-            }
-            __syncthreads();
-        }
-        double cross;
-        {
-            double c4[4] = {0.0, 0.0, 0.0, 0.0};            // four chains, fixed order
-            const long total = (long)k * ld;                // padding columns are zero in both
-            long e = t;
-            for (; e + 3 * 256 < total; e += 4 * 256) {
-#pragma unroll
-                for (int u = 0; u < 4; ++u) c4[u] = fma(Xr[e + u * 256], Wr[e + u * 256], c4[u]);
-            }
-            for (; e < total; e += 256) c4[0] = fma(Xr[e], Wr[e], c4[0]);
-            cross = (c4[0] + c4[1]) + (c4[2] + c4[3]);
-        }
-        sm3[t] = cross;
-        double quad = 0.0, pen = 0.0;
-        for (int e = t; e < k * k; e += 256) {
-            const int i = e / k, j = e % k;
-            quad += ZtZ[(o + i) * KP + o + j] * WtW[(o + j) * KP + o + i];
-            if (j > i) pen += WtW[(o + i) * KP + o + i] + WtW[(o + j) * KP + o + j] - 2.0 * WtW[(o + i) * KP + o + j];
-        }
-        sm[t] = quad;
-        sm2[t] = pen;
-        __syncthreads();
-        for (int q = 128; q > 0; q >>= 1) {
-            if (t < q) {
-                sm[t] += sm[t + q];
-                sm2[t] += sm2[t + q];
-                sm3[t] += sm3[t + q];
-            }
-            __syncthreads();
-        }
-        if (t == 0) {
-            double penalty = 0.0;
-            if (lambda != 0.0 && k > 1) penalty = lambda * (2.0 / ((double)k * p * (k - 1.0))) * sm2[0];
-            const double cost = 0.5 * (trace - 2.0 * sm3[0] + sm[0]) / n_samples + penalty;
-            if (what == 0) {
-                sl.cost0[r] = cost;
-            } else {
-                double *rec = sl.costs + (size_t)r * sl.stride;
-                int idx = sl.counters[r];
-                if (idx >= sl.stride) idx = sl.stride - 1;        // a finished slot waiting to be replaced
-                rec[idx] = cost;
-                sl.counters[r] = idx + 1;
-                if (what == 2) {
-                    const int it = idx / 2;
-                    iter_judge_thread0(it, sl.cost0[r], rec, &sl.st[r], tol, mono_tol, criterion, require, 1, 1,
-                                       nullptr, 0);
-                    // the iteration cap ends a slot like the stopping rule does (not converged)
-                    if (!sl.st[r].stop && it + 1 >= sl.max_outer) {
-                        sl.st[r].stop = 1;
-                        sl.st[r].stop_iter = it;
-                    }
-                }
-            }
-        }
+    const int k = sl.k, r = blockIdx.x, o = r * k;    // one slot per block
+    if (!((mask >> r) & 1u)) return;
+    double *Gr = WtW + (size_t)o * KP + o;
+    gpnh_cost_body(ZtZ + (size_t)o * KP + o, Gr, k, KP, ZtX + (long)o * ld, Wt + (long)o * ld, ld,
+                   form_gram ? Gr : nullptr, sm, sm2, sm3, wl);
+    if (threadIdx.x == 0) {
+        const double cost = gpnh_cost_value(trace, sm3[0], sm[0], sm2[0], k, p, n_samples, lambda);
+        if (what == 0) sl.cost0[r] = cost;            // its own: the initial cost is no entry of the record
+        else slot_record(sl, r, cost, what, tol, mono_tol, criterion, require, nullptr, 0);
     }
 }
 
@@ -3498,7 +3406,7 @@ int launch_gpnh_judge(Ctx *c, int it, double cost0, const double *costs, IterSta
 }
 
 // AA restarts side by side: cost of slot blockIdx.x from the diagonal blocks of the Gram state
-// (k_aa_cost's arithmetic); what = 0: initial cost -> cost0[r]; what = 2: the cost after the weights
+// (aa_cost_body); what = 0: initial cost -> cost0[r]; what = 2: the cost after the weights
 // update -> the slot's record, then its judge (the iteration index is the record's)
 __global__ __launch_bounds__(256) void k_aa_cost_slots(const double *__restrict__ state,
                                                        const double *__restrict__ alpha, int KP, double trace,
@@ -3507,40 +3415,11 @@ __global__ __launch_bounds__(256) void k_aa_cost_slots(const double *__restrict_
                                                        int criterion, int require)
 {
     __shared__ double sm[256];
-    const int t = threadIdx.x, r = blockIdx.x, k = sl.k, o = r * k;
-    const size_t off = (size_t)o * KP + o;
-    const double *ZtZ = state + off, *CKCt = state + KP * KP + off, *CKZ = state + 2 * KP * KP + off;
-    const double *al = alpha + o;
-    double acc = 0.0;
-    for (int e = t; e < k * k; e += 256) {
-        const int i = e / k, j = e % k;
-        acc += al[i] * ZtZ[i * KP + j] * al[j] * CKCt[j * KP + i];
-    }
-    if (t < k) acc -= 2.0 * (al[t] * CKZ[t * KP + t]);
-    sm[t] = acc;
-    __syncthreads();
-    for (int q = 128; q > 0; q >>= 1) {
-        if (t < q) sm[t] += sm[t + q];
-        __syncthreads();
-    }
-    if (t == 0) {
-        const double cost = 0.5 * (trace + sm[0]) / n_global;
-        if (what == 0) {
-            sl.cost0[r] = cost;
-        } else {
-            double *rec = sl.costs + (size_t)r * sl.stride;
-            int idx = sl.counters[r];
-            if (idx >= sl.stride) idx = sl.stride - 1;
-            rec[idx] = cost;
-            sl.counters[r] = idx + 1;
-            const int it = idx / 2;
-            iter_judge_thread0(it, sl.cost0[r], rec, &sl.st[r], tol, mono_tol, criterion, require, 1, 1,
-                               scal + (size_t)r * AA_SC_STRIDE, 1);
-            if (!sl.st[r].stop && it + 1 >= sl.max_outer) {
-                sl.st[r].stop = 1;
-                sl.st[r].stop_iter = it;
-            }
-        }
+    const int r = blockIdx.x, k = sl.k, o = r * k;
+    const double cost = aa_cost_body(state + (size_t)o * KP + o, alpha + o, k, KP, trace, n_global, sm);
+    if (threadIdx.x == 0) {
+        if (what == 0) sl.cost0[r] = cost;            // its own: the initial cost is no entry of the record
+        else slot_record(sl, r, cost, what, tol, mono_tol, criterion, require, scal + (size_t)r * AA_SC_STRIDE, 1);
     }
 }
 
@@ -3719,13 +3598,9 @@ int launch_linesearch_fused(Ctx *c, const aa_spg_params *sp, double *cost_out, i
                            (const double *)c->P.as<double>(), (const double *)c->Q.as<double>(),
                            (int)c->p_pad, part, cpb, c->k);
     if (c->slots_aa) {
-        SlotRecords rec;
-        rec.costs = c->slotCosts.as<double>();
-        rec.stride = c->slots_stride;
-        rec.counters = c->slotCounters.as<int>();
         hipLaunchKernelGGL(k_linesearch_fin_slots, dim3(1), dim3(1024), 0, c->stream, (const double *)part, nb, c->KP,
                            c->gramOut.as<double>(), (const double *)c->Mdev.as<double>(), c->scalars.as<double>(),
-                           *sp, c->slots_k, c->slots_R, ckct, (double)c->n_global, rec);
+                           *sp, c->slots_k, c->slots_R, ckct, (double)c->n_global, slots_of(c));
     } else
     hipLaunchKernelGGL(k_linesearch_fin, dim3(1), dim3(1024), 0, c->stream, (const double *)part, nb, c->KP,
                        c->gramOut.as<double>(), (const double *)c->Mdev.as<double>(),
