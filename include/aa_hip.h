@@ -413,7 +413,8 @@ int aa_furthest_sum(aa_ctx *ctx, int k, long start_index, const int *exclude, in
  *                         call of either slot mode resets whatever an earlier, un-ended one left */
 typedef struct {
     int stop, converged, error_stage, stop_iter;
-    int not_spd;            /* the slot's normal equations were not positive definite */
+    int flags;              /* GPNH slots: nonzero when the slot's normal equations were not positive definite;
+                             * AA slots: the slot's SPG warning flags (AA_SPG_FLAG_* bits) */
     int iterations_run;     /* outer iterations this slot has been through since it was loaded */
 } aa_slot_status;
 int aa_gpnh_slots_begin(aa_ctx *ctx, int R, int k, const aa_gpnh_params *gp, const aa_qp_params *qp);
@@ -430,11 +431,10 @@ int aa_gpnh_slots_fetch(aa_ctx *ctx, int r, double *Wt, long ld, double *Z, doub
  * C X -- recomputed from the fetched C, or (carried != 0) as the loop carried it at the stopping
  * iteration, which is what aa_get_archetypes returns after an aa_iterate that stopped on the last
  * iteration of a batch; aa_slots_reload puts the next restart into the freed slot (its first dictionary
- * update is the cold one of a fit, the running slots keep the products they carry); aa_slots_finish
- * (optional, all slots stopped) restores the stopping-iteration factors and rebuilds the products;
+ * update is the cold one of a fit, the running slots keep the products they carry);
  * aa_slots_end returns the context to single fits (from either slot mode: it also ends a run begun with
- * aa_gpnh_slots_begin).  status[r].not_spd carries the slot's SPG warning
- * flags (AA_SPG_FLAG_*).  Every restart gets the bits aa_iterate gives it on its own. */
+ * aa_gpnh_slots_begin).  status[r].flags carries the slot's SPG warning flags (AA_SPG_FLAG_*).  Every
+ * restart gets the bits aa_iterate gives it on its own. */
 int aa_slots_begin(aa_ctx *ctx, int R, int k, const aa_iter_params *loop, const aa_spg_params *spg,
                    const aa_qp_params *qp, const aa_spg_params *scale_spg /* loop->delta != 0 */);
 int aa_slots_load(aa_ctx *ctx, int r, const double *C, long ldc, const double *Z, const double *alpha /* k, or NULL: ones */);
@@ -442,7 +442,6 @@ int aa_slots_run(aa_ctx *ctx, int n_iters, aa_slot_status *status);
 /* a new restart into slot r of a RUNNING group (its previous occupant has stopped and been fetched): the
  * other slots keep the products they carry; the slot's next dictionary update is the cold one of a fit */
 int aa_slots_reload(aa_ctx *ctx, int r, const double *C, long ldc, const double *Z, const double *alpha);
-int aa_slots_finish(aa_ctx *ctx);     /* all slots stopped: stopping-iteration factors restored, products rebuilt */
 int aa_slots_fetch(aa_ctx *ctx, int r, double *C, long ldc, double *Z, double *CX, long ldx, int carried,
                    double *costs, double *cost0, double *alpha /* k scale factors out, nullable */);
 int aa_slots_end(aa_ctx *ctx);

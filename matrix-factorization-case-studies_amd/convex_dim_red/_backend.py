@@ -79,9 +79,10 @@ class GPNHParams(ctypes.Structure):
 
 
 class SlotStatus(ctypes.Structure):
-    """aa_slot_status: one restart slot of aa_gpnh_slots_run."""
+    """aa_slot_status: one restart slot of aa_gpnh_slots_run / aa_slots_run.  ``flags``: GPNH -- nonzero when
+    the slot's normal equations were not positive definite; AA -- the slot's SPG_FLAG_* warning bits."""
     _fields_ = [("stop", ctypes.c_int), ("converged", ctypes.c_int), ("error_stage", ctypes.c_int),
-                ("stop_iter", ctypes.c_int), ("not_spd", ctypes.c_int), ("iterations_run", ctypes.c_int)]
+                ("stop_iter", ctypes.c_int), ("flags", ctypes.c_int), ("iterations_run", ctypes.c_int)]
 
 
 class QPStats(ctypes.Structure):
@@ -160,7 +161,6 @@ _SIGNATURES = {
     "aa_slots_load": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, _dp, _dp]),
     "aa_slots_run": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.POINTER(SlotStatus)]),
     "aa_slots_reload": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, _dp, _dp]),
-    "aa_slots_finish": (ctypes.c_int, [_vp]),
     "aa_slots_fetch": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, _dp, _dp, ctypes.c_long, ctypes.c_int,
                                       _dp, _dp, _dp]),
     "aa_slots_end": (ctypes.c_int, [_vp]),
@@ -309,6 +309,17 @@ def qp_params(**kw):
 _SPG_KEYS = ("gamma", "memory", "sigma_one", "sigma_two", "lambda_min", "alpha0", "alpha_min",
              "alpha_max", "epsilon_one", "epsilon_two", "use_infinity_norm", "verbose",
              "max_iterations", "max_feval")
+
+
+def _iter_params(max_outer, tolerance, stopping_criterion, require_monotonic, mono_tolerance, update_dictionary,
+                 update_weights, check_every, delta):
+    """aa_iter_params from the estimators' loop controls (``mono_tolerance`` None: the tolerance)."""
+    crit = {"abs_delta_f": 0, "rel_delta_f": 1}.get(stopping_criterion)
+    if crit is None:
+        raise ValueError("unsupported stopping criterion '%s'" % stopping_criterion)
+    return IterParams(int(max_outer), float(tolerance), crit, int(bool(require_monotonic)),
+                      float(tolerance if mono_tolerance is None else mono_tolerance),
+                      int(bool(update_dictionary)), int(bool(update_weights)), int(check_every), float(delta))
 
 
 def spg_params(**kw):
@@ -597,13 +608,8 @@ class Context(object):
                 mono_tolerance=None, delta=0.0, scale_kw=None):
         """Up to ``max_outer`` outer iterations with the monotonicity check and the stopping rule
         evaluated on the device (aa_iterate); returns (costs[2 * (n_iter + 1)], IterStats)."""
-        crit = {"abs_delta_f": 0, "rel_delta_f": 1}.get(stopping_criterion)
-        if crit is None:
-            raise ValueError("unsupported stopping criterion '%s'" % stopping_criterion)
-        ip = IterParams(int(max_outer), float(tolerance), crit, int(bool(require_monotonic)),
-                        float(tolerance if mono_tolerance is None else mono_tolerance),
-                        int(bool(update_dictionary)), int(bool(update_weights)), int(check_every),
-                        float(delta))
+        ip = _iter_params(max_outer, tolerance, stopping_criterion, require_monotonic, mono_tolerance,
+                          update_dictionary, update_weights, check_every, delta)
         sp, qp = spg_params(**spg_kw), qp_params(**qp_kw)
         ssp = spg_params(**scale_kw) if (scale_kw is not None and delta != 0) else None
         costs = np.zeros(2 * int(max_outer))
@@ -678,13 +684,9 @@ class Context(object):
         """The GPNH alternating loop on the device (aa_gpnh_iterate); returns
         (cost0, costs[2 * (n_iter + 1)], IterStats).  stats.error_stage == 3: the regularised
         normal equations were not positive definite (the caller falls back to lstsq)."""
-        crit = {"abs_delta_f": 0, "rel_delta_f": 1}.get(stopping_criterion)
-        if crit is None:
-            raise ValueError("unsupported stopping criterion '%s'" % stopping_criterion)
-        gp = GPNHParams(float(lambda_W), IterParams(
-            int(max_outer), float(tolerance), crit, int(bool(require_monotonic)),
-            float(tolerance if mono_tolerance is None else mono_tolerance),
-            int(bool(update_dictionary)), int(bool(update_weights)), int(check_every), 0.0))
+        gp = GPNHParams(float(lambda_W), _iter_params(max_outer, tolerance, stopping_criterion, require_monotonic,
+                                                      mono_tolerance, update_dictionary, update_weights,
+                                                      check_every, 0.0))
         qp = qp_params(**qp_kw)
         costs = np.zeros(2 * int(max_outer))
         st = IterStats()
@@ -696,12 +698,8 @@ class Context(object):
     # ---- GPNH restarts side by side (aa_gpnh_slots_*; restarts.fit_restarts drives them)
     def gpnh_slots_begin(self, n_slots, k, lambda_W, max_outer, tolerance, stopping_criterion, require_monotonic,
                          qp_kw, mono_tolerance=None):
-        crit = {"abs_delta_f": 0, "rel_delta_f": 1}.get(stopping_criterion)
-        if crit is None:
-            raise ValueError("unsupported stopping criterion '%s'" % stopping_criterion)
-        gp = GPNHParams(float(lambda_W), IterParams(
-            int(max_outer), float(tolerance), crit, int(bool(require_monotonic)),
-            float(tolerance if mono_tolerance is None else mono_tolerance), 1, 1, 8, 0.0))
+        gp = GPNHParams(float(lambda_W), _iter_params(max_outer, tolerance, stopping_criterion, require_monotonic,
+                                                      mono_tolerance, True, True, 8, 0.0))
         qp = qp_params(**qp_kw)
         _check(self.lib.aa_gpnh_slots_begin(self.h, int(n_slots), int(k), ctypes.byref(gp), ctypes.byref(qp)))
         self.k = int(n_slots) * int(k)
@@ -713,10 +711,13 @@ class Context(object):
         Z = _c64(Z)
         _check(self.lib.aa_gpnh_slots_load(self.h, int(r), _ptr(Wt), Wt.shape[1], _ptr(Z)))
 
-    def gpnh_slots_run(self, n_iters):
+    def _slots_run(self, fn, n_iters):
         st = (SlotStatus * self._slots[0])()
-        _check(self.lib.aa_gpnh_slots_run(self.h, int(n_iters), st))
+        _check(fn(self.h, int(n_iters), st))
         return list(st)
+
+    def gpnh_slots_run(self, n_iters):
+        return self._slots_run(self.lib.aa_gpnh_slots_run, n_iters)
 
     def gpnh_slots_fetch(self, r, stop_iter):
         """(weights n x k, dictionary p x k, cost0, costs[2 (stop_iter + 1)]) of a stopped slot."""
@@ -731,11 +732,8 @@ class Context(object):
     # ---- AA restarts side by side (aa_slots_*)
     def aa_slots_begin(self, n_slots, k, max_outer, tolerance, stopping_criterion, require_monotonic, spg_kw, qp_kw,
                        mono_tolerance=None, delta=0.0, scale_kw=None):
-        crit = {"abs_delta_f": 0, "rel_delta_f": 1}.get(stopping_criterion)
-        if crit is None:
-            raise ValueError("unsupported stopping criterion '%s'" % stopping_criterion)
-        ip = IterParams(int(max_outer), float(tolerance), crit, int(bool(require_monotonic)),
-                        float(tolerance if mono_tolerance is None else mono_tolerance), 1, 1, 8, float(delta))
+        ip = _iter_params(max_outer, tolerance, stopping_criterion, require_monotonic, mono_tolerance, True, True, 8,
+                          delta)
         sp, qp = spg_params(**spg_kw), qp_params(**qp_kw)
         scale = spg_params(**(scale_kw or {})) if delta != 0 else None
         _check(self.lib.aa_slots_begin(self.h, int(n_slots), int(k), ctypes.byref(ip), ctypes.byref(sp),
@@ -743,23 +741,21 @@ class Context(object):
         self.k = int(n_slots) * int(k)
         self._slots = (int(n_slots), int(k), int(max_outer))
 
-    def aa_slots_load(self, r, C, Z, alpha=None):
+    def _aa_slots_put(self, fn, r, C, Z, alpha):
         C, Z = _c64(C), _c64(Z)
         a = None if alpha is None else _c64(alpha)
-        _check(self.lib.aa_slots_load(self.h, int(r), _ptr(C), C.shape[1], _ptr(Z), None if a is None else _ptr(a)))
+        _check(fn(self.h, int(r), _ptr(C), C.shape[1], _ptr(Z), None if a is None else _ptr(a)))
+
+    def aa_slots_load(self, r, C, Z, alpha=None):
+        """``C``: k x n_samples, ``Z``: n_samples x k, into slot r of a group that has not run yet."""
+        self._aa_slots_put(self.lib.aa_slots_load, r, C, Z, alpha)
 
     def aa_slots_reload(self, r, C, Z, alpha=None):
-        C, Z = _c64(C), _c64(Z)
-        a = None if alpha is None else _c64(alpha)
-        _check(self.lib.aa_slots_reload(self.h, int(r), _ptr(C), C.shape[1], _ptr(Z), None if a is None else _ptr(a)))
+        """The same into a freed slot of a RUNNING group (the other slots carry on)."""
+        self._aa_slots_put(self.lib.aa_slots_reload, r, C, Z, alpha)
 
     def aa_slots_run(self, n_iters):
-        st = (SlotStatus * self._slots[0])()
-        _check(self.lib.aa_slots_run(self.h, int(n_iters), st))
-        return list(st)
-
-    def aa_slots_finish(self):
-        _check(self.lib.aa_slots_finish(self.h))
+        return self._slots_run(self.lib.aa_slots_run, n_iters)
 
     def aa_slots_fetch(self, r, stop_iter, carried):
         """(weights n x k, dictionary k x n, C X k x p, cost0, costs[2 (stop_iter + 1)], alpha[k]) of a stopped slot."""

@@ -10,11 +10,11 @@ loop; a worker thread draws while the device already iterates on the first resta
 and
 
 * GPNH models, and AA models with the drivers' settings (one SPG iteration per dictionary update,
-  any delta, fewer than 65 536 samples, k <= 16): lays the restarts SIDE BY SIDE in the component slots of
-  one set of device arrays, where they share every launch of an outer iteration; a restart that stops
-  hands its slot to the next one (``_fit_gpnh_slots`` / aa_gpnh_slots_*, ``_fit_aa_slots`` /
-  aa_slots_*): 3.4-6x the sequential loop's speed on the JRA-55- and HadISST-shaped problems with
-  ``n_init = 100``;
+  any delta, fewer than 65 536 samples, k <= 16): lays the restarts SIDE BY SIDE in the component slots
+  of one set of device arrays, where they share every launch of an outer iteration; a restart that
+  stops hands its slot to the next one (``_fit_slots`` with ``_GpnhFamily`` / aa_gpnh_slots_* or
+  ``_AAFamily`` / aa_slots_*): 3.4-6x the sequential loop's speed on the JRA-55- and HadISST-shaped
+  problems with ``n_init = 100``;
 * other AA settings: runs the fits on worker threads, each on its own device context; the contexts
   of a device share one resident copy of the data (useful with ``devices=[...]``: whole restarts
   dealt over GPUs; on ONE GPU several fits at a time are not faster).
@@ -253,94 +253,6 @@ def _next_pending(pending, models, left):
     return None
 
 
-def _fit_gpnh_slots(models, starts, data, device, poll_every=8, n_slots=None):
-    """Up to 64 // k restarts side by side in ONE set of device arrays (aa_gpnh_slots_*): every outer
-    iteration's launches serve all of them, a restart that stops is taken out and the next pending
-    one takes its slot.  Restart by restart the result is the one the sequential loop gives, bit
-    for bit (each slot runs the single fit's arithmetic on its own columns).  Returns the indices
-    of restarts whose normal equations were not positive definite (the sequential path solves those
-    with lstsq like the reference)."""
-    import time
-    import warnings
-    m0 = models[0]
-    k = m0.n_components
-    n_samples = data.shape[0]
-    n_slots = min(_gpnh_slot_count(m0, n_samples, n_slots), len(models))
-    fallback, errors = [], {}
-    ctx = _backend.Context(dtype=m0.dtype, device=device)
-    try:
-        ctx.set_data(data)
-        mono_tol = m0.tolerance
-        if ctx.dtype_code == _backend.AA_F32:
-            mono_tol = max(m0.tolerance, 8 * 6e-8 * ctx.data_trace() / n_samples)
-        ctx.gpnh_slots_begin(n_slots, k, m0.lambda_W, m0.max_iterations, m0.tolerance, m0.stopping_criterion,
-                             m0.require_monotonic_cost_decrease, m0.weights_solver_kwargs, mono_tolerance=mono_tol)
-        pending = list(range(len(models)))
-        owner = [None] * n_slots
-        loaded_at = [0.0] * n_slots
-        tables = [None] * len(models)
-
-        prof = slots_profile
-        prof.update(load=0.0, run=0.0, fetch=0.0, polls=0, slots=n_slots)
-
-        def load(r):
-            i = _next_pending(pending, models, fallback)
-            if i is None:
-                return
-            start = starts[i]                     # (waits for the draw if the feed is behind)
-            t0 = time.perf_counter()
-            start = _resolve_start(ctx, start, data, models[i])
-            ctx.gpnh_slots_load(r, start["dictionary"], start["weights"])
-            owner[r] = i
-            loaded_at[r] = time.perf_counter()
-            prof["load"] += loaded_at[r] - t0
-
-        for r in range(n_slots):
-            load(r)
-        while any(o is not None for o in owner):
-            t0 = time.perf_counter()
-            status = ctx.gpnh_slots_run(poll_every)
-            prof["run"] += time.perf_counter() - t0
-            prof["polls"] += 1
-            for r, st in enumerate(status):
-                i = owner[r]
-                if i is None:
-                    continue
-                if st.not_spd:
-                    fallback.append(i)
-                elif st.stop:
-                    m = models[i]
-                    if st.error_stage:
-                        errors[i] = RuntimeError('factorization cost increased after {} update'.format(
-                            'dictionary' if st.error_stage == 1 else 'weights'))
-                    else:
-                        t0 = time.perf_counter()
-                        Z, W, cost0, costs = ctx.gpnh_slots_fetch(r, st.stop_iter)
-                        prof["fetch"] += time.perf_counter() - t0
-                        finals = costs[1::2]
-                        begins = np.concatenate(([cost0], finals[:-1]))
-                        m.weights, m.dictionary = Z, W
-                        m.cost, m.n_iter = float(finals[-1]), int(st.stop_iter)
-                        m.cost_deltas = [float(d) for d in finals - begins]
-                        m.avg_time_per_iter = (time.perf_counter() - loaded_at[r]) / max(st.iterations_run, 1)
-                        tables[i] = (finals, begins, m.avg_time_per_iter, bool(st.converged))
-                        if m.n_iter == m.max_iterations and m.tolerance > 0:
-                            warnings.warn('Maximum number of iterations %d reached.' % m.max_iterations, UserWarning)
-                else:
-                    continue
-                owner[r] = None
-                if pending:
-                    load(r)
-        ctx.aa_slots_end()
-    finally:
-        ctx.close()
-    if m0.verbose:
-        _print_tables(models, tables, "*** GPNH convex coding: n_components = {:d} ***", 100)
-    if errors:
-        raise errors[min(errors)]
-    return fallback
-
-
 def _aa_slots_eligible(m0, n_models, data):
     """AA restarts that can share one set of device arrays (aa_slots_*): the drivers' setting -- one SPG
     iteration per dictionary update -- fewer than 65 536 samples, k <= 16 (and every restart with the
@@ -357,101 +269,192 @@ def _aa_slots_eligible(m0, n_models, data):
             and _backend.distributed_env() is None)
 
 
-def _fit_aa_slots(models, starts, data, device, poll_every=8, n_slots=None):
-    """Up to 32 // k AA restarts side by side in ONE set of device arrays (aa_slots_*): every launch of
-    an outer iteration serves all of them; a restart that stops is taken out and the next pending one
-    takes its slot (its first dictionary update is the cold one of a fit while the others carry on:
-    aa_slots_reload).  Restart by restart the result is the sequential loop's, bit for bit."""
+# what a family's retire() answers for a slot after a poll
+_KEEP, _STOPPED, _SEQUENTIAL = "keep running", "stopped", "send to the sequential path"
+
+
+class _GpnhFamily(object):
+    """What the GPNH slots (aa_gpnh_slots_*, up to 64 // k restarts at a time) do their own way in
+    ``_fit_slots``."""
+    title, rule = "*** GPNH convex coding: n_components = {:d} ***", 100
+    stages = {1: 'dictionary', 2: 'weights'}
+    slot_count = staticmethod(_gpnh_slot_count)
+
+    @staticmethod
+    def begin(ctx, n_slots, m0, mono_tol):
+        ctx.gpnh_slots_begin(n_slots, m0.n_components, m0.lambda_W, m0.max_iterations, m0.tolerance,
+                             m0.stopping_criterion, m0.require_monotonic_cost_decrease, m0.weights_solver_kwargs,
+                             mono_tolerance=mono_tol)
+
+    @staticmethod
+    def load(ctx, r, start, running):
+        ctx.gpnh_slots_load(r, start["dictionary"], start["weights"])
+
+    @staticmethod
+    def run(ctx, n_iters):
+        return ctx.gpnh_slots_run(n_iters)
+
+    @staticmethod
+    def retire(st):
+        if st.flags:                              # normal equations not positive definite: the sequential
+            return _SEQUENTIAL                    # path solves those with lstsq like the reference
+        return _STOPPED if st.stop else _KEEP
+
+    @staticmethod
+    def on_stop(st):
+        pass
+
+    @staticmethod
+    def harvest(ctx, r, st, m):
+        Z, W, cost0, costs = ctx.gpnh_slots_fetch(r, st.stop_iter)
+        finals = costs[1::2]
+        begins = np.concatenate(([cost0], finals[:-1]))
+        m.weights, m.dictionary = Z, W
+        m.cost_deltas = [float(d) for d in finals - begins]
+        return finals, begins
+
+
+class _AAFamily(object):
+    """What the AA slots (aa_slots_*, up to 32 // k restarts at a time) do their own way in ``_fit_slots``:
+    the first group starts together, a later restart joins the running group (its first dictionary update
+    is the cold one of a fit while the others carry on: aa_slots_reload)."""
+    title, rule = "*** AA: n_components = {:d} ***", 80
+    stages = {1: 'dictionary', 2: 'weights', 3: 'scale factors'}
+
+    @staticmethod
+    def slot_count(m0, n_samples, n_slots):
+        cap = 32 // m0.n_components
+        return cap if n_slots is None else min(int(n_slots), cap)
+
+    @staticmethod
+    def begin(ctx, n_slots, m0, mono_tol):
+        ctx.aa_slots_begin(n_slots, m0.n_components, m0.max_iterations, m0.tolerance, m0.stopping_criterion,
+                           m0.require_monotonic_cost_decrease, m0.dictionary_solver_kwargs,
+                           m0.weights_solver_kwargs, mono_tolerance=mono_tol, delta=m0.delta,
+                           scale_kw=m0.scale_factors_solver_kwargs)
+
+    @staticmethod
+    def load(ctx, r, start, running):
+        put = ctx.aa_slots_reload if running else ctx.aa_slots_load
+        put(r, start["dictionary"], start["weights"], start["alpha"])
+
+    @staticmethod
+    def run(ctx, n_iters):
+        return ctx.aa_slots_run(n_iters)
+
+    @staticmethod
+    def retire(st):
+        return _STOPPED if st.stop else _KEEP
+
+    @staticmethod
+    def on_stop(st):                              # st.flags: the SPG warnings of the slot's fit, errors or not
+        _aa_module._warn_from_spg_flags(st)
+
+    @staticmethod
+    def harvest(ctx, r, st, m):
+        # aa_iterate rebuilds the products only when it ran past the stopping iteration
+        carried = (st.stop_iter + 1) % _aa_module._DEVICE_LOOP_BATCH == 0 or st.stop_iter + 1 == m.max_iterations
+        Z, C, CX, cost0, costs, alpha = ctx.aa_slots_fetch(r, st.stop_iter, carried)
+        finals = costs[1::2]
+        begins = np.concatenate(([cost0], finals[:-1]))
+        if m.delta != 0:                          # ArchetypalAnalysis.fit_transform (reference :1140-1144)
+            C = np.dot(np.diag(alpha), C)
+            CX = alpha[:, np.newaxis] * CX
+        m.weights, m.dictionary, m.alpha, m.archetypes = Z, C, alpha, CX
+        m.cost_deltas = [d for d in finals - begins]
+        return finals, begins
+
+
+def _fit_slots(family, models, starts, data, device, poll_every=8, n_slots=None):
+    """Restarts side by side in ONE set of device arrays (``family``: _GpnhFamily or _AAFamily): every
+    launch of an outer iteration serves all slots; a restart that stops is taken out and the next pending
+    one takes its slot.  Restart by restart the result is the one the sequential loop gives, bit for bit
+    (each slot runs the single fit's arithmetic on its own columns).  Returns the indices of the restarts
+    left to the sequential path, in the order they were met: those with other settings than the first
+    one, and GPNH restarts whose normal equations were not positive definite."""
     import time
     import warnings
-    from .archetypal_analysis import _warn_from_spg_flags, _DEVICE_LOOP_BATCH
-
-    class _Flags(object):
-        def __init__(self, flags):
-            self.spg_flags = flags
-
     m0 = models[0]
-    k = m0.n_components
-    n_slots = min((32 // k) if n_slots is None else int(n_slots), 32 // k, len(models))
     n_samples = data.shape[0]
+    n_slots = min(family.slot_count(m0, n_samples, n_slots), len(models))
+    left, errors = [], {}
+    pending = list(range(len(models)))
+    owner = [None] * n_slots
+    loaded_at = [0.0] * n_slots
+    tables = [None] * len(models)
     prof = slots_profile
     prof.update(load=0.0, run=0.0, fetch=0.0, polls=0, slots=n_slots)
     ctx = _backend.Context(dtype=m0.dtype, device=device)
-    errors, left = {}, []
     try:
         ctx.set_data(data)
         mono_tol = m0.tolerance
         if ctx.dtype_code == _backend.AA_F32:
             mono_tol = max(m0.tolerance, 8 * 6e-8 * ctx.data_trace() / n_samples)
-        pending = list(range(len(models)))
-        owner = [None] * n_slots
-        loaded_at = [0.0] * n_slots
-        tables = [None] * len(models)
         t0 = time.perf_counter()
-        ctx.aa_slots_begin(n_slots, k, m0.max_iterations, m0.tolerance, m0.stopping_criterion,
-                           m0.require_monotonic_cost_decrease, m0.dictionary_solver_kwargs,
-                           m0.weights_solver_kwargs, mono_tolerance=mono_tol, delta=m0.delta,
-                           scale_kw=m0.scale_factors_solver_kwargs)
-        for r in range(n_slots):                  # the first group starts together
+        family.begin(ctx, n_slots, m0, mono_tol)
+        prof["load"] += time.perf_counter() - t0
+
+        def load(r, running):
             i = _next_pending(pending, models, left)
             if i is None:
-                break
-            start = _resolve_start(ctx, starts[i], data, models[i])
-            ctx.aa_slots_load(r, start["dictionary"], start["weights"], start["alpha"])
+                return
+            start = starts[i]                     # (waits for the draw if the feed is behind)
+            t0 = time.perf_counter()
+            start = _resolve_start(ctx, start, data, models[i])
+            family.load(ctx, r, start, running)
             owner[r] = i
             loaded_at[r] = time.perf_counter()
-        prof["load"] += time.perf_counter() - t0
+            prof["load"] += loaded_at[r] - t0
+
+        for r in range(n_slots):                  # the first group starts together
+            load(r, False)
         while any(o is not None for o in owner):
             t0 = time.perf_counter()
-            status = ctx.aa_slots_run(poll_every)
+            status = family.run(ctx, poll_every)
             prof["run"] += time.perf_counter() - t0
             prof["polls"] += 1
             for r, st in enumerate(status):
                 i = owner[r]
-                if i is None or not st.stop:
+                if i is None:
                     continue
-                m = models[i]
-                t0 = time.perf_counter()
-                _warn_from_spg_flags(_Flags(st.not_spd))
-                if st.error_stage:
+                verdict = family.retire(st)
+                if verdict == _KEEP:
+                    continue
+                if verdict == _STOPPED:
+                    family.on_stop(st)
+                if verdict == _SEQUENTIAL:
+                    left.append(i)
+                elif st.error_stage:
                     errors[i] = RuntimeError('factorization cost increased after {} update'.format(
-                        {1: 'dictionary', 2: 'weights', 3: 'scale factors'}[st.error_stage]))
+                        family.stages.get(st.error_stage, 'weights')))
                 else:
-                    # aa_iterate rebuilds the products only when it ran past the stopping iteration
-                    carried = (st.stop_iter + 1) % _DEVICE_LOOP_BATCH == 0 or st.stop_iter + 1 == m.max_iterations
-                    Z, C, CX, cost0, costs, alpha = ctx.aa_slots_fetch(r, st.stop_iter, carried)
-                    finals = costs[1::2]
-                    begins = np.concatenate(([cost0], finals[:-1]))
-                    if m.delta != 0:                  # ArchetypalAnalysis.fit_transform (reference :1140-1144)
-                        C = np.dot(np.diag(alpha), C)
-                        CX = alpha[:, np.newaxis] * CX
-                    m.weights, m.dictionary, m.alpha = Z, C, alpha
+                    m = models[i]
+                    t0 = time.perf_counter()
+                    finals, begins = family.harvest(ctx, r, st, m)
+                    prof["fetch"] += time.perf_counter() - t0
                     m.cost, m.n_iter = float(finals[-1]), int(st.stop_iter)
-                    m.cost_deltas = [d for d in finals - begins]
                     m.avg_time_per_iter = (time.perf_counter() - loaded_at[r]) / max(st.iterations_run, 1)
                     tables[i] = (finals, begins, m.avg_time_per_iter, bool(st.converged))
-                    m.archetypes = CX
                     if m.n_iter == m.max_iterations and m.tolerance > 0:
                         warnings.warn('Maximum number of iterations %d reached.' % m.max_iterations, UserWarning)
-                prof["fetch"] += time.perf_counter() - t0
                 owner[r] = None
-                i = _next_pending(pending, models, left)
-                if i is not None:
-                    start = starts[i]             # (waits for the draw if the feed is behind)
-                    t0 = time.perf_counter()
-                    start = _resolve_start(ctx, start, data, models[i])
-                    ctx.aa_slots_reload(r, start["dictionary"], start["weights"], start["alpha"])
-                    owner[r] = i
-                    loaded_at[r] = time.perf_counter()
-                    prof["load"] += loaded_at[r] - t0
+                load(r, True)
         ctx.aa_slots_end()
     finally:
         ctx.close()
     if m0.verbose:
-        _print_tables(models, tables, "*** AA: n_components = {:d} ***", 80)
+        _print_tables(models, tables, family.title, family.rule)
     if errors:
         raise errors[min(errors)]
     return left
+
+
+def _fit_gpnh_slots(models, starts, data, device, poll_every=8, n_slots=None):
+    return _fit_slots(_GpnhFamily, models, starts, data, device, poll_every, n_slots)
+
+
+def _fit_aa_slots(models, starts, data, device, poll_every=8, n_slots=None):
+    return _fit_slots(_AAFamily, models, starts, data, device, poll_every, n_slots)
 
 
 def fit_restarts(make_model, data, n_init, n_jobs=None, devices=None, side_by_side=True, n_slots=None):
@@ -465,9 +468,8 @@ def fit_restarts(make_model, data, n_init, n_jobs=None, devices=None, side_by_si
     ``side_by_side`` (models with the same hyper-parameters; GPNH with k <= 16, AA with the drivers'
     settings -- one SPG iteration per dictionary update, fewer than 65 536 samples, k <= 16):
     the restarts run ``n_slots`` at a time (default: 64 // k for GPNH, 32 // k for AA) in ONE set of
-    device arrays per device and share every launch of an outer iteration (``_fit_gpnh_slots``,
-    ``_fit_aa_slots``); with several ``devices`` restart i runs on device i mod G; ``n_jobs`` is not
-    used then.
+    device arrays per device and share every launch of an outer iteration (``_fit_slots``); with
+    several ``devices`` restart i runs on device i mod G; ``n_jobs`` is not used then.
     Returns ``(models, best)``: the fitted models in restart order and the index of the first one
     with the lowest cost (the model the drivers' ``if cost < best_cost`` loop keeps)."""
     data = np.asarray(data)

@@ -152,7 +152,8 @@ struct Ctx {
     hipStream_t stream3 = nullptr;             // the live consumers of parked QP samples (qp_live): a queue of
                                                // their own, stream2 may still hold the residual projection
     hipEvent_t evFork = nullptr, evJoin = nullptr;
-    // GPNH restarts side by side (aa_gpnh_slots_*): per-slot cost records, counters, status, initial costs
+    // restarts side by side, both families (aa_slots_*, aa_gpnh_slots_*): per-slot cost records, counters,
+    // status, initial costs
     DevBuf slotCosts, slotCounters, slotStates, slotCost0;
     int slots_R = 0, slots_k = 0, slots_stride = 0, slots_max_outer = 0;
     // AA restarts side by side (aa_slots_*): the launchers of the coupled steps pick their per-slot
@@ -163,7 +164,7 @@ struct Ctx {
                                                // factors, products recomputed); slots_cold_cols: their columns
     unsigned slots_cold_cols = 0xffffffffu;
     DevBuf slotSaveP, slotSaveGr;              // C X and (C X X')' of the running slots across a reload
-    DevBuf slotScal, slotSnapP;
+    DevBuf slotSnapP;                          // C X of every slot at its stopping iteration
     aa_iter_params slots_ip;
     aa_spg_params slots_sp, slots_scale_sp;
     aa_gpnh_params slots_gp;

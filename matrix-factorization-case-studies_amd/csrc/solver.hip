@@ -1575,6 +1575,143 @@ int aa_gpnh_iterate(aa_ctx *h, const aa_gpnh_params *gp, const aa_qp_params *qp,
     return AA_OK;
 }
 
+// ------------------------------------------------------------------ restart slots: the host steps both families share
+// (AA: aa_slots_*, GPNH: aa_gpnh_slots_*.)  Restart r lives in columns [r k, (r + 1) k) of the tall arrays
+// and rows [r k, (r + 1) k) of the wide ones; per slot there is a cost record, a counter, an IterState
+// and an initial cost (Ctx::slot*).
+
+// begin, the common part: whatever an earlier slot run of either family left -- ended or not -- gives way
+// to fresh, zeroed factor arrays of R k components; trace, unit scale factors, the slot geometry, the
+// per-slot records allocated.  The callers check their arguments and do everything family-specific.
+static int slots_begin_common(Ctx *c, int R, int k, int max_outer)
+{
+    c->slots_aa = false;
+    c->slots_started = false;
+    c->products_valid = false;
+    c->k = 0;                                         // force fresh, zeroed factor arrays
+    AA_CHECK(ensure_problem(c, R * k));
+    AA_CHECK(ensure_trace(c));
+    for (int i = 0; i < c->k; ++i) c->alpha[i] = 1.0;
+    AA_CHECK(upload_alpha(c));
+    c->slots_R = R;
+    c->slots_k = k;
+    c->slots_max_outer = max_outer;
+    c->slots_stride = 2 * max_outer + 64;
+    AA_CHECK(c->slotCosts.alloc((size_t)R * c->slots_stride * sizeof(double)));
+    AA_CHECK(c->slotCounters.alloc(64 * sizeof(int)));
+    AA_CHECK(c->slotStates.alloc(32 * sizeof(IterState)));
+    AA_CHECK(c->slotCost0.alloc(32 * sizeof(double)));
+    return AA_OK;
+}
+
+// every slot empty (stop = 1: the judge leaves it alone), every counter zero
+static int slots_empty_records(Ctx *c)
+{
+    std::vector<IterState> st(32);
+    memset(st.data(), 0, st.size() * sizeof(IterState));
+    for (int r = 0; r < 32; ++r) st[r].stop = 1;
+    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.p, st.data(), st.size() * sizeof(IterState), hipMemcpyHostToDevice));
+    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.p, 0, 64 * sizeof(int)));
+    return AA_OK;
+}
+
+// slot r takes a new restart: running state, no iteration counted
+static int slot_clear_record(Ctx *c, int r)
+{
+    IterState zero;
+    memset(&zero, 0, sizeof(zero));
+    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.as<IterState>() + r, &zero, sizeof(zero), hipMemcpyHostToDevice));
+    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.as<int>() + r, 0, sizeof(int)));
+    return AA_OK;
+}
+
+// columns [o, o + slots_k) of a tall device array (row stride KP) <-> a dense n x slots_k host array
+static int slot_put_tall(Ctx *c, DevBuf &dst, int o, const double *src)
+{
+    const size_t w = (size_t)c->slots_k * sizeof(double);
+    AA_CHECK_HIP(ctx_memcpy2d(c, dst.as<double>() + o, (size_t)c->KP * sizeof(double), src, w, w, (size_t)c->n,
+                             hipMemcpyHostToDevice));
+    return AA_OK;
+}
+
+static int slot_get_tall(Ctx *c, const DevBuf &src, int o, double *dst)
+{
+    const size_t w = (size_t)c->slots_k * sizeof(double);
+    AA_CHECK_HIP(ctx_memcpy2d(c, dst, w, src.as<double>() + o, (size_t)c->KP * sizeof(double), w, (size_t)c->n,
+                             hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+// the same columns <-> the caller's slots_k x n array C (leading dimension ldc): transposed on the host
+static int slot_put_tall_T(Ctx *c, DevBuf &dst, int o, const double *C, long ldc)
+{
+    const int k = c->slots_k;
+    std::vector<double> ct((size_t)c->n * k);
+    for (long row = 0; row < c->n; ++row)
+        for (int i = 0; i < k; ++i) ct[(size_t)row * k + i] = C[(size_t)i * ldc + row];
+    return slot_put_tall(c, dst, o, ct.data());
+}
+
+static int slot_get_tall_T(Ctx *c, const DevBuf &src, int o, double *C, long ldc)
+{
+    const int k = c->slots_k;
+    std::vector<double> ct((size_t)c->n * k);
+    AA_CHECK(slot_get_tall(c, src, o, ct.data()));
+    for (long row = 0; row < c->n; ++row)
+        for (int i = 0; i < k; ++i) C[(size_t)i * ldc + row] = ct[(size_t)row * k + i];
+    return AA_OK;
+}
+
+// rows [o, o + slots_k) of a wide device array (row stride p_pad) <-> a slots_k x p host array (leading dimension ld)
+static int slot_put_wide(Ctx *c, DevBuf &dst, int o, const double *src, long ld)
+{
+    AA_CHECK_HIP(ctx_memcpy2d(c, dst.as<double>() + (size_t)o * c->p_pad, (size_t)c->p_pad * sizeof(double), src,
+                             (size_t)ld * sizeof(double), (size_t)c->p * sizeof(double), (size_t)c->slots_k,
+                             hipMemcpyHostToDevice));
+    return AA_OK;
+}
+
+static int slot_get_wide(Ctx *c, const DevBuf &src, int o, double *dst, long ld)
+{
+    AA_CHECK_HIP(ctx_memcpy2d(c, dst, (size_t)ld * sizeof(double), src.as<double>() + (size_t)o * c->p_pad,
+                             (size_t)c->p_pad * sizeof(double), (size_t)c->p * sizeof(double), (size_t)c->slots_k,
+                             hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+// cost record (2 (stop_iter + 1) values) and initial cost of slot r, which must have stopped
+static int slot_fetch_record(Ctx *c, int r, double *costs, double *cost0)
+{
+    IterState st;
+    AA_CHECK_HIP(ctx_memcpy(c, &st, c->slotStates.as<IterState>() + r, sizeof(st), hipMemcpyDeviceToHost));
+    AA_REQUIRE(st.stop, AA_ERR_STATE, "slot %d has not stopped", r);
+    AA_CHECK_HIP(ctx_memcpy(c, costs, c->slotCosts.as<double>() + (size_t)r * c->slots_stride,
+                           (size_t)2 * (st.stop_iter + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    AA_CHECK_HIP(ctx_memcpy(c, cost0, c->slotCost0.as<double>() + r, sizeof(double), hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+// the tail of a run call: waits for the iterations, status of every slot out.  flags: the SPG warning
+// flags of the slot (AA) or "normal equations not positive definite" (GPNH: IterState::pad0)
+static int slots_read_status(Ctx *c, aa_slot_status *status, bool aa)
+{
+    const int R = c->slots_R;
+    std::vector<IterState> st(R);
+    std::vector<int> cnt(R);
+    AA_CHECK_HIP(hipMemcpyAsync(st.data(), c->slotStates.p, (size_t)R * sizeof(IterState), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipMemcpyAsync(cnt.data(), c->slotCounters.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    for (int r = 0; r < R; ++r) {
+        status[r].stop = st[r].stop;
+        status[r].converged = st[r].converged;
+        status[r].error_stage = st[r].error_stage;
+        status[r].stop_iter = st[r].stop_iter;
+        status[r].flags = aa ? st[r].spg_flags : st[r].pad0;
+        status[r].iterations_run = cnt[r] / 2;
+    }
+    return AA_OK;
+}
+
 // ------------------------------------------------------------------ AA restarts side by side
 // (bin/run_hadisst_aa.py:149-174).  R independent fits of k components each in the
 // component slots of ONE set of device arrays (restart r: columns [r k, (r + 1) k) of C' and Z): the
@@ -1604,24 +1741,11 @@ int aa_slots_begin(aa_ctx *h, int R, int k, const aa_iter_params *ip, const aa_s
     AA_REQUIRE(ip->max_outer >= 1 && ip->update_dictionary && ip->update_weights, AA_ERR_ARG, "slots: both updates");
     AA_REQUIRE(spg->max_iterations == 1 && spg->memory <= 16, AA_ERR_ARG, "slots: one SPG iteration per dictionary update");
     AA_REQUIRE(g_fuse_finalize && g_proj_mode == 0, AA_ERR_STATE, "slots: default projection options");
-    c->slots_aa = false;
-    c->k = 0;                                         // fresh, zeroed factor arrays
-    AA_CHECK(ensure_problem(c, R * k));
-    AA_CHECK(ensure_trace(c));
-    for (int i = 0; i < c->k; ++i) c->alpha[i] = 1.0;
-    AA_CHECK(upload_alpha(c));
-    c->slots_R = R;
-    c->slots_k = k;
-    c->slots_max_outer = ip->max_outer;
-    c->slots_stride = 2 * ip->max_outer + 64;
+    AA_CHECK(slots_begin_common(c, R, k, ip->max_outer));
     c->slots_ip = *ip;
     c->slots_sp = *spg;
     c->slots_qp = *qp;
     if (scale_spg) c->slots_scale_sp = *scale_spg;
-    AA_CHECK(c->slotCosts.alloc((size_t)R * c->slots_stride * sizeof(double)));
-    AA_CHECK(c->slotCounters.alloc(64 * sizeof(int)));
-    AA_CHECK(c->slotStates.alloc(32 * sizeof(IterState)));
-    AA_CHECK(c->slotCost0.alloc(32 * sizeof(double)));
     AA_CHECK(c->snapAlpha.alloc(64 * sizeof(double)));
     c->scalars.release();
     AA_CHECK(c->scalars.alloc((size_t)(R + 1) * AA_SC_STRIDE * sizeof(double)));      // one block per slot
@@ -1631,11 +1755,7 @@ int aa_slots_begin(aa_ctx *h, int R, int k, const aa_iter_params *ip, const aa_s
     AA_CHECK(c->slotSnapP.alloc((size_t)c->KP * c->p_pad * sizeof(double)));
     AA_CHECK_HIP(ctx_memset(c, c->snapC.p, 0, tall_bytes));
     AA_CHECK_HIP(ctx_memset(c, c->snapZ.p, 0, tall_bytes));
-    std::vector<IterState> st(32);
-    memset(st.data(), 0, st.size() * sizeof(IterState));
-    for (int r = 0; r < 32; ++r) st[r].stop = 1;      // empty
-    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.p, st.data(), st.size() * sizeof(IterState), hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.p, 0, 64 * sizeof(int)));
+    AA_CHECK(slots_empty_records(c));
     AA_CHECK_HIP(ctx_memset(c, c->Ct.p, 0, tall_bytes));
     AA_CHECK_HIP(ctx_memset(c, c->Zt.p, 0, tall_bytes));
     AA_CHECK_HIP(ctx_memset(c, c->Mdev.p, 0, (size_t)c->KP * c->KP * sizeof(double)));
@@ -1653,24 +1773,30 @@ int aa_slots_begin(aa_ctx *h, int R, int k, const aa_iter_params *ip, const aa_s
         c->projPassHint[m] = c->projPassHint2[m] = 0;
         c->projListShort[m] = false;
     }
-    c->slots_started = false;
     return AA_OK;
 }
 
-// start factors of a restart into slot r (C: k x n, leading dimension ldc; Z: n x k), the products of
-// the stacked state rebuilt (aa_prepare's passes), the slot's initial cost
-static int slots_set_alpha(Ctx *c, int r, const double *alpha, bool running)
+// the head of a load and of a reload: the caller's factors into slot r's columns of C' and Z (C: k x n,
+// leading dimension ldc; Z: n x k), its record cleared, its scale factors set (null: ones)
+static int slot_upload_aa(Ctx *c, int r, const double *C, long ldc, const double *Z, const double *alpha, bool running)
 {
-    // the host copy follows the device's (the scale-factor kernel moves the running slots' factors)
-    if (running) {
+    const int o = r * c->slots_k;
+    AA_CHECK(join_side(c));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK(slot_put_tall_T(c, c->Ct, o, C, ldc));
+    AA_CHECK(slot_put_tall(c, c->Zt, o, Z));
+    AA_CHECK(slot_clear_record(c, r));
+    if (running) {   // the host copy follows the device's (the scale-factor kernel moves the running slots' factors)
         std::vector<double> a(c->KP, 1.0);
         AA_CHECK_HIP(ctx_memcpy(c, a.data(), c->alphaDev.p, (size_t)c->KP * sizeof(double), hipMemcpyDeviceToHost));
         for (int i = 0; i < c->k; ++i) c->alpha[i] = a[i];
     }
-    for (int i = 0; i < c->slots_k; ++i) c->alpha[r * c->slots_k + i] = alpha ? alpha[i] : 1.0;
+    for (int i = 0; i < c->slots_k; ++i) c->alpha[o + i] = alpha ? alpha[i] : 1.0;
     return upload_alpha(c);
 }
 
+// start factors of a restart into slot r; the first run call rebuilds the products of the stacked
+// state (aa_prepare's passes) and forms the slots' initial costs
 int aa_slots_load(aa_ctx *h, int r, const double *C, long ldc, const double *Z, const double *alpha)
 {
     AA_REQUIRE(h && C && Z, AA_ERR_ARG, "null argument");
@@ -1678,21 +1804,7 @@ int aa_slots_load(aa_ctx *h, int r, const double *C, long ldc, const double *Z, 
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->slots_aa && r >= 0 && r < c->slots_R, AA_ERR_ARG, "slot %d out of range", r);
     AA_REQUIRE(ldc >= c->n, AA_ERR_ARG, "ldc < n");
-    const int k = c->slots_k, o = r * k;
-    AA_CHECK(join_side(c));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    std::vector<double> ct((size_t)c->n * k);
-    for (long row = 0; row < c->n; ++row)
-        for (int i = 0; i < k; ++i) ct[(size_t)row * k + i] = C[(size_t)i * ldc + row];
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->Ct.as<double>() + o, (size_t)c->KP * sizeof(double), ct.data(), (size_t)k * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->Zt.as<double>() + o, (size_t)c->KP * sizeof(double), Z, (size_t)k * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyHostToDevice));
-    IterState zero;
-    memset(&zero, 0, sizeof(zero));
-    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.as<IterState>() + r, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.as<int>() + r, 0, sizeof(int)));
-    AA_CHECK(slots_set_alpha(c, r, alpha, false));
+    AA_CHECK(slot_upload_aa(c, r, C, ldc, Z, alpha, false));
     c->products_valid = false;
     c->grams_valid = false;
     c->slots_started = false;
@@ -1710,20 +1822,7 @@ int aa_slots_reload(aa_ctx *h, int r, const double *C, long ldc, const double *Z
     AA_REQUIRE(c->slots_aa && c->slots_started && r >= 0 && r < c->slots_R, AA_ERR_ARG, "slot %d out of range", r);
     AA_REQUIRE(ldc >= c->n, AA_ERR_ARG, "ldc < n");
     const int k = c->slots_k, o = r * k, KP = c->KP;
-    AA_CHECK(join_side(c));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    std::vector<double> ct((size_t)c->n * k);
-    for (long row = 0; row < c->n; ++row)
-        for (int i = 0; i < k; ++i) ct[(size_t)row * k + i] = C[(size_t)i * ldc + row];
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->Ct.as<double>() + o, (size_t)KP * sizeof(double), ct.data(), (size_t)k * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->Zt.as<double>() + o, (size_t)KP * sizeof(double), Z, (size_t)k * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyHostToDevice));
-    IterState zero;
-    memset(&zero, 0, sizeof(zero));
-    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.as<IterState>() + r, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.as<int>() + r, 0, sizeof(int)));
-    AA_CHECK(slots_set_alpha(c, r, alpha, true));
+    AA_CHECK(slot_upload_aa(c, r, C, ldc, Z, alpha, true));
     // a fit starts its projections cold (aa_set_state): a warm threshold of +inf selects nothing, which
     // is the cold start of k_proj_small -- for this slot's columns, in both projection states
     {
@@ -1782,17 +1881,16 @@ int aa_slots_reload(aa_ctx *h, int r, const double *C, long ldc, const double *Z
 }
 
 // n_iters outer iterations of every slot; status[R] out.  The first call after the loads prepares the
-// stacked state the way aa_set_state + aa_prepare prepare a single fit (all slots of a group start
-// together: the first dictionary update of a fit projects the caller's factors and recomputes the
-// products, later ones start from the previous update's -- a host-side choice that the slots share,
-// which is why a group is loaded as a whole and a finished slot waits for the others).
+// stacked state the way aa_set_state + aa_prepare prepare a single fit: the slots of the first group
+// start together, with the cold dictionary update of a fit (the caller's factors projected, the products
+// recomputed).  A slot freed later is refilled while the others run (aa_slots_reload): slots_cold marks
+// it, and the next update is cold for its columns only.
 int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
 {
     AA_REQUIRE(h && status && n_iters >= 1, AA_ERR_ARG, "bad argument");
     Ctx *c = &h->c;
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->slots_aa && c->slots_R > 0, AA_ERR_STATE, "aa_slots_begin first");
-    const int R = c->slots_R;
     if (!c->slots_started) {
         c->x_feasible = false;
         AA_CHECK(prepare(c, nullptr));
@@ -1821,45 +1919,12 @@ int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
         AA_CHECK(launch_aa_cost_slots(c, 2, &c->slots_ip));
         AA_CHECK(launch_aa_snap_slots(c));
     }
-    std::vector<IterState> st(R);
-    std::vector<int> cnt(R);
-    AA_CHECK_HIP(hipMemcpyAsync(st.data(), c->slotStates.p, (size_t)R * sizeof(IterState), hipMemcpyDeviceToHost, c->stream));
-    AA_CHECK_HIP(hipMemcpyAsync(cnt.data(), c->slotCounters.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < R; ++r) {
-        status[r].stop = st[r].stop;
-        status[r].converged = st[r].converged;
-        status[r].error_stage = st[r].error_stage;
-        status[r].stop_iter = st[r].stop_iter;
-        status[r].not_spd = st[r].spg_flags;          // AA: the SPG warning flags of the slot
-        status[r].iterations_run = cnt[r] / 2;
-    }
-    return AA_OK;
-}
-
-// every slot has stopped: the factors of the stopping iterations back into the working arrays and the
-// products rebuilt from them (what aa_iterate does for a fit that ran past its stopping iteration)
-int aa_slots_finish(aa_ctx *h)
-{
-    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
-    Ctx *c = &h->c;
-    AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_REQUIRE(c->slots_aa && c->slots_started, AA_ERR_STATE, "nothing to finish");
-    AA_CHECK(join_side(c));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    const size_t tall_bytes = (size_t)c->n_pad * c->KP * sizeof(double);
-    AA_CHECK_HIP(ctx_memcpy(c, c->Ct.p, c->snapC.p, tall_bytes, hipMemcpyDeviceToDevice));
-    AA_CHECK_HIP(ctx_memcpy(c, c->Zt.p, c->snapZ.p, tall_bytes, hipMemcpyDeviceToDevice));
-    c->products_valid = false;
-    c->grams_valid = false;
-    AA_CHECK(prepare(c, nullptr));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    return AA_OK;
+    return slots_read_status(c, status, true);
 }
 
 // factors (C: k x n with leading dimension ldc, Z: n x k), C X (k x p, leading dimension ldx: recomputed
-// from the fetched C after aa_slots_finish, or -- carried != 0 -- as the loop carried it at the stopping
-// iteration), cost record and initial cost of a stopped slot
+// from the fetched C, or -- carried != 0 -- as the loop carried it at the stopping iteration), cost record
+// and initial cost of a stopped slot
 int aa_slots_fetch(aa_ctx *h, int r, double *C, long ldc, double *Z, double *CX, long ldx, int carried,
                    double *costs, double *cost0, double *alpha)
 {
@@ -1868,25 +1933,15 @@ int aa_slots_fetch(aa_ctx *h, int r, double *C, long ldc, double *Z, double *CX,
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->slots_aa && r >= 0 && r < c->slots_R, AA_ERR_ARG, "slot %d out of range", r);
     AA_REQUIRE(ldc >= c->n, AA_ERR_ARG, "ldc < n");
+    AA_REQUIRE(ldx >= c->p, AA_ERR_ARG, "ldx < p");
     AA_CHECK(join_side(c));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    IterState st;
-    AA_CHECK_HIP(ctx_memcpy(c, &st, c->slotStates.as<IterState>() + r, sizeof(st), hipMemcpyDeviceToHost));
-    AA_REQUIRE(st.stop, AA_ERR_STATE, "slot %d has not stopped", r);
+    AA_CHECK(slot_fetch_record(c, r, costs, cost0));
     const int k = c->slots_k, o = r * k;
-    std::vector<double> ct((size_t)c->n * k);
-    AA_CHECK_HIP(ctx_memcpy2d(c, ct.data(), (size_t)k * sizeof(double), c->snapC.as<double>() + o, (size_t)c->KP * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyDeviceToHost));
-    for (long row = 0; row < c->n; ++row)
-        for (int i = 0; i < k; ++i) C[(size_t)i * ldc + row] = ct[(size_t)row * k + i];
-    AA_CHECK_HIP(ctx_memcpy2d(c, Z, (size_t)k * sizeof(double), c->snapZ.as<double>() + o, (size_t)c->KP * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyDeviceToHost));
-    AA_CHECK_HIP(ctx_memcpy(c, costs, c->slotCosts.as<double>() + (size_t)r * c->slots_stride,
-                           (size_t)2 * (st.stop_iter + 1) * sizeof(double), hipMemcpyDeviceToHost));
-    AA_CHECK_HIP(ctx_memcpy(c, cost0, c->slotCost0.as<double>() + r, sizeof(double), hipMemcpyDeviceToHost));
-    if (alpha)                                                // the scale factors of the stopping iteration
+    AA_CHECK(slot_get_tall_T(c, c->snapC, o, C, ldc));        // the factors of the stopping iteration
+    AA_CHECK(slot_get_tall(c, c->snapZ, o, Z));
+    if (alpha)                                                // ... and its scale factors
         AA_CHECK_HIP(ctx_memcpy(c, alpha, c->snapAlpha.as<double>() + o, (size_t)k * sizeof(double), hipMemcpyDeviceToHost));
-    AA_REQUIRE(ldx >= c->p, AA_ERR_ARG, "ldx < p");
     if (!carried) {
         // C X recomputed from the stopping iteration's dictionary: the pass aa_prepare runs (on the
         // scratch arrays of the dictionary update, free between iterations)
@@ -1894,10 +1949,7 @@ int aa_slots_fetch(aa_ctx *h, int r, double *C, long ldc, double *Z, double *CX,
         AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr));
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     }
-    const double *src = (carried ? c->slotSnapP.as<double>() : c->Q.as<double>()) + (size_t)o * c->p_pad;
-    AA_CHECK_HIP(ctx_memcpy2d(c, CX, (size_t)ldx * sizeof(double), src, (size_t)c->p_pad * sizeof(double),
-                             (size_t)c->p * sizeof(double), (size_t)k, hipMemcpyDeviceToHost));
-    return AA_OK;
+    return slot_get_wide(c, carried ? c->slotSnapP : c->Q, o, CX, ldx);
 }
 
 // leaves the slot mode (the context can be used for single fits again)
@@ -1942,33 +1994,14 @@ int aa_gpnh_slots_begin(aa_ctx *h, int R, int k, const aa_gpnh_params *gp, const
     AA_REQUIRE(qp->max_iterations >= 1 && qp->memory <= 8, AA_ERR_ARG, "slots: QP max_iterations >= 1, memory <= 8");
     AA_REQUIRE(qp->max_iterations <= 4 || (qp->memory <= 1 && k <= 16 && c->n < 65536), AA_ERR_ARG,
                "slots: QPs of more than four passes need memory 1, k <= 16, fewer than 65 536 samples");
-    c->k = 0;                                         // force fresh, zeroed factor arrays
-    c->slots_aa = false;                              // (an AA slot run that was never ended)
-    c->slots_started = false;
-    c->products_valid = false;
-    AA_CHECK(ensure_problem(c, R * k));
-    AA_CHECK(ensure_trace(c));
-    for (int i = 0; i < c->k; ++i) c->alpha[i] = 1.0;
-    AA_CHECK(upload_alpha(c));
-    c->slots_R = R;
-    c->slots_k = k;
-    c->slots_max_outer = ip->max_outer;
-    c->slots_stride = 2 * ip->max_outer + 64;
+    AA_CHECK(slots_begin_common(c, R, k, ip->max_outer));
     c->slots_gp = *gp;
     c->slots_qp = *qp;
-    AA_CHECK(c->slotCosts.alloc((size_t)R * c->slots_stride * sizeof(double)));
-    AA_CHECK(c->slotCounters.alloc(64 * sizeof(int)));
-    AA_CHECK(c->slotStates.alloc(32 * sizeof(IterState)));
-    AA_CHECK(c->slotCost0.alloc(32 * sizeof(double)));
     size_t snap_bytes = (size_t)c->n_pad * c->KP * sizeof(double);
     if ((size_t)c->KP * c->p_pad * sizeof(double) > snap_bytes) snap_bytes = (size_t)c->KP * c->p_pad * sizeof(double);
     AA_CHECK(c->snapC.alloc(snap_bytes));
     AA_CHECK(c->snapZ.alloc(snap_bytes));
-    std::vector<IterState> st(32);
-    memset(st.data(), 0, st.size() * sizeof(IterState));
-    for (int r = 0; r < 32; ++r) st[r].stop = 1;      // empty: the judge leaves it alone
-    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.p, st.data(), st.size() * sizeof(IterState), hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.p, 0, 64 * sizeof(int)));
+    AA_CHECK(slots_empty_records(c));
     AA_CHECK_HIP(ctx_memset(c, c->Zt.p, 0, (size_t)c->n_pad * c->KP * sizeof(double)));
     AA_CHECK_HIP(ctx_memset(c, c->P.p, 0, (size_t)c->KP * c->p_pad * sizeof(double)));
     AA_CHECK_HIP(ctx_memset(c, c->gramState.p, 0, (size_t)3 * c->KP * c->KP * sizeof(double)));
@@ -1988,17 +2021,11 @@ int aa_gpnh_slots_load(aa_ctx *h, int r, const double *Wt, long ld, const double
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->slots_R > 0 && r >= 0 && r < c->slots_R, AA_ERR_ARG, "slot %d out of range", r);
     AA_REQUIRE(ld >= c->p, AA_ERR_ARG, "ld < p");
-    const int k = c->slots_k, o = r * k;
+    const int o = r * c->slots_k;
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->P.as<double>() + (size_t)o * c->p_pad, (size_t)c->p_pad * sizeof(double), Wt,
-                             (size_t)ld * sizeof(double), (size_t)c->p * sizeof(double), (size_t)k,
-                             hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->Zt.as<double>() + o, (size_t)c->KP * sizeof(double), Z, (size_t)k * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyHostToDevice));
-    IterState zero;
-    memset(&zero, 0, sizeof(zero));
-    AA_CHECK_HIP(ctx_memcpy(c, c->slotStates.as<IterState>() + r, &zero, sizeof(zero), hipMemcpyHostToDevice));
-    AA_CHECK_HIP(ctx_memset(c, c->slotCounters.as<int>() + r, 0, sizeof(int)));
+    AA_CHECK(slot_put_wide(c, c->P, o, Wt, ld));
+    AA_CHECK(slot_put_tall(c, c->Zt, o, Z));
+    AA_CHECK(slot_clear_record(c, r));
     // the products of the stacked factors (the other slots' parts come out as they were) and this
     // slot's initial cost, the way aa_gpnh_iterate forms it
     AA_CHECK(launch_wide_to_T(c, c->P.as<double>(), operandT(c, c->P, c->Pw)));
@@ -2020,7 +2047,7 @@ int aa_gpnh_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
     const int R = c->slots_R, k = c->slots_k;
     const double lambda = c->slots_gp.lambda_W;
     const aa_iter_params *ip = &c->slots_gp.loop;
-    const unsigned all = R >= 32 ? 0xffffffffu : ((1u << R) - 1u);
+    const unsigned all = slots_all_mask(c);
     // the single fit forms W'W inside its cost kernel when the factor is small (gpnh_cost_can_gram
     // with ITS k); the slots follow the same rule so that every restart sees the same bits
     const bool gram_in_cost = k * k <= 256 && (long)k * c->p_pad <= 4096;
@@ -2038,20 +2065,7 @@ int aa_gpnh_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
         AA_CHECK(launch_gpnh_cost_slots(c, lambda, all, 2, ip, false));
         AA_CHECK(launch_gpnh_snap_slots(c));
     }
-    std::vector<IterState> st(R);
-    std::vector<int> cnt(R);
-    AA_CHECK_HIP(hipMemcpyAsync(st.data(), c->slotStates.p, (size_t)R * sizeof(IterState), hipMemcpyDeviceToHost, c->stream));
-    AA_CHECK_HIP(hipMemcpyAsync(cnt.data(), c->slotCounters.p, (size_t)R * sizeof(int), hipMemcpyDeviceToHost, c->stream));
-    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    for (int r = 0; r < R; ++r) {
-        status[r].stop = st[r].stop;
-        status[r].converged = st[r].converged;
-        status[r].error_stage = st[r].error_stage;
-        status[r].stop_iter = st[r].stop_iter;
-        status[r].not_spd = st[r].pad0;
-        status[r].iterations_run = cnt[r] / 2;
-    }
-    return AA_OK;
+    return slots_read_status(c, status, false);
 }
 
 int aa_gpnh_slots_fetch(aa_ctx *h, int r, double *Wt, long ld, double *Z, double *costs, double *cost0)
@@ -2062,20 +2076,10 @@ int aa_gpnh_slots_fetch(aa_ctx *h, int r, double *Wt, long ld, double *Z, double
     AA_REQUIRE(c->slots_R > 0 && r >= 0 && r < c->slots_R, AA_ERR_ARG, "slot %d out of range", r);
     AA_REQUIRE(ld >= c->p, AA_ERR_ARG, "ld < p");
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    IterState st;
-    AA_CHECK_HIP(ctx_memcpy(c, &st, c->slotStates.as<IterState>() + r, sizeof(st), hipMemcpyDeviceToHost));
-    AA_REQUIRE(st.stop, AA_ERR_STATE, "slot %d has not stopped", r);
-    const int k = c->slots_k, o = r * k;
-    // the factors of the stopping iteration (k_gpnh_snap_slots)
-    AA_CHECK_HIP(ctx_memcpy2d(c, Wt, (size_t)ld * sizeof(double), c->snapC.as<double>() + (size_t)o * c->p_pad,
-                             (size_t)c->p_pad * sizeof(double), (size_t)c->p * sizeof(double), (size_t)k,
-                             hipMemcpyDeviceToHost));
-    AA_CHECK_HIP(ctx_memcpy2d(c, Z, (size_t)k * sizeof(double), c->snapZ.as<double>() + o, (size_t)c->KP * sizeof(double),
-                             (size_t)k * sizeof(double), (size_t)c->n, hipMemcpyDeviceToHost));
-    AA_CHECK_HIP(ctx_memcpy(c, costs, c->slotCosts.as<double>() + (size_t)r * c->slots_stride,
-                           (size_t)2 * (st.stop_iter + 1) * sizeof(double), hipMemcpyDeviceToHost));
-    AA_CHECK_HIP(ctx_memcpy(c, cost0, c->slotCost0.as<double>() + r, sizeof(double), hipMemcpyDeviceToHost));
-    return AA_OK;
+    AA_CHECK(slot_fetch_record(c, r, costs, cost0));
+    const int o = r * c->slots_k;
+    AA_CHECK(slot_get_wide(c, c->snapC, o, Wt, ld));          // the factors of the stopping iteration (k_gpnh_snap_slots)
+    return slot_get_tall(c, c->snapZ, o, Z);
 }
 
 int aa_gpnh_residual_cost(aa_ctx *h, double *cost)

@@ -372,6 +372,128 @@ def test_restart_feed_draws_in_the_sequential_loops_order():
         bad.join()
 
 
+class _PlaybackContext(object):
+    """Stands in for _backend.Context under restarts._fit_slots: a slot stops after weights[0, 0] polls with
+    status flags weights[0, 1] and error stage weights[0, 2]; every call is logged."""
+    dtype_code = _backend.AA_F64
+    log = []
+
+    def __init__(self, dtype=None, device=None):
+        self.loaded = {}
+
+    def set_data(self, X):
+        pass
+
+    def _begin(self, n_slots, *args, **kw):
+        self.n_slots = n_slots
+        self.log.append(("begin", n_slots))
+
+    gpnh_slots_begin = aa_slots_begin = _begin
+
+    def _put(name):
+        def put(self, r, dictionary, weights, alpha=None):
+            self.loaded[r] = [0] + [int(v) for v in weights[0]]
+            self.log.append((name, r))
+        return put
+
+    gpnh_slots_load, aa_slots_load, aa_slots_reload = _put("gpnh_load"), _put("load"), _put("reload")
+
+    def _run(self, n_iters):
+        out = []
+        for r in range(self.n_slots):
+            slot = self.loaded.get(r, [0, 0, 0, 0])
+            slot[0] += 1
+            polls, need, flags, stage = slot
+            stop = int(polls >= need)
+            out.append(_backend.SlotStatus(stop, 1, stage if stop else 0, n_iters * need - 1, flags, n_iters * polls))
+        return out
+
+    gpnh_slots_run = aa_slots_run = _run
+
+    def gpnh_slots_fetch(self, r, stop_iter):
+        self.log.append(("fetch", r))
+        return np.zeros((3, 2)), np.zeros((4, 2)), 5.0, np.arange(2.0 * (stop_iter + 1))[::-1].copy()
+
+    def aa_slots_fetch(self, r, stop_iter, carried):
+        self.log.append(("fetch", r, bool(carried)))
+        return (np.zeros((3, 2)), np.ones((2, 3)), np.ones((2, 4)), 5.0,
+                np.arange(2.0 * (stop_iter + 1))[::-1].copy(), np.full(2, 2.0))
+
+    def aa_slots_end(self):
+        self.log.append("end")
+
+    def close(self):
+        self.log.append("close")
+
+
+def _playback_start(polls, flags=0, stage=0):
+    Z = np.zeros((3, 3))
+    Z[0] = (polls, flags, stage)
+    return dict(dictionary=np.zeros((2, 3)), weights=Z, alpha=np.ones(2))
+
+
+@pytest.mark.parametrize("family", ["gpnh", "aa"])
+def test_slot_driver_on_a_stand_in_context(family, monkeypatch, capsys):
+    """restarts._fit_slots without a device: five restarts in two slots.  The refill order, aa_slots_load
+    for the first group against aa_slots_reload afterwards, a GPNH slot with its flag set going to the
+    sequential path unfetched, the SPG warning of a stopped AA slot, the attributes and the element type
+    of cost_deltas, the carried rule, the profile keys, the verbose tables in restart order, the context
+    ended and closed; and the error of the lowest restart raised after every slot has been served, an AA
+    slot's warning issued before its error is recorded."""
+    from convex_dim_red import restarts
+    monkeypatch.setattr(_backend, "Context", _PlaybackContext)
+    gpnh = family == "gpnh"
+    fit = restarts._fit_gpnh_slots if gpnh else restarts._fit_aa_slots
+    make = ((lambda: cdr.GPNHConvexCoding(2, max_iterations=100, tolerance=1e-3, verbose=True)) if gpnh else
+            (lambda: cdr.ArchetypalAnalysis(2, max_iterations=100, tolerance=1e-3, verbose=True, delta=0.1)))
+    models = [make() for _ in range(5)]
+    starts = [_playback_start(1), _playback_start(2, flags=1 if gpnh else _backend.SPG_FLAG_MAX_ITER),
+              _playback_start(1), _playback_start(3), _playback_start(1)]
+    _PlaybackContext.log = log = []
+    restarts.slots_profile.clear()
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        left = fit(models, starts, np.zeros((3, 4)), None, n_slots=2)
+    first, later = ("gpnh_load", "gpnh_load") if gpnh else ("load", "reload")
+    refills = [0, 1, 0] if gpnh else [0, 0, 1]        # (the GPNH slot 1 is freed at once: its flag is set)
+    assert [e for e in log if e[0] != "fetch"] == ([("begin", 2), (first, 0), (first, 1)]
+                                                   + [(later, r) for r in refills] + ["end", "close"])
+    assert left == ([1] if gpnh else [])
+    assert len(caught) == (0 if gpnh else 1)
+    done = [m for i, m in enumerate(models) if not (gpnh and i == 1)]
+    assert [m.n_iter for m in done] == ([7, 7, 23, 7] if gpnh else [7, 15, 7, 23, 7])
+    for m in done:
+        assert m.cost == 0.0 and len(m.cost_deltas) == m.n_iter + 1 and m.cost_deltas[0] == 2.0 * m.n_iter - 5.0
+        assert type(m.cost_deltas[0]) is (float if gpnh else np.float64)
+        assert m.avg_time_per_iter > 0 and m.weights.shape == (3, 2)
+    if gpnh:
+        assert sum(e[0] == "fetch" for e in log) == 4                          # restart 1 is not fetched
+    else:
+        assert all(e[2] for e in log if e[0] == "fetch")                       # stopped on the last iteration of a batch
+        m = models[0]                                                          # delta != 0: scaled by alpha
+        assert np.array_equal(m.dictionary, np.full((2, 3), 2.0)) and np.array_equal(m.archetypes, np.full((2, 4), 2.0))
+        assert np.array_equal(m.alpha, np.full(2, 2.0))
+    assert sorted(restarts.slots_profile) == ["fetch", "load", "polls", "run", "slots"]
+    assert restarts.slots_profile["slots"] == 2 and restarts.slots_profile["polls"] == (4 if gpnh else 5)
+    out = capsys.readouterr().out
+    assert out.count("n_components = 2 ***") == len(done) and out.count("*** Converged at iteration 24 ***") == 1
+    assert out.index("iteration 24") < out.rindex("iteration 8 ***")           # restart 3 before restart 4
+    assert ("-" * (100 if gpnh else 80) + "\n") in out and ("-" * 101) not in out
+
+    # errors: every slot is served, then the lowest restart's error is raised
+    models = [make() for _ in range(3)]
+    starts = [_playback_start(1), _playback_start(2, flags=0 if gpnh else _backend.SPG_FLAG_MAX_ITER, stage=2),
+              _playback_start(1, stage=1)]
+    _PlaybackContext.log = log = []
+    with warnings.catch_warnings(record=True) as caught:
+        warnings.simplefilter("always")
+        with pytest.raises(RuntimeError, match="cost increased after weights update"):
+            fit(models, starts, np.zeros((3, 4)), None, n_slots=2)
+    assert log[-2:] == ["end", "close"] and sum(e[0] == "fetch" for e in log) == 1
+    assert len(caught) == (0 if gpnh else 1)
+    capsys.readouterr()
+
+
 def test_bench_rows_do_not_depend_on_threads_or_shards():
     """bench.synthetic_rows draws its blocks on worker threads: the matrix is bit for bit the
     serial block-by-block definition, whatever the thread count and the shard bounds."""

@@ -919,6 +919,65 @@ def test_gpnh_slot_with_singular_normal_equations_goes_to_the_sequential_path(cd
         assert np.array_equal(models[i].dictionary, seq[i].dictionary)
 
 
+def test_slot_modes_follow_each_other_on_one_context(cdr, orc):
+    """A begin call of either slot mode resets whatever an earlier, un-ended one left: on ONE context an
+    AA slot run that is never ended, a GPNH slot run after it, aa_slots_end and then a plain single AA
+    fit each give, bit for bit, what the same calls give on a fresh context of their own."""
+    from convex_dim_red import _backend
+    from convex_dim_red.archetypal_analysis import _DEVICE_LOOP_BATCH
+    rng = np.random.RandomState(7)
+    n, p, k, R, iters = 300, 40, 4, 2, 6
+    X = orc.right_stochastic_matrix((n, k), rng).dot(rng.standard_normal((k, p))) + 0.1 * rng.standard_normal((n, p))
+    aa_starts = [(orc.right_stochastic_matrix((k, n), rng), orc.right_stochastic_matrix((n, k), rng))
+                 for _ in range(R)]
+    gpnh_starts = [(rng.standard_normal((p, k)), orc.right_stochastic_matrix((n, k), rng)) for _ in range(R)]
+    C1, Z1 = orc.right_stochastic_matrix((k, n), rng), orc.right_stochastic_matrix((n, k), rng)
+
+    def aa_slots(ctx):                                # left un-ended
+        ctx.aa_slots_begin(R, k, iters, 0.0, "abs_delta_f", False, dict(max_iterations=1), {})
+        for r, (C0, Z0) in enumerate(aa_starts):
+            ctx.aa_slots_load(r, C0, Z0)
+        out = []
+        for r, st in enumerate(ctx.aa_slots_run(iters)):
+            assert st.stop and not st.error_stage
+            carried = (st.stop_iter + 1) % _DEVICE_LOOP_BATCH == 0 or st.stop_iter + 1 == iters   # restarts.py's rule
+            out.extend(ctx.aa_slots_fetch(r, st.stop_iter, carried))
+        return out
+
+    def gpnh_slots(ctx):
+        ctx.gpnh_slots_begin(R, k, 0.5, iters, 0.0, "abs_delta_f", False, dict(max_iterations=1))
+        for r, (W0, Z0) in enumerate(gpnh_starts):
+            ctx.gpnh_slots_load(r, W0, Z0)
+        out = []
+        for r, st in enumerate(ctx.gpnh_slots_run(iters)):
+            assert st.stop and not st.error_stage
+            out.extend(ctx.gpnh_slots_fetch(r, st.stop_iter))
+        return out
+
+    def single_fit(ctx):
+        ctx.set_state(C1, Z1, np.ones(k))
+        cost0 = ctx.prepare()
+        costs, st = ctx.iterate(cost0, iters, 0.0, "abs_delta_f", False, True, True, dict(max_iterations=1), {})
+        assert not st.error_stage
+        return [cost0, costs, st.n_iter, ctx.archetypes()] + list(ctx.get_state())
+
+    legs = (aa_slots, gpnh_slots, single_fit)
+    want = []
+    for leg in legs:
+        with _backend.Context(dtype="float64") as ctx:
+            ctx.set_data(X)
+            want.append(leg(ctx))
+    with _backend.Context(dtype="float64") as ctx:
+        ctx.set_data(X)
+        got = [aa_slots(ctx), gpnh_slots(ctx)]
+        ctx.aa_slots_end()
+        got.append(single_fit(ctx))
+    for leg, a, b in zip(legs, got, want):
+        assert len(a) == len(b) and len(a) >= 4
+        for j, (x, y) in enumerate(zip(a, b)):
+            assert np.array_equal(x, y), "%s: output %d differs from the fresh context's" % (leg.__name__, j)
+
+
 def test_fit_restarts_over_two_devices(cdr, orc):
     """fit_restarts(devices=[0, 1]): the workers are dealt over two GPUs, one resident copy of the
     data per device; restart by restart the same costs and factors as on one device.  Skipped on a
