@@ -546,6 +546,14 @@ int aa_gemm_timing(aa_ctx *ctx, int enable, double *ms_reduce_rows, int *n_reduc
  * (tests/test_gpu_headline.py).  The reference has no counterpart (NumPy picks its BLAS kernels
  * silently).  Empty names before the first pass.  Returns AA_ERR_ARG if `len` is too small. */
 int aa_pass_kernels(aa_ctx *ctx, char *buf, int len);
+/* Column simplex projections the context has launched since it was created, by the strategy the
+ * launcher picked for each (csrc/kernels_tall.hip: launch_proj): out[0] one kernel with 32 entries
+ * per thread (n <= 8192), out[1] the same with 64 (option proj_small = 2, n <= 16 384), out[2]
+ * candidate lists, out[3] iterative full passes (option proj_mode = 1, and the multi-rank fallback
+ * counts as the list projection it belongs to).  Host-side counters: reading them launches nothing
+ * and they steer nothing.  A test of one strategy has to know that it ran that strategy
+ * (tests/test_gpu_projection.py).  The reference has no counterpart (one sorted projection). */
+int aa_proj_counts(aa_ctx *ctx, long out[4]);
 
 #ifdef __cplusplus
 }

@@ -171,6 +171,7 @@ _SIGNATURES = {
     "aa_gemm_timing": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_int), _dp,
                                       ctypes.POINTER(ctypes.c_int)]),
     "aa_pass_kernels": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
+    "aa_proj_counts": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
@@ -866,6 +867,13 @@ class Context(object):
         buf = ctypes.create_string_buffer(128)
         _check(self.lib.aa_pass_kernels(self.h, buf, 128))
         return tuple(buf.value.decode().split(";"))
+
+    def proj_counts(self):
+        """Column simplex projections this context has launched so far, by strategy:
+        ``{"small32", "small64", "list", "iterative"}`` (aa_proj_counts)."""
+        out = (ctypes.c_long * 4)()
+        _check(self.lib.aa_proj_counts(self.h, out))
+        return dict(zip(("small32", "small64", "list", "iterative"), (int(v) for v in out)))
 
     def time_kernel(self, which, reps):
         ms = ctypes.c_double(0)

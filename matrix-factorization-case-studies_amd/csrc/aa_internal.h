@@ -274,6 +274,7 @@ struct Ctx {
     int tallBlocks = 0;                        // blocks of the tall reductions
     int projPassHint[4] = {0, 0, 0, 0};        // Michelot passes the last projection of each kind needed
     bool projWarm[4] = {false, false, false, false};   // ProjState::warm[kind] is valid
+    long projCounts[4] = {0, 0, 0, 0};         // launch_proj calls by strategy: small32, small64, list, iterative (aa_proj_counts)
     bool projListShort[4] = {false, false, false, false};   // multi-rank: gathered lists of this kind were <= a quarter of the solver's capacity at the last poll
     bool x_feasible = false;                   // dictionary known to be on the simplex
     bool products_valid = false;               // P (= CX) and Gr (= C XX' or C K) match Ct

@@ -2341,6 +2341,7 @@ int launch_proj(Ctx *c, const double *x, const double *g, double a_const, int a_
     // outer iteration with it against 0.533 with the four list launches -- 32 blocks walking 12 500 strided
     // entries each are slower than 256 blocks streaming them -- so the default stays at 8192 rows; option proj_small=2)
     if (g_proj_mode == 0 && !multi && g_proj_small && c->n <= (g_proj_small >= 2 ? 256L * 64 : 256L * 32)) {
+        c->projCounts[c->n <= 256L * 32 ? 0 : 1] += 1;
         if (c->n <= 256L * 32)
             hipLaunchKernelGGL(k_proj_small<32>, dim3(c->k), dim3(256), 0, c->stream, x, g, a_const, (const double *)scal,
                                a_slot, c->n, c->KP, c->projWarm[mode] ? mode : 0, ps, c->slots_aa ? c->slots_k : 0);
@@ -2350,6 +2351,7 @@ int launch_proj(Ctx *c, const double *x, const double *g, double a_const, int a_
     } else if (g_proj_mode == 0) {
         const int RS = 256 / c->KP;
         const long nseg = (long)c->tallBlocks * RS, segcap = rpb / RS;
+        c->projCounts[2] += 1;
         FinTail ft1;
         memset(&ft1, 0, sizeof(ft1));
         if (fin_in_last) {
@@ -2407,6 +2409,7 @@ int launch_proj(Ctx *c, const double *x, const double *g, double a_const, int a_
         }
         AA_CHECK_HIP(hipGetLastError());
     } else {
+        c->projCounts[3] += 1;
         TALL_DISPATCH(k_proj_colmax, x, g, a_const, (const double *)scal, a_slot, c->n, rpb, c->k, wbuf, part);
         AA_CHECK(finalize_and_post(c, 1, 1u, POST_COLMAX, 0, c->projWarm[mode] ? mode : 0, false));
         AA_CHECK(proj_iterative_passes(c, wsrc, mode, rpb,

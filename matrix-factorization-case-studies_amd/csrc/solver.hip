@@ -2334,6 +2334,13 @@ int aa_pass_kernels(aa_ctx *h, char *buf, int len)
     return AA_OK;
 }
 
+int aa_proj_counts(aa_ctx *h, long *out)
+{
+    AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
+    for (int i = 0; i < 4; ++i) out[i] = h->c.projCounts[i];
+    return AA_OK;
+}
+
 int aa_gemm_timing(aa_ctx *h, int enable, double *ms_reduce_rows, int *n_reduce_rows,
                    double *ms_row_local, int *n_row_local)
 {

@@ -1067,10 +1067,11 @@ def test_gemm_timing_counts_launches(cdr, orc):
 
 def test_qp_sample_order_does_not_change_results(cdr, orc):
     """The lane kernel takes the samples longest-first by their pass counts in the previous
-    weights update; samples are independent, so the order cannot change a single bit."""
+    weights update; samples are independent, so the order cannot change a single bit.  launch_qp
+    orders only above 4096 samples, so n lies above that: at n = 2300 both legs ran unordered."""
     from convex_dim_red import _backend
     rng = np.random.RandomState(31)
-    n, p, k = 2300, 180, 11
+    n, p, k = 4200, 180, 11
     X = rng.standard_normal((n, p)).astype(np.float32)
     C = orc.right_stochastic_matrix((k, n), rng)
     Z = orc.right_stochastic_matrix((n, k), rng)
