@@ -141,7 +141,8 @@ int aa_device_count(int *count);
  *                               pass counts in the previous weights update, longest first
  *   "qp_overlap_tail"   0|1    1: the wave-per-sample kernel of the stragglers runs on a side
  *                               stream while Z'X is accumulated (float32 data); the rows it
- *                               changes enter Z'X as a rank-m correction.  Default 0: measured
+ *                               changes enter Z'X as a rank-m correction; the weights carry the
+ *                               bits of the serial order.  Default 0: measured
  *                               neutral, the stragglers run 2x slower next to the GEMM
  *   "qp_live"           0|1    1: the four-lane kernel hands parked samples to a consumer launch of the
  *                               wave-per-sample kernel that is resident beside it on CUs of its own
@@ -554,6 +555,19 @@ int aa_pass_kernels(aa_ctx *ctx, char *buf, int len);
  * and they steer nothing.  A test of one strategy has to know that it ran that strategy
  * (tests/test_gpu_projection.py).  The reference has no counterpart (one sorted projection). */
 int aa_proj_counts(aa_ctx *ctx, long out[4]);
+/* The kernels the most recent per-sample QP of a context was launched with (csrc/kernels_qp.hip:
+ * launch_qp), in launch order and separated by ';': the first-phase kernel with its template
+ * arguments and the pass cap it ran with, then every continuation launch of the wave-per-sample
+ * kernel, with ":park=N" where it parks samples beyond N passes for a later stage.  Examples:
+ * "k_qp_quad_w3<2,1,0>:cap=24;k_qp_wave<32,1,1>", "k_qp<8,0>:cap=1;k_qp_wave<32,1,1>",
+ * "k_qp_quad_w3<1,1,0>:cap=24;k_qp_wave_ord<1>:park=96;k_qp_wave<32,1,1>", "k_qp_row<2>",
+ * "k_qp_wave<64,0,1>", "k_qp_project_only<16>".  (A first phase whose cap is max_iterations has
+ * no continuation.)  `ctx` NULL: the scratch context that aa_quad_simplex_spg_batch keeps for
+ * `device`, which the stateless entry hides.  Empty before the first QP.  A host-side string:
+ * reading it launches nothing and it steers nothing.  A test of one mapping has to know that it
+ * ran that mapping (tests/test_gpu_qp_kernels.py).  The restart-slot launches are not recorded.
+ * Returns AA_ERR_ARG if `len` is too small. */
+int aa_qp_kernels(aa_ctx *ctx, int device, char *buf, int len);
 
 #ifdef __cplusplus
 }

@@ -172,6 +172,7 @@ _SIGNATURES = {
                                       ctypes.POINTER(ctypes.c_int)]),
     "aa_pass_kernels": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "aa_proj_counts": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
+    "aa_qp_kernels": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
@@ -366,6 +367,14 @@ def qp_batch(A, B, Z0, layout, return_iters=False, **kw):
         device_index(), _ptr(A), _ptr(B), sj, st, _ptr(Z0), _ptr(Z), n, k, ctypes.byref(p),
         iters.ctypes.data_as(_ip)))
     return (Z, iters) if return_iters else Z
+
+
+def qp_kernels(ctx=None):
+    """What the last per-sample QP launched, e.g. ``"k_qp_quad_w3<2,1,0>:cap=24;k_qp_wave<32,1,1>"``
+    (aa_qp_kernels): of ``ctx``, or of the scratch context behind ``qp_batch`` on this device."""
+    buf = ctypes.create_string_buffer(256)
+    _check(load_library().aa_qp_kernels(None if ctx is None else ctx.h, device_index(), buf, 256))
+    return buf.value.decode()
 
 
 # ---------------------------------------------------------------- resident solver
@@ -867,6 +876,10 @@ class Context(object):
         buf = ctypes.create_string_buffer(128)
         _check(self.lib.aa_pass_kernels(self.h, buf, 128))
         return tuple(buf.value.decode().split(";"))
+
+    def qp_kernels(self):
+        """The kernels of the last weights QP of this context (see the module's ``qp_kernels``)."""
+        return qp_kernels(self)
 
     def proj_counts(self):
         """Column simplex projections this context has launched so far, by strategy:

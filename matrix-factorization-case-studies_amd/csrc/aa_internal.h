@@ -173,6 +173,7 @@ struct Ctx {
     long qp_live_cap = 0;
     int qp_live_epoch = 0;
     char pass_names[2][48] = {{0}, {0}};       // last reduce-over-rows / row-local kernel launched (aa_pass_kernels)
+    char qp_names[192] = {0};                  // what the last launch_qp launched, ';'-separated (aa_qp_kernels)
     bool qp_tail_pending = false;              // stragglers run on stream2, results in tmpTall by slot
     // the residual projection of the dictionary SPG (spg.py:250-276: convergence flags only) runs on
     // the side stream beside the weights QP, on its own scratch set (launch_proj_side / join_side)

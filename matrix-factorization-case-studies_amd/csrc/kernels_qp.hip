@@ -838,9 +838,13 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
                                                  int *__restrict__ park_rows = nullptr,
                                                  QpCarry *__restrict__ park = nullptr,
                                                  QpLive lv = QpLive{0, 0, 0u, 0u, nullptr, nullptr},
-                                                 int rst_b = 0, long rst_n = 0, unsigned int blk0 = 0u)
+                                                 int rst_b = 0, long rst_n = 0, unsigned int blk0 = 0u,
+                                                 double *__restrict__ park_g = nullptr /*[parked slot][KQ]*/)
 {
     // blk0: the first blk0 blocks of the grid do something else (k_qp_wave_ord)
+    // park_g: the gradient of a parked sample travels with it (the two stages of the deferred tail: the
+    // launch that takes the second list reads it from its zslot rows, which it fills only at the end), so
+    // that parking a sample does not change a bit of it -- a hand-over without it forms g = A x + b afresh
     if (gridDim.y > 1) {                               // restarts side by side: blockIdx.y = slot
         const int rst = blockIdx.y;
         A += (long)rst * KQ * KQ;
@@ -937,7 +941,10 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
             x = live ? fmax(x - t0, 0.0) : 0.0;
             support_r = support;
         }
-        double g = matvec(x) + b;
+        const bool carried_g = !fresh && zslot && count_ptr;     // second stage: slot = the slot it was parked in
+        double g;
+        if (carried_g) g = live ? zslot[(size_t)slot * KQ + comp] : 0.0;
+        else g = matvec(x) + b;
         if (fresh) {
             double xg, xb;
             qw_sum2<HALF>(x * g, x * b, lane, xg, xb);
@@ -1058,8 +1065,9 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
             else Z[row * ldz + comp] = x;
         }
         if (parked) {
+            unsigned int s2 = 0u;
             if (lane == 0) {
-                const unsigned int s2 = atomicAdd(n_parked, 1u);
+                s2 = atomicAdd(n_parked, 1u);
                 park_rows[s2] = (int)row;
                 QpCarry cr;
                 cr.alpha = alpha;
@@ -1067,6 +1075,10 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
                 cr.n_iter = n_iter;
                 cr.n_feval = n_feval;
                 park[s2] = cr;
+            }
+            if (park_g) {
+                s2 = (unsigned int)__builtin_amdgcn_readfirstlane((int)s2);
+                if (live && lane == comp) park_g[(size_t)s2 * KQ + comp] = g;
             }
             continue;
         }
@@ -1088,9 +1100,10 @@ __device__ __forceinline__ void qp_wave_body(const double *__restrict__ A /*[KQ]
                 const unsigned int *__restrict__ count_ptr = nullptr,                                               \
                 int park_at = 1 << 30, unsigned int *__restrict__ n_parked = nullptr,                               \
                 int *__restrict__ park_rows = nullptr, QpCarry *__restrict__ park = nullptr,                        \
-                QpLive lv = QpLive{0, 0, 0u, 0u, nullptr, nullptr}, int rst_b = 0, long rst_n = 0
+                QpLive lv = QpLive{0, 0, 0u, 0u, nullptr, nullptr}, int rst_b = 0, long rst_n = 0,                  \
+                double *__restrict__ park_g = nullptr
 #define QW_PASS A, B, stride_j, stride_t, bscale, Z, ldz, n_fresh, k, p, iters, hdr, ovf_rows, ovf, zslot,           \
-                count_ptr, park_at, n_parked, park_rows, park, lv, rst_b, rst_n
+                count_ptr, park_at, n_parked, park_rows, park, lv, rst_b, rst_n, 0u, park_g
 template <int KQ, bool MEM1 = false, bool LAZY = true>
 __global__ __launch_bounds__(256) void k_qp_wave(QW_ARGS) { qp_wave_body<KQ, MEM1, LAZY>(QW_PASS); }
 // the live consumers (QpLive mode 1): blocks of 16 waves that are launched with a whole CU's LDS
@@ -2134,7 +2147,8 @@ __global__ __launch_bounds__(256) void k_qp_wave_ord(QpOrder od, const double *_
                                                      const QpCarry *__restrict__ ovf, int park_at = 1 << 30,
                                                      unsigned int *__restrict__ n_parked = nullptr,
                                                      int *__restrict__ park_rows = nullptr,
-                                                     QpCarry *__restrict__ park = nullptr)
+                                                     QpCarry *__restrict__ park = nullptr,
+                                                     double *__restrict__ park_g = nullptr)
 {
     if ((int)blockIdx.x < od.blocks) {
         qp_order_block(od);
@@ -2143,7 +2157,7 @@ __global__ __launch_bounds__(256) void k_qp_wave_ord(QpOrder od, const double *_
     qp_wave_body<32, true, LAZY>(A, B, stride_j, stride_t, bscale, Z, ldz, (long)-1, k, p, iters, hdr, ovf_rows, ovf,
                                  (double *)nullptr, (const unsigned int *)nullptr, park_at,
                                  n_parked, park_rows, park,
-                                 QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, (unsigned int)od.blocks);
+                                 QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, (unsigned int)od.blocks, park_g);
 }
 
 // The set-up kernels' shared pieces (k_qp_setup, k_qp_setup_slots, k_qp_setup_slots_aa).  One thread: the
@@ -2325,6 +2339,21 @@ int launch_qp_slots_aa(Ctx *c, const aa_qp_params *p)
     return AA_OK;
 }
 
+// What launch_qp launched, in launch order and separated by ';' (aa_qp_kernels): a host-side string,
+// written beside the launches and read by nothing that launches.
+static void qp_name(Ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+static void qp_name(Ctx *c, const char *fmt, ...)
+{
+    const size_t at = strlen(c->qp_names);
+    if (at + 2 >= sizeof(c->qp_names)) return;
+    if (at) strcat(c->qp_names, ";");
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c->qp_names + strlen(c->qp_names), sizeof(c->qp_names) - strlen(c->qp_names), fmt, ap);
+    va_end(ap);
+}
+#define QP_NAME(...) qp_name(c, __VA_ARGS__)
+
 int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, long stride_t,
               const double *bscale_host, double *Ztall, int ldz, long n, int k,
               const aa_qp_params *p, int *iters_dev, aa_qp_stats *stats, const double *gram_dev,
@@ -2334,6 +2363,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
     while (KQ < k) KQ *= 2;
     AA_REQUIRE(KQ <= 64, AA_ERR_ARG, "QP: k = %d > 64 unsupported", k);
     AA_REQUIRE(n < (1L << 31), AA_ERR_ARG, "QP: too many samples");
+    c->qp_names[0] = 0;
     // default (qp_mode 0), k <= 32: four lanes per sample in the matrix-core operand layout
     // (k_qp_quad) followed by the wave-per-sample kernel for the samples that reach its pass cap --
     // ahead of the other mappings at every size measured (1 600 .. 100 000 samples per GPU:
@@ -2430,6 +2460,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         switch (KQ) { case 4: QPP(4); break; case 8: QPP(8); break; case 16: QPP(16); break;
                       case 32: QPP(32); break; default: QPP(64); break; }
 #undef QPP
+        QP_NAME("k_qp_project_only<%d>", KQ);
     } else if (row_mode) {
         // samples ordered by their previous pass count, longest first (iters_dev still holds the
         // counts of the previous update of this context); every sample runs to completion
@@ -2443,6 +2474,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         else
             hipLaunchKernelGGL(k_qp_row<2>, dim3((unsigned)waves), dim3(64), 0, c->stream, A2d, KW, Btall,
                                stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm);
+        QP_NAME("k_qp_row<%d>", k <= 16 ? 1 : 2);
     } else if (quad_mode) {
         int cap = g_qp_quad_cap > 0 ? g_qp_quad_cap : (n >= 65536 ? 32 : 24);
         if (p->memory > 1 || p->max_iterations <= cap) cap = p->max_iterations;
@@ -2490,6 +2522,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                                (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
                                (const unsigned int *)nullptr, 1 << 30,
                                (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
+            QP_NAME("k_qp_wave_live");
             AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream3));
         }
         // (the ordering kernels run while the cross-stream dependency of the consumers resolves: the
@@ -2509,6 +2542,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         else         { if (p->memory <= 1) QQL(2, true); else QQL(2, false); }
 #undef QQL
 #undef QQK
+        QP_NAME("k_qp_quad_w3<%d,%d,%d>:cap=%d", k <= 16 ? 1 : 2, p->memory <= 1, g_qp_quad_lazy && !live, cap);
         if (live) {
             // clean-up: whatever the consumers did not take (they give up after a bounded wait)
             AA_CHECK_HIP(hipStreamWaitEvent(c->stream, c->evJoin, 0));
@@ -2518,6 +2552,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                                (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
                                (const unsigned int *)nullptr, 1 << 30,
                                (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
+            QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
         } else if (cap < p->max_iterations) {
             // the parked samples, one wave each.  defer_tail: on the side stream, results to
             // tmpTall by slot; the caller's Z'X pass runs beside them on the weights as k_qp_quad
@@ -2535,18 +2570,24 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                     if (g_qp_wave_lazy)
                         hipLaunchKernelGGL(k_qp_wave_ord<true>, og, dim3(256), 0, c->stream, od, A2d, Btall, stride_j,
                                            stride_t, bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2);
+                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2,
+                                           c->tmpTall.as<double>());
                     else
                         hipLaunchKernelGGL(k_qp_wave_ord<false>, og, dim3(256), 0, c->stream, od, A2d, Btall, stride_j,
                                            stride_t, bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2);
+                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2,
+                                           c->tmpTall.as<double>());
                     c->qp_perm_ready = true;
                     c->qp_perm_n = n;
-                } else
+                    QP_NAME("k_qp_wave_ord<%d>:park=%d", g_qp_wave_lazy != 0, tail_cap);
+                } else {
                 QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, c->stream, A2d, Btall,
                                    stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                                   (const unsigned int *)nullptr, tail_cap, &hdr->pad, ovf2_rows, ovf2);
+                                   (const unsigned int *)nullptr, tail_cap, &hdr->pad, ovf2_rows, ovf2,
+                                   QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, c->tmpTall.as<double>());
+                QP_NAME("k_qp_wave<32,1,%d>:park=%d", g_qp_wave_lazy != 0, tail_cap);
+                }
                 // the handful beyond tail_cap on the side stream.  (Tried: a CU-masked stream pair,
                 // hipExtStreamCreateWithCUMask -- 8 or 16 CUs for these chains alone, the rest of the chip for
                 // the caller's pass, so that the two share no SIMD.  With masked queues alive EVERY launch of the
@@ -2559,6 +2600,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                                    stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf2_rows, (const QpCarry *)ovf2, c->tmpTall.as<double>(),
                                    (const unsigned int *)&hdr->pad);
+                QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
                 AA_CHECK_HIP(hipEventRecord(c->evJoin, ss));
                 c->qp_tail_pending = true;
                 c->qp_tail_rows = ovf2_rows;
@@ -2587,10 +2629,13 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                                            (QpCarry *)nullptr);
                     c->qp_perm_ready = true;
                     c->qp_perm_n = n;
-                } else
+                    QP_NAME("k_qp_wave_ord<%d>", g_qp_wave_lazy != 0);
+                } else {
                 QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
                                    stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                    (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
+                QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
+                }
                 if (defer) {
                     AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
                     c->qp_tail_pending = true;
@@ -2609,6 +2654,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         if (KW == 64) { if (p->memory <= 1) QWF(64, true); else QWF(64, false); }
         else          { if (p->memory <= 1) QWF(32, true); else QWF(32, false); }
 #undef QWF
+        QP_NAME("k_qp_wave<%d,%d,1>", KW, p->memory <= 1);
     } else {
         // phase 1: every sample gets up to pass_cap passes in a lane
         int cap = qp_pass_cap();
@@ -2630,6 +2676,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                       default: QPL(32); break; }
 #undef QPL2
 #undef QPL
+        QP_NAME("k_qp<%d,%d>:cap=%d", KQ > 32 ? 32 : KQ, k == KQ, cap);
         if (cap < p->max_iterations) {
             // phase 2: the stragglers, one wave each (grid is fixed; the count is read on
             // the device, so no host synchronisation between the phases)
@@ -2647,6 +2694,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
             QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
                                stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
                                (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
+            QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
             if (defer) {
                 AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
                 c->qp_tail_pending = true;

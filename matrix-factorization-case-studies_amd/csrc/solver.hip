@@ -2209,6 +2209,10 @@ int aa_simplex_project_rows(int device, const double *in, double *out, long rows
     return rc;
 }
 
+// the scratch contexts of the stateless QP entry, one per device (aa_quad_simplex_spg_batch, aa_qp_kernels)
+static aa_ctx *g_qp_scratch[64] = {nullptr};
+static std::mutex g_qp_scratch_mu;
+
 int aa_quad_simplex_spg_batch(int device, const double *A, const double *B, long stride_j, long stride_t,
                               const double *Z0, double *Zout, long n, int k, const aa_qp_params *params,
                               int *iters)
@@ -2222,12 +2226,10 @@ int aa_quad_simplex_spg_batch(int device, const double *A, const double *B, long
     // cost 8 ms -- more than the QPs of every unit-test-sized problem
     // (ctypes releases the GIL: calls from several threads take turns on the scratch context; it
     // is never destroyed -- HIP may already be gone when static destructors run)
-    static aa_ctx *scratch[64] = {nullptr};
-    static std::mutex scratch_mu;
     AA_REQUIRE(device >= 0 && device < 64, AA_ERR_ARG, "device %d out of range", device);
-    std::lock_guard<std::mutex> hold(scratch_mu);
-    if (!scratch[device]) AA_CHECK(aa_ctx_create(&scratch[device], device, AA_F64));
-    aa_ctx *h = scratch[device];
+    std::lock_guard<std::mutex> hold(g_qp_scratch_mu);
+    if (!g_qp_scratch[device]) AA_CHECK(aa_ctx_create(&g_qp_scratch[device], device, AA_F64));
+    aa_ctx *h = g_qp_scratch[device];
     AA_CHECK_HIP(hipSetDevice(device));
     Ctx *c = &h->c;
     c->qp_iters_valid = false;
@@ -2331,6 +2333,19 @@ int aa_pass_kernels(aa_ctx *h, char *buf, int len)
     const int need = snprintf(nullptr, 0, "%s;%s", c->pass_names[0], c->pass_names[1]) + 1;
     AA_REQUIRE(len >= need, AA_ERR_ARG, "aa_pass_kernels: buffer of %d bytes, %d needed", len, need);
     snprintf(buf, (size_t)len, "%s;%s", c->pass_names[0], c->pass_names[1]);
+    return AA_OK;
+}
+
+int aa_qp_kernels(aa_ctx *h, int device, char *buf, int len)
+{
+    AA_REQUIRE(buf && len > 0, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(h || (device >= 0 && device < 64), AA_ERR_ARG, "device %d out of range", device);
+    std::lock_guard<std::mutex> hold(g_qp_scratch_mu);
+    if (!h) h = g_qp_scratch[device];
+    const char *names = h ? h->c.qp_names : "";
+    AA_REQUIRE((size_t)len > strlen(names), AA_ERR_ARG, "aa_qp_kernels: buffer of %d bytes, %zu needed", len,
+               strlen(names) + 1);
+    strcpy(buf, names);
     return AA_OK;
 }
 
