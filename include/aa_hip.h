@@ -278,6 +278,24 @@ int aa_share_data(aa_ctx *ctx, const aa_ctx *owner);
  * kernel.  Unlike aa_share_data the copy owns its memory: the owner may be destroyed afterwards. */
 int aa_set_data_rows(aa_ctx *ctx, const aa_ctx *owner, long row0, long n);
 
+/* Column statistics and standardisation of resident data (the --standardize step of
+ * bin/run_jra55_pca_aa.py:165-166 / bin/run_jra55_pca_gpnh.py:162-163,
+ * `valid_data / np.std(valid_data, axis=0, keepdims=True)`, without a round trip through the host).
+ *
+ * aa_data_column_moments: mean[j] = sum_r X[r][j] / n and var[j] = sum_r (X[r][j] - mean[j])^2 / n (ddof 0,
+ *   as np.var) of the n resident rows, p values each, either output may be NULL.  Two sweeps over the matrix
+ *   (csrc/kernels_tall.hip: k_col_moment_sweep), float64 arithmetic in both context dtypes (elements converted
+ *   on load), row-slab partials combined in a fixed order: two calls return the same bits.  Data form with a
+ *   stored matrix (AA_ERR_STATE otherwise), single rank.
+ * aa_set_data_rows_affine: aa_set_data_rows with Y[r][j] = (X[row0 + r][j] - shift[j]) / scale[j]: float64
+ *   subtraction and a true float64 division, rounded once to the context's element type.  shift / scale: host
+ *   arrays of owner's p values; NULL: 0 / 1.  A scale[j] that is zero or not finite, or a shift[j] that is not
+ *   finite, is refused with AA_ERR_ARG before ctx is touched (it keeps the data it had).  Otherwise the
+ *   preconditions, refusals and effects on ctx of aa_set_data_rows. */
+int aa_data_column_moments(aa_ctx *ctx, double *mean, double *var);
+int aa_set_data_rows_affine(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, const double *shift,
+                            const double *scale);
+
 /* KernelAA on the implicit linear kernel K = X X' (SURVEY 8(f4)): with `on` != 0 the resident
  * DATA matrix X (n x p) stands in for the n x n kernel matrix of _iterate_kernel_aa
  * (archetypal_analysis.py:399-531), which is never formed: every product with K runs as two

@@ -115,6 +115,8 @@ _SIGNATURES = {
     "aa_set_rbf_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double]),
     "aa_share_data": (ctypes.c_int, [_vp, _vp]),
     "aa_set_data_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long]),
+    "aa_set_data_rows_affine": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _dp, _dp]),
+    "aa_data_column_moments": (ctypes.c_int, [_vp, _dp, _dp]),
     "aa_set_data_weighted": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                             _dp, ctypes.c_long, ctypes.c_long,
                                             ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_long)]),
@@ -493,6 +495,32 @@ class Context(object):
         _check(self.lib.aa_set_data_rows(self.h, owner.h, int(row0), int(n)))
         self.n, self.p = int(n), owner.p
         self.row_lo, self.n_global = 0, int(n)
+
+    def set_data_rows_affine(self, owner, row0, n, shift=None, scale=None):
+        """``(owner[row0:row0 + n] - shift) / scale`` becomes this context's data matrix
+        (aa_set_data_rows_affine): float64 arithmetic, one rounding to the context's dtype.  ``shift`` /
+        ``scale``: None (0 / 1) or one value per column of ``owner``."""
+        def column_values(a, name):
+            if a is None:
+                return None
+            a = _c64(a)
+            if a.shape != (owner.p,):
+                raise ValueError("%s: %d values expected, one per column; got shape %r" % (name, owner.p, a.shape))
+            return a
+        shift, scale = column_values(shift, "shift"), column_values(scale, "scale")
+        _check(self.lib.aa_set_data_rows_affine(self.h, owner.h, int(row0), int(n),
+                                                None if shift is None else _ptr(shift),
+                                                None if scale is None else _ptr(scale)))
+        self.n, self.p = int(n), owner.p
+        self.row_lo, self.n_global = 0, int(n)
+
+    def data_column_moments(self, mean=True, var=True):
+        """``(mean[p], var[p])`` of the columns of the resident data matrix (aa_data_column_moments): two
+        float64 sweeps, ``var`` the mean squared deviation (ddof 0); an output that is not asked for is None."""
+        m = np.empty(self.p) if mean else None
+        v = np.empty(self.p) if var else None
+        _check(self.lib.aa_data_column_moments(self.h, None if m is None else _ptr(m), None if v is None else _ptr(v)))
+        return m, v
 
     def set_rbf_features(self, X, gamma):
         """The implicit RBF kernel exp(-gamma ||x_i - x_j||^2) of the rows of X as this context's kernel

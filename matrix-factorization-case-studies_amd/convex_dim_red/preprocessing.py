@@ -10,9 +10,40 @@ driver, which passes ``da.values`` (sample dimension first) and the weights it c
 """
 from __future__ import absolute_import, division
 
+from collections import namedtuple
+
 import numpy as np
 
 from . import _backend
+
+# Column statistics of a resident block: float64 arrays of length n_features (``std`` = sqrt of the mean squared
+# deviation, ddof 0, as ``np.std``) and the number of rows they were taken over.
+ColumnStats = namedtuple("ColumnStats", ("mean", "std", "n_samples"))
+# What ``DeviceData.standardized`` applied: the ``ColumnStats`` it divided by (and subtracted, if ``center``).
+ColumnScaling = namedtuple("ColumnScaling", ("stats", "center"))
+
+
+def _checked_stats(stats, n_features, center):
+    """(shift or None, scale) of a standardisation, or ValueError: decided on the host, from ``stats`` alone."""
+    std = None if stats.std is None else np.asarray(stats.std, dtype=np.float64)
+    if std is None or std.shape != (n_features,):
+        raise ValueError("DeviceData.standardized: stats.std must hold one value per feature (%d); got %s"
+                         % (n_features, "None" if std is None else "shape %r" % (std.shape,)))
+    bad = np.flatnonzero(~np.isfinite(std) | (std == 0))
+    if bad.size:
+        raise ValueError("DeviceData.standardized: %d column(s) have a zero or non-finite std (the first is column "
+                         "%d); the reference's division would fill them with inf / NaN" % (bad.size, bad[0]))
+    if not center:
+        return None, std
+    if stats.mean is None:
+        raise ValueError("DeviceData.standardized: center=True needs stats with a mean")
+    mean = np.asarray(stats.mean, dtype=np.float64)
+    if mean.shape != (n_features,):
+        raise ValueError("DeviceData.standardized: stats.mean must hold one value per feature (%d); got shape %r"
+                         % (n_features, mean.shape))
+    if not np.all(np.isfinite(mean)):
+        raise ValueError("DeviceData.standardized: stats.mean has non-finite entries")
+    return mean, std
 
 
 class DeviceData(object):
@@ -21,18 +52,21 @@ class DeviceData(object):
     ``shape``  -- (n_samples, n_valid_features) of the block it holds;
     ``valid``  -- boolean mask over the flattened features (True: kept), what the drivers use to
                   put archetypes back on the grid;
-    ``to_host()`` -- the matrix as float64 NumPy (downloaded once, then cached).
+    ``to_host()`` -- the matrix as float64 NumPy (downloaded once, then cached);
+    ``scaling``  -- None, or the ``ColumnScaling`` a block made by ``standardized()`` was scaled with.
 
     Pass it as ``data`` to ``ArchetypalAnalysis.fit_transform / transform`` or
     ``GPNHConvexCoding.fit_transform``; ``close()`` (or ``with``) frees the device copy."""
 
-    def __init__(self, ctx, shape, valid, original_shape):
+    def __init__(self, ctx, shape, valid, original_shape, scaling=None):
         self._ctx = ctx
         self.shape = shape
         self.valid = valid
         self.original_shape = original_shape
+        self.scaling = scaling
         self.ndim = 2
         self._host = None
+        self._stats = None
 
     @property
     def dtype(self):
@@ -71,7 +105,56 @@ class DeviceData(object):
         except Exception:
             ctx.close()
             raise
-        return DeviceData(ctx, (hi - lo, self.shape[1]), self.valid, self.original_shape)
+        return DeviceData(ctx, (hi - lo, self.shape[1]), self.valid, self.original_shape, self.scaling)
+
+    def column_stats(self):
+        """``ColumnStats(mean, std, n_samples)`` of the block's columns, from two float64 sweeps over the
+        resident matrix (aa_data_column_moments); computed once (a ``DeviceData`` never changes)."""
+        if self._stats is None:
+            if self._ctx is None or not self._ctx.h:
+                raise RuntimeError("DeviceData has been closed")
+            mean, var = self._ctx.data_column_moments()
+            self._stats = ColumnStats(mean, np.sqrt(var), self.shape[0])
+        return self._stats
+
+    def standardized(self, center=False, stats=None):
+        """A new ``DeviceData`` (same device and dtype, a lifetime of its own) holding ``x / std``, or
+        ``(x - mean) / std`` with ``center``: the drivers' ``--standardize``
+        (``valid_data / np.std(valid_data, axis=0, keepdims=True)``, bin/run_jra55_pca_aa.py:165-166) without
+        leaving the device.  ``stats``: None (this block's own ``column_stats()``) or the ``ColumnStats`` of
+        another block -- a validation or cross-validation test block takes its training block's.  A zero or
+        non-finite std, where the reference would silently produce inf / NaN, is a ``ValueError`` raised before
+        anything is copied.  ``valid`` and ``original_shape`` are inherited; ``scaling`` records what was applied."""
+        if stats is not None:
+            shift, scale = _checked_stats(stats, self.shape[1], center)
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        if stats is None:
+            stats = self.column_stats()
+            shift, scale = _checked_stats(stats, self.shape[1], center)
+        ctx = _backend.Context(dtype=self.dtype, device=self._ctx.device)
+        try:
+            ctx.set_data_rows_affine(self._ctx, 0, self.shape[0], shift, scale)
+        except Exception:
+            ctx.close()
+            raise
+        return DeviceData(ctx, self.shape, self.valid, self.original_shape, ColumnScaling(stats, bool(center)))
+
+    def unscale(self, array):
+        """Host only: a ``(..., n_features)`` array in this block's units (archetypes, a dictionary's transpose,
+        a reconstruction) back in the units before ``standardized()``: ``array * std (+ mean)``.  The identity
+        for a block that is not standardised."""
+        if self.scaling is None:
+            return array
+        array = np.asarray(array, dtype=np.float64)
+        stats, center = self.scaling
+        if array.ndim < 1 or array.shape[-1] != self.shape[1]:
+            raise ValueError("DeviceData.unscale: the last axis must hold the %d features; got shape %r"
+                             % (self.shape[1], array.shape))
+        out = array * np.asarray(stats.std, dtype=np.float64)
+        if center:
+            out += np.asarray(stats.mean, dtype=np.float64)
+        return out
 
     def to_host(self):
         if self._host is None:
@@ -94,14 +177,17 @@ class DeviceData(object):
         return self
 
 
-def weight_and_flatten_on_device(values, weights=None, rows=None, dtype=None, device=None):
+def weight_and_flatten_on_device(values, weights=None, rows=None, dtype=None, device=None, standardize=False):
     """``values``: array (n_samples, *feature_dims), NaN where data are missing (``da.values``
     with the sample dimension first, as ``weight_and_flatten_data`` arranges it);
     ``weights``: None or an array broadcastable to ``feature_dims`` (e.g. the latitude weights
     ``sqrt(cos(lat))[:, None]`` for (lat, lon) fields);
     ``rows``: None (all samples) or a ``slice`` / ``(start, stop)`` of the block to keep resident
     (``slice(0, n_training)`` for the training set, ``slice(n_training, None)`` for validation --
-    the NaN mask is always taken over ALL samples, as the reference takes it before it splits).
+    the NaN mask is always taken over ALL samples, as the reference takes it before it splits);
+    ``standardize``: divide every kept column by its standard deviation over the rows kept, as the JRA-55
+    drivers' ``--standardize`` does after the mask (bin/run_jra55_pca_aa.py:157-166); the block returned is
+    ``DeviceData.standardized()`` of the one described above and carries the statistics in ``scaling``.
     Returns a ``DeviceData``."""
     values = np.asarray(values)
     if values.ndim < 2:
@@ -127,4 +213,8 @@ def weight_and_flatten_on_device(values, weights=None, rows=None, dtype=None, de
     except Exception:
         ctx.close()
         raise
-    return DeviceData(ctx, (stop - start, int(valid.sum())), valid, feature_shape)
+    block = DeviceData(ctx, (stop - start, int(valid.sum())), valid, feature_shape)
+    if not standardize:
+        return block
+    with block:
+        return block.standardized()

@@ -342,6 +342,14 @@ int launch_col_has_nan(Ctx *c, const void *raw_dev, int host_dtype, long ld, lon
 int launch_gather_weight(Ctx *c, const void *raw_dev, int host_dtype, long ld, long row0, long n,
                          const int *idx_dev, long p_valid, const double *w_dev);
 int launch_data_to_double(Ctx *c, double *out_dev);
+// column moments of the resident matrix in two sweeps (float64 arithmetic, fixed summation order) and the
+// affine row-block copy behind aa_set_data_rows_affine
+#define AA_MOMENT_MAX_SLABS 2048
+long moment_slab_rows(long n, long p_pad, long *nslab_out);          // rows per slab; *nslab_out <= min(n, AA_MOMENT_MAX_SLABS)
+int launch_col_moments(Ctx *c, double *partial_dev /* nslab x p_pad */, double *mean_dev /* p_pad */,
+                       double *var_dev /* p_pad, nullable */);
+int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shift_dev /*nullable*/,
+                       const double *scale_dev /*nullable*/);
 int launch_gpnh_solve(Ctx *c, double lambda, int *ok_dev);
 // R restarts side by side (kernels_tall.hip: GpnhSlots)
 int launch_gpnh_solve_slots(Ctx *c, double lambda);

@@ -2777,6 +2777,197 @@ int launch_data_to_double(Ctx *c, double *out_dev)
     return AA_OK;
 }
 
+// ---- column moments and the affine row-block copy (run_jra55_pca_aa.py:165-166 / run_jra55_pca_gpnh.py:162-163:
+// valid_data / np.std(valid_data, axis=0), on the resident matrix)
+//
+// A block covers 128 adjacent columns with 16-byte loads (float4: 32 lanes, double2: 64 lanes; row starts are
+// 512-byte aligned because p_pad is a multiple of 128), the rest of its 256 threads are row lanes.
+template <typename T> struct ColVec;
+template <> struct ColVec<float>  { typedef float4  vec; enum { V = 4, CL = 32, RL = 8 }; };
+template <> struct ColVec<double> { typedef double2 vec; enum { V = 2, CL = 64, RL = 4 }; };
+__device__ __forceinline__ void colvec_get(const float4 &v, double *x) { x[0] = v.x; x[1] = v.y; x[2] = v.z; x[3] = v.w; }
+__device__ __forceinline__ void colvec_get(const double2 &v, double *x) { x[0] = v.x; x[1] = v.y; }
+__device__ __forceinline__ float4 colvec_put(const double *x, float)
+{
+    return make_float4((float)x[0], (float)x[1], (float)x[2], (float)x[3]);
+}
+__device__ __forceinline__ double2 colvec_put(const double *x, double) { return make_double2(x[0], x[1]); }
+
+// One sweep of the two-sweep column moments: partial[slab][j] = sum over the slab's rows of x (SQ = false) or
+// of (x - mean[j])^2 (SQ = true), all in float64.  Slab blockIdx.y holds rows [y rps, min((y + 1) rps, n)); a row
+// lane adds its rows in ascending order, the row lanes are combined in lane order through LDS: the same bits on
+// every call, no atomics.
+template <typename T, bool SQ>
+__global__ __launch_bounds__(256) void k_col_moment_sweep(const T *__restrict__ X, long ld, long n, long rps,
+                                                          const double *__restrict__ mean, double *__restrict__ partial)
+{
+    typedef ColVec<T> CV;
+    typedef typename CV::vec vec;
+    constexpr int V = CV::V, CL = CV::CL, RL = CV::RL;
+    __shared__ double red[RL][128];
+    const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const long col = (long)blockIdx.x * 128 + cl * V;
+    const long r0 = (long)blockIdx.y * rps;
+    const long r1 = r0 + rps < n ? r0 + rps : n;
+    double m[V], acc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        m[v] = SQ ? mean[col + v] : 0.0;
+        acc[v] = 0.0;
+    }
+    const T *src = X + col;
+    long r = r0 + rl;
+    for (; r + 3 * RL < r1; r += 4 * RL) {              // four loads in flight per thread
+        vec q[4];
+#pragma unroll
+        for (int u = 0; u < 4; ++u) q[u] = *reinterpret_cast<const vec *>(src + (r + u * RL) * ld);
+#pragma unroll
+        for (int u = 0; u < 4; ++u) {
+            double x[V];
+            colvec_get(q[u], x);
+#pragma unroll
+            for (int v = 0; v < V; ++v) {
+                const double d = x[v] - m[v];
+                acc[v] += SQ ? d * d : d;
+            }
+        }
+    }
+    for (; r < r1; r += RL) {
+        double x[V];
+        colvec_get(*reinterpret_cast<const vec *>(src + r * ld), x);
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            const double d = x[v] - m[v];
+            acc[v] += SQ ? d * d : d;
+        }
+    }
+#pragma unroll
+    for (int v = 0; v < V; ++v) red[rl][cl * V + v] = acc[v];
+    __syncthreads();
+    if (threadIdx.x < 128) {
+        double s = red[0][threadIdx.x];
+#pragma unroll
+        for (int i = 1; i < RL; ++i) s += red[i][threadIdx.x];
+        partial[(long)blockIdx.y * ld + (long)blockIdx.x * 128 + threadIdx.x] = s;
+    }
+}
+
+// out[j] = (sum of the slab partials of column j, in a fixed order) / n.  8 columns x 32 slab lanes per block:
+// slab lane i adds slabs i, i + 32, ... in ascending order (four loads in flight: a thread walking the slabs
+// one by one is a chain of dependent-latency loads), then the 32 lanes are added in lane order.
+__global__ __launch_bounds__(256) void k_col_moment_finish(const double *__restrict__ partial, long ld, long nslab,
+                                                           double n, double *__restrict__ out)
+{
+    __shared__ double red[32][8];
+    const int cl = threadIdx.x % 8, sl = threadIdx.x / 8;
+    const long col = (long)blockIdx.x * 8 + cl;           // < ld: the grid is ld / 8
+    const double *src = partial + col;
+    double s = 0.0;
+    long i = sl;
+    for (; i + 96 < nslab; i += 128) {
+        const double a0 = src[i * ld], a1 = src[(i + 32) * ld], a2 = src[(i + 64) * ld], a3 = src[(i + 96) * ld];
+        s += a0;
+        s += a1;
+        s += a2;
+        s += a3;
+    }
+    for (; i < nslab; i += 32) s += src[i * ld];
+    red[sl][cl] = s;
+    __syncthreads();
+    if (sl == 0) {
+        double t = red[0][cl];
+#pragma unroll
+        for (int j = 1; j < 32; ++j) t += red[j][cl];
+        out[col] = t / n;
+    }
+}
+
+// Y[r][j] = (T)(((double)X[row0 + r][j] - shift[j]) / scale[j]) for r < n, j < p: float64 subtraction and a true
+// float64 division, one rounding to T.  Columns p .. p_pad of a vector that straddles p are stored as the zeros
+// they already are; vectors beyond p and rows beyond n are not touched (Y is a zero-filled allocation).
+template <typename T>
+__global__ __launch_bounds__(256) void k_affine_rows(const T *__restrict__ X, long ld, long row0, long n, long p,
+                                                     const double *__restrict__ shift, const double *__restrict__ scale,
+                                                     T *__restrict__ Y)
+{
+    typedef ColVec<T> CV;
+    typedef typename CV::vec vec;
+    constexpr int V = CV::V, CL = CV::CL, RL = CV::RL;
+    const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const long col = (long)blockIdx.x * 128 + cl * V;
+    if (col >= p) return;
+    double sh[V], sc[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        sh[v] = (shift && col + v < p) ? shift[col + v] : 0.0;
+        sc[v] = (scale && col + v < p) ? scale[col + v] : 1.0;
+    }
+    for (long r = (long)blockIdx.y * RL + rl; r < n; r += (long)gridDim.y * RL) {
+        double x[V];
+        colvec_get(*reinterpret_cast<const vec *>(X + (row0 + r) * ld + col), x);
+#pragma unroll
+        for (int v = 0; v < V; ++v) x[v] = col + v < p ? (x[v] - sh[v]) / sc[v] : 0.0;
+        *reinterpret_cast<vec *>(Y + r * ld + col) = colvec_put(x, T());
+    }
+}
+
+// Row slabs of the moment sweeps: enough blocks to fill the chip (about 2048) when there are few 128-column
+// blocks, never more slabs than rows, at most AA_MOMENT_MAX_SLABS.
+long moment_slab_rows(long n, long p_pad, long *nslab_out)
+{
+    const long xb = p_pad / 128;
+    long nslab = (AA_MOMENT_MAX_SLABS + xb - 1) / xb;
+    if (nslab > n) nslab = n;
+    const long rps = (n + nslab - 1) / nslab;
+    *nslab_out = (n + rps - 1) / rps;
+    return rps;
+}
+
+// mean_dev / var_dev: p_pad doubles each (var_dev nullable: one sweep); partial_dev: nslab x p_pad doubles
+int launch_col_moments(Ctx *c, double *partial_dev, double *mean_dev, double *var_dev)
+{
+    long nslab = 0;
+    const long rps = moment_slab_rows(c->n, c->p_pad, &nslab);
+    const dim3 grid((unsigned)(c->p_pad / 128), (unsigned)nslab), fgrid((unsigned)(c->p_pad / 8));
+#define SWEEP(T, SQ, mean, out)                                                                                   \
+    do {                                                                                                          \
+        hipLaunchKernelGGL((k_col_moment_sweep<T, SQ>), grid, dim3(256), 0, c->stream, c->X.as<T>(), c->p_pad,    \
+                           c->n, rps, mean, partial_dev);                                                         \
+        AA_CHECK_HIP(hipGetLastError());                                                                          \
+        hipLaunchKernelGGL(k_col_moment_finish, fgrid, dim3(256), 0, c->stream, partial_dev, c->p_pad, nslab,     \
+                           (double)c->n, out);                                                                    \
+        AA_CHECK_HIP(hipGetLastError());                                                                          \
+    } while (0)
+    if (c->dtype == AA_F32) {
+        SWEEP(float, false, (const double *)nullptr, mean_dev);
+        if (var_dev) SWEEP(float, true, mean_dev, var_dev);
+    } else {
+        SWEEP(double, false, (const double *)nullptr, mean_dev);
+        if (var_dev) SWEEP(double, true, mean_dev, var_dev);
+    }
+#undef SWEEP
+    return AA_OK;
+}
+
+// c->X (zero filled, c->n x c->p_pad) from rows [row0, row0 + c->n) of the owner's matrix of the same p_pad
+int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shift_dev, const double *scale_dev)
+{
+    const long xb = c->p_pad / 128;
+    const long RL = c->dtype == AA_F32 ? ColVec<float>::RL : ColVec<double>::RL;
+    long yb = (4096 + xb - 1) / xb;
+    if (yb > (c->n + RL - 1) / RL) yb = (c->n + RL - 1) / RL;
+    if (yb > 65535) yb = 65535;
+    const dim3 grid((unsigned)xb, (unsigned)yb);
+    if (c->dtype == AA_F32)
+        hipLaunchKernelGGL(k_affine_rows<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(owner_X),
+                           c->p_pad, row0, c->n, c->p, shift_dev, scale_dev, c->X.as<float>());
+    else
+        hipLaunchKernelGGL(k_affine_rows<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(owner_X),
+                           c->p_pad, row0, c->n, c->p, shift_dev, scale_dev, c->X.as<double>());
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
 // ---------------------------------------------------------------- scale factors (delta != 0)
 // _update_kernel_aa_scale_factors (archetypal_analysis.py:243-258): spg() (spg.py:46-283) on the
 // k-vector alpha with the box projection clip(alpha, 1 - delta, 1 + delta), objective and gradient

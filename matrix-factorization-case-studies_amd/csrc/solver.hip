@@ -881,6 +881,97 @@ int aa_set_data_rows(aa_ctx *h, const aa_ctx *owner, long row0, long n)
     return AA_OK;
 }
 
+int aa_set_data_rows_affine(aa_ctx *h, const aa_ctx *owner, long row0, long n, const double *shift, const double *scale)
+{
+    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_rows_affine: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
+    AA_REQUIRE(o->device == c->device && o->dtype == c->dtype, AA_ERR_ARG,
+               "aa_set_data_rows_affine: same device and same data type needed");
+    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
+               "aa_set_data_rows_affine is single-rank");
+    AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
+               row0 + n, o->n);
+    // refused before anything of ctx is released: a zero or non-finite divisor, a non-finite shift
+    for (long j = 0; j < o->p; ++j) {
+        AA_REQUIRE(!scale || (scale[j] != 0.0 && scale[j] - scale[j] == 0.0), AA_ERR_ARG,
+                   "aa_set_data_rows_affine: scale[%ld] = %g is zero or not finite", j, scale[j]);
+        AA_REQUIRE(!shift || shift[j] - shift[j] == 0.0, AA_ERR_ARG,
+                   "aa_set_data_rows_affine: shift[%ld] = %g is not finite", j, shift[j]);
+    }
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    c->form = AA_FORM_DATA;
+    c->linear_kernel = false;
+    c->implicit_kernel = 0;
+    c->cross_s = 0;
+    c->n = n;
+    c->p = o->p;
+    c->n_pad = round_up(n, 128);
+    c->p_pad = o->p_pad;
+    c->n_global = n;
+    c->row_offset = 0;
+    c->have_data = false;
+    const size_t es = esize(c);
+    c->X.release();
+    AA_CHECK(c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * es));   // zero filled: the padding of aa_set_data
+    DevBuf coef;                                                              // shift | scale, p_pad doubles each
+    int rc = coef.alloc((size_t)2 * c->p_pad * sizeof(double));
+    hipError_t e = hipSuccess;
+    double *dshift = shift ? coef.as<double>() : nullptr, *dscale = scale ? coef.as<double>() + c->p_pad : nullptr;
+    if (rc == AA_OK && shift) e = ctx_memcpy(c, dshift, shift, (size_t)c->p * sizeof(double), hipMemcpyHostToDevice);
+    if (rc == AA_OK && e == hipSuccess && scale)
+        e = ctx_memcpy(c, dscale, scale, (size_t)c->p * sizeof(double), hipMemcpyHostToDevice);
+    if (rc == AA_OK && e == hipSuccess) rc = launch_affine_rows(c, o->X.p, row0, dshift, dscale);
+    if (rc == AA_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
+    coef.release();
+    if (rc == AA_OK && e != hipSuccess) {
+        set_error("aa_set_data_rows_affine: %s", hipGetErrorString(e));
+        rc = AA_ERR_HIP;
+    }
+    AA_CHECK(rc);
+    c->have_data = true;
+    c->have_trace = false;
+    c->k = 0;   // forces (re)allocation of the factor buffers
+    c->KP = 0;
+    c->have_state = false;
+    c->grams_valid = false;
+    return AA_OK;
+}
+
+int aa_data_column_moments(aa_ctx *h, double *mean, double *var)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_data_column_moments: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA, AA_ERR_STATE, "no data matrix (data form)");
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "aa_data_column_moments is single-rank");
+    if (!mean && !var) return AA_OK;
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(join_side(c));
+    long nslab = 0;
+    (void)moment_slab_rows(c->n, c->p_pad, &nslab);
+    DevBuf partial, mom;                                                      // mom: mean | var, p_pad doubles each
+    int rc = partial.alloc((size_t)nslab * c->p_pad * sizeof(double));
+    if (rc == AA_OK) rc = mom.alloc((size_t)2 * c->p_pad * sizeof(double));
+    if (rc == AA_OK)
+        rc = launch_col_moments(c, partial.as<double>(), mom.as<double>(), var ? mom.as<double>() + c->p_pad : nullptr);
+    hipError_t e = hipSuccess;
+    if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
+    if (rc == AA_OK && e == hipSuccess && mean)
+        e = ctx_memcpy(c, mean, mom.p, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost);
+    if (rc == AA_OK && e == hipSuccess && var)
+        e = ctx_memcpy(c, var, mom.as<double>() + c->p_pad, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost);
+    partial.release();
+    mom.release();
+    if (rc == AA_OK && e != hipSuccess) {
+        set_error("aa_data_column_moments: %s", hipGetErrorString(e));
+        rc = AA_ERR_HIP;
+    }
+    return rc;
+}
+
 int aa_set_data_weighted(aa_ctx *h, const void *raw, int host_dtype, long n_total, long p_full, long ld,
                          const double *col_weight, long row0, long n, unsigned char *valid, long *p_valid)
 {
