@@ -358,7 +358,8 @@ typedef struct {
                                   scale-factor update                                        */
     int    error_iter;
     int    spg_flags;          /* OR of the dictionary SPG's AA_SPG_FLAG_* over iterations */
-    int    reserved;
+    int    reserved;           /* iterations enqueued: >= n_iter + 1 and < n_iter + 1 + check_every
+                                  (the ones behind n_iter ran and were discarded)           */
     double cost;               /* cost after the last iteration kept                       */
 } aa_iter_stats;
 

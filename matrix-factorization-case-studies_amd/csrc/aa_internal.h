@@ -136,9 +136,44 @@ struct ProjState {          // per projection, device memory
 
 #define AA_SC_STRIDE 64      // doubles per slot of the per-slot scalar blocks (>= SC_COUNT)
 
-struct IterState {          // aa_iterate: device-side loop status
-    int stop, converged, error_stage, stop_iter, last_iter, spg_flags, pad0, pad1;
+struct IterState {          // device-side loop status of a fit (aa_iterate, aa_gpnh_iterate) or of a restart slot
+    int stop, converged, error_stage, stop_iter, last_iter, spg_flags;
+    int not_definite;       // GPNH: the normal equations of a dictionary update were not positive definite
+    int pad1;
 };
+
+// The outer iteration's judge: the monotonicity check, then the stopping criterion
+// (archetypal_analysis.py:167-197), evaluated on the device by one thread.  The rule is constant for a
+// loop; the rest names the iteration judged.  Kernels take either part by value.
+struct JudgeRule {
+    double tol, mono_tol;
+    int criterion, require, upd_dict, upd_w;
+    int track_spg;          // an SPG run is behind the dictionary update: fold its flags into the status record
+};
+struct LoopJudge {
+    JudgeRule rule;
+    int on, it;             // on: a rule is set (a zeroed record judges nothing)
+    double cost0;
+    IterState *st;
+};
+// the only reader of the rule's fields of aa_iter_params (beside the argument checks)
+inline LoopJudge loop_judge(const aa_iter_params *ip, int it, double cost0, IterState *st, int track_spg)
+{
+    LoopJudge jd;
+    memset(&jd, 0, sizeof(jd));
+    jd.rule.tol = ip->tolerance;
+    jd.rule.mono_tol = ip->mono_tolerance;
+    jd.rule.criterion = ip->criterion;
+    jd.rule.require = ip->require_monotonic;
+    jd.rule.upd_dict = ip->update_dictionary;
+    jd.rule.upd_w = ip->update_weights;
+    jd.rule.track_spg = track_spg;
+    jd.on = 1;
+    jd.it = it;
+    jd.cost0 = cost0;
+    jd.st = st;
+    return jd;
+}
 
 // ------------------------------------------------------------------ context
 struct Comm;   // RCCL wrapper (comm.hip)
@@ -314,16 +349,9 @@ int launch_ride_post(Ctx *c, Ctx::RidePost *rp, const double *gather);   // the 
 #define AA_WIDE_TAIL(KP) ((size_t)(KP) * (KP) + (size_t)64 * 4 * (KP))   // doubles behind a wide buffer for riders // A'B  (KPxKP)
 int launch_gram_wide(Ctx *c, const double *A, const double *B, double *out_dev); // A B' (KPxKP)
 int launch_scale_gram(Ctx *c, double *dst, const double *src);      // dst = D src D
-// the outer iteration's judge, run by the cost kernel that records the iteration's last cost
-struct GpnhJudge {
-    int on, it;
-    double cost0, tol, mono_tol;
-    int criterion, require, upd_dict, upd_w;
-    IterState *st;
-    int track_spg;              // AA: fold the dictionary SPG's flags into the status record
-};
-int launch_aa_cost(Ctx *c, double *out_dev, int *slot_counter_dev = nullptr, const GpnhJudge *judge = nullptr);   // cost from gramState;
-                                              // with a counter: out_dev[(*counter)++]
+// cost from gramState; with a counter: out_dev[(*counter)++]; with a judge: the outer iteration's judge
+// rides in the kernel, behind the iteration's last cost
+int launch_aa_cost(Ctx *c, double *out_dev, int *slot_counter_dev = nullptr, const LoopJudge *judge = nullptr);
 int launch_set_scalars(Ctx *c, double trace, double fnorm);          // SC_TRACE, SC_FNORM
 int launch_wide_axpy_lambda(Ctx *c, double *P, const double *Q, void *PT);   // P += lambda*Q; PT = T(P)
 int launch_wide_to_T(Ctx *c, const double *src, void *dstT);
@@ -332,11 +360,15 @@ int launch_transpose_tall_to_wide(Ctx *c, const double *tall, double *wide, void
 int launch_scalar_stage(Ctx *c, int stage, const aa_spg_params *sp, int it);
 int launch_linesearch_fused(Ctx *c, const aa_spg_params *sp, double *cost_out, int *cost_slot);
 int launch_dict_setup(Ctx *c, const aa_spg_params *sp, double fnorm, unsigned slotmask = 0xffffffffu);
-int launch_iter_judge(Ctx *c, int it, double cost0, const double *costs, IterState *st,
-                      const aa_iter_params *ip, bool judged = false);
+// the judge of iteration jd.it (judged: the cost kernel before it has run it already), then the conditional
+// snapshot of the factors when the loop stopped at that iteration: Z and the dictionary -- C' with the scale
+// factors (AA), or -- wide_dict -- W' (GPNH)
+int launch_iter_judge(Ctx *c, const LoopJudge &jd, const double *costs, bool judged, bool wide_dict);
 int launch_cost_carry(Ctx *c, double *costs, int *slot, double cost0);
-int launch_scale_factors(Ctx *c, const aa_spg_params *sp, double delta_box, int it, double cost0,
-                         const double *costs, const int *slot, IterState *st, double mono_tol, int require);
+// jd: iteration, initial cost and status record of the single fit (the slots take theirs from the slot
+// records), and the rule whose monotonicity check follows the update
+int launch_scale_factors(Ctx *c, const aa_spg_params *sp, double delta_box, const LoopJudge &jd,
+                         const double *costs, const int *slot);
 int launch_col_has_nan(Ctx *c, const void *raw_dev, int host_dtype, long ld, long n_total, long p_full,
                        const double *w_dev /*nullable*/, unsigned char *flags_dev);
 int launch_gather_weight(Ctx *c, const void *raw_dev, int host_dtype, long ld, long row0, long n,
@@ -351,19 +383,18 @@ int launch_col_moments(Ctx *c, double *partial_dev /* nslab x p_pad */, double *
 int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shift_dev /*nullable*/,
                        const double *scale_dev /*nullable*/);
 int launch_gpnh_solve(Ctx *c, double lambda, int *ok_dev);
-// R restarts side by side (kernels_tall.hip: GpnhSlots)
+// R restarts side by side (kernels_tall.hip: RestartSlots); rule: what the slots' judges apply (what = 2; a
+// zeroed one otherwise)
 int launch_gpnh_solve_slots(Ctx *c, double lambda);
-int launch_gpnh_cost_slots(Ctx *c, double lambda, unsigned mask, int what, const aa_iter_params *ip, bool form_gram);
+int launch_gpnh_cost_slots(Ctx *c, double lambda, unsigned mask, int what, const JudgeRule &rule, bool form_gram);
 int launch_gpnh_snap_slots(Ctx *c);
-int launch_aa_cost_slots(Ctx *c, int what, const aa_iter_params *ip);
+int launch_aa_cost_slots(Ctx *c, int what, const JudgeRule &rule);
 int launch_aa_snap_slots(Ctx *c);
 int launch_qp_slots_aa(Ctx *c, const aa_qp_params *p);      // kernels_qp.hip: quad + wave kernels, grid.y = slot
 int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_params *p);   // kernels_qp.hip
 bool gpnh_cost_can_gram(const Ctx *c);
 int launch_gpnh_cost(Ctx *c, double lambda, double *out_dev, int *slot_counter, bool from_wide = false,
-                     bool gram_w = false, const GpnhJudge *judge = nullptr);
-int launch_gpnh_judge(Ctx *c, int it, double cost0, const double *costs, IterState *st,
-                      const aa_iter_params *ip, bool judged = false);
+                     bool gram_w = false, const LoopJudge *judge = nullptr);
 enum { ST_INIT_F = 0, ST_ALPHA = 1, ST_LINESEARCH = 2, ST_BB = 3, ST_CONV = 4 };
 int launch_row_sqnorm_sum(Ctx *c, double *trace_out_host);
 int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double *xj_host, double *d_host);

@@ -1782,7 +1782,7 @@ __device__ __forceinline__ void sum_pq_partials(const double *__restrict__ parti
 // own cost record, slot counter and status record (slot_record), and takes its iteration index
 // from its slot counter: slots start and stop independently (a stopped slot keeps iterating until
 // the host replaces it; its factors were saved at the stopping iteration).
-struct GpnhSlots {
+struct RestartSlots {
     int R, k;
     double *costs;        // [R][stride]
     int stride;
@@ -1792,17 +1792,15 @@ struct GpnhSlots {
     int max_outer;
 };
 
-__device__ __forceinline__ void iter_judge_thread0(int it, double cost0, const double *__restrict__ costs,
-                                                   IterState *__restrict__ st, double tol, double mono_tol,
-                                                   int criterion, int require, int upd_dict, int upd_w,
-                                                   const double *__restrict__ scal, int track_spg);
+__device__ __forceinline__ void iter_judge_thread0(const LoopJudge &jd, const double *__restrict__ costs,
+                                                   const double *__restrict__ scal);
 
 // One thread: `cost` into slot r's record at the slot's counter.  what = 1: the cost after the dictionary
-// update; what = 2: the cost after the weights update, then the slot's judge (the iteration index is the
-// record's; scal_r: the slot's scalar block when an SPG run is behind it) and the iteration cap.
-__device__ __forceinline__ void slot_record(const GpnhSlots &sl, int r, double cost, int what, double tol,
-                                            double mono_tol, int criterion, int require,
-                                            const double *__restrict__ scal_r, int track_spg)
+// update; what = 2: the cost after the weights update, then the slot's judge (`rule` on the record's
+// iteration index, initial cost and status; scal_r: the slot's scalar block when an SPG run is behind it)
+// and the iteration cap.
+__device__ __forceinline__ void slot_record(const RestartSlots &sl, int r, double cost, int what,
+                                            const JudgeRule &rule, const double *__restrict__ scal_r)
 {
     double *rec = sl.costs + (size_t)r * sl.stride;
     int idx = sl.counters[r];
@@ -1811,7 +1809,13 @@ __device__ __forceinline__ void slot_record(const GpnhSlots &sl, int r, double c
     sl.counters[r] = idx + 1;
     if (what == 2) {
         const int it = idx / 2;
-        iter_judge_thread0(it, sl.cost0[r], rec, &sl.st[r], tol, mono_tol, criterion, require, 1, 1, scal_r, track_spg);
+        LoopJudge jd;
+        jd.rule = rule;
+        jd.on = 1;
+        jd.it = it;
+        jd.cost0 = sl.cost0[r];
+        jd.st = &sl.st[r];
+        iter_judge_thread0(jd, rec, scal_r);
         // the iteration cap ends a slot like the stopping rule does (not converged)
         if (!sl.st[r].stop && it + 1 >= sl.max_outer) {
             sl.st[r].stop = 1;
@@ -1901,7 +1905,7 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin_slots(const double *__r
                                                                const double *__restrict__ M,
                                                                double *__restrict__ scal, aa_spg_params sp,
                                                                int k, int R, double *__restrict__ ckct_state,
-                                                               double n_global, GpnhSlots sl)
+                                                               double n_global, RestartSlots sl)
 {
     __shared__ double smt[256];
     __shared__ double smt2[256];
@@ -1915,7 +1919,7 @@ __global__ __launch_bounds__(1024) void k_linesearch_fin_slots(const double *__r
         linesearch_traces(Mr, G1, G2, k, KP, smt, smt2);
         if (t == 0) {
             linesearch_thread0(sc, sp, smt[0], smt2[0]);
-            slot_record(sl, r, aa_cost_from_scalars(sc, n_global), 1, 0.0, 0.0, 0, 0, nullptr, 0);
+            slot_record(sl, r, aa_cost_from_scalars(sc, n_global), 1, JudgeRule{}, nullptr);
         }
         __syncthreads();
     }
@@ -2653,7 +2657,7 @@ __global__ __launch_bounds__(256) void k_aa_cost(const double *__restrict__ stat
                                                  double trace, double n_global,
                                                  double *__restrict__ out,
                                                  int *__restrict__ slot_counter,
-                                                 const double *__restrict__ scal, GpnhJudge jd)
+                                                 const double *__restrict__ scal, LoopJudge jd)
 {
     __shared__ double sm[256];
     const double cost = aa_cost_body(state, alpha, k, KP, trace, n_global, sm);
@@ -2663,9 +2667,7 @@ __global__ __launch_bounds__(256) void k_aa_cost(const double *__restrict__ stat
         const int idx = slot_counter ? (*slot_counter)++ : 0;
         out[idx] = cost;
         // the outer iteration's judge rides along with the iteration's last cost (aa_iterate)
-        if (jd.on)
-            iter_judge_thread0(jd.it, jd.cost0, out, jd.st, jd.tol, jd.mono_tol, jd.criterion, jd.require,
-                               jd.upd_dict, jd.upd_w, scal, jd.track_spg);
+        if (jd.on) iter_judge_thread0(jd, out, scal);
     }
 }
 
@@ -2995,14 +2997,18 @@ __device__ __forceinline__ double sf_wmax(double v)
 __global__ __launch_bounds__(64) void k_scale_factors_spg(const double *__restrict__ state /*ZtZ|CKCt|CKZ*/,
                                                           double *__restrict__ alpha, int k, int KP,
                                                           double trace, double n_global, double delta_box,
-                                                          aa_spg_params sp, int it, double cost0,
+                                                          aa_spg_params sp, LoopJudge jd,
                                                           const double *__restrict__ costs,
                                                           const int *__restrict__ slot,
-                                                          IterState *__restrict__ st, double mono_tol,
-                                                          int require, const double *slot_costs = nullptr,
+                                                          const double *slot_costs = nullptr,
                                                           int slot_stride = 0, const double *slot_cost0 = nullptr)
 {
     extern __shared__ double lds[];               // B1 [k][k+1] | B2 [k][k+1] | xs [64]
+    int it = jd.it;
+    double cost0 = jd.cost0;
+    IterState *st = jd.st;
+    const double mono_tol = jd.rule.mono_tol;
+    const int require = jd.rule.require;
     if (slot_costs) {
         // restarts side by side (aa_slots_*): block = slot -- its diagonal blocks of the Gram state, its
         // k scale factors, its cost record, counter and status; the iteration index is the record's
@@ -3129,16 +3135,18 @@ __global__ __launch_bounds__(64) void k_scale_factors_spg(const double *__restri
     }
 }
 
-int launch_scale_factors(Ctx *c, const aa_spg_params *sp, double delta_box, int it, double cost0,
-                         const double *costs, const int *slot, IterState *st, double mono_tol, int require)
+int launch_scale_factors(Ctx *c, const aa_spg_params *sp, double delta_box, const LoopJudge &jd,
+                         const double *costs, const int *slot)
 {
     if (c->slots_aa) {
         const int k = c->slots_k;
         const size_t lds_s = ((size_t)2 * k * (k + 1) + 64) * sizeof(double);
+        LoopJudge js = jd;                        // the rule; block r takes the rest from slot r's records
+        js.st = c->slotStates.as<IterState>();
         hipLaunchKernelGGL(k_scale_factors_spg, dim3((unsigned)c->slots_R), dim3(64), lds_s, c->stream,
                            (const double *)c->gramState.as<double>(), c->alphaDev.as<double>(), k, c->KP,
-                           c->trace, (double)c->n_global, delta_box, *sp, 0, 0.0, (const double *)nullptr,
-                           (const int *)c->slotCounters.as<int>(), c->slotStates.as<IterState>(), mono_tol, require,
+                           c->trace, (double)c->n_global, delta_box, *sp, js, (const double *)nullptr,
+                           (const int *)c->slotCounters.as<int>(),
                            (const double *)c->slotCosts.as<double>(), c->slots_stride,
                            (const double *)c->slotCost0.as<double>());
         AA_CHECK_HIP(hipGetLastError());
@@ -3147,21 +3155,22 @@ int launch_scale_factors(Ctx *c, const aa_spg_params *sp, double delta_box, int 
     const size_t lds = ((size_t)2 * c->k * (c->k + 1) + 64) * sizeof(double);
     hipLaunchKernelGGL(k_scale_factors_spg, dim3(1), dim3(64), lds, c->stream,
                        (const double *)c->gramState.as<double>(), c->alphaDev.as<double>(), c->k, c->KP,
-                       c->trace, (double)c->n_global, delta_box, *sp, it, cost0, costs, slot, st, mono_tol,
-                       require);
+                       c->trace, (double)c->n_global, delta_box, *sp, jd, costs, slot);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
 
 // ---------------------------------------------------------------- device-side loop control
-// Status record of aa_iterate (device memory): written by one thread after every outer
-// iteration, read by the host once per batch.
+// Status record of a device loop (aa_iterate, aa_gpnh_iterate; device memory): written by one thread
+// after every outer iteration, read by the host once per batch.
 // costs[2*it], costs[2*it + 1]: cost after the dictionary / weights update of iteration `it`.
-__device__ __forceinline__ void iter_judge_thread0(int it, double cost0, const double *__restrict__ costs,
-                                                   IterState *__restrict__ st, double tol, double mono_tol,
-                                                   int criterion, int require, int upd_dict, int upd_w,
-                                                   const double *__restrict__ scal, int track_spg)
+__device__ __forceinline__ void iter_judge_thread0(const LoopJudge &jd, const double *__restrict__ costs,
+                                                   const double *__restrict__ scal)
 {
+    const int it = jd.it, criterion = jd.rule.criterion, require = jd.rule.require;
+    const int upd_dict = jd.rule.upd_dict, upd_w = jd.rule.upd_w, track_spg = jd.rule.track_spg;
+    const double cost0 = jd.cost0, tol = jd.rule.tol, mono_tol = jd.rule.mono_tol;
+    IterState *__restrict__ st = jd.st;
     if (st->stop) return;
     const double old = it == 0 ? cost0 : costs[2 * it - 1];
     const double c1 = costs[2 * it], c2 = costs[2 * it + 1];
@@ -3198,31 +3207,26 @@ __device__ __forceinline__ void iter_judge_thread0(int it, double cost0, const d
     }
 }
 
-__global__ void k_iter_judge(int it, double cost0, const double *__restrict__ costs,
-                             IterState *__restrict__ st, double tol, double mono_tol, int criterion,
-                             int require, int upd_dict, int upd_w, const double *__restrict__ scal,
-                             int track_spg)
+__global__ void k_iter_judge(LoopJudge jd, const double *__restrict__ costs, const double *__restrict__ scal)
 {
     if (threadIdx.x != 0 || blockIdx.x != 0) return;
-    iter_judge_thread0(it, cost0, costs, st, tol, mono_tol, criterion, require, upd_dict, upd_w, scal, track_spg);
+    iter_judge_thread0(jd, costs, scal);
 }
 
-// keeps the factors of the iteration at which the loop stopped (later iterations of the same
-// batch overwrite Ct / Zt); every block reads one word and leaves unless this is that iteration
+// keeps the factors of the iteration at which the loop stopped (later iterations of the same batch
+// overwrite them): two arrays and, when given, the KP scale factors; every block reads one word and
+// leaves unless this is that iteration
 __global__ __launch_bounds__(256) void k_iter_snapshot(int it, const IterState *__restrict__ st,
-                                                       const double *__restrict__ Ct,
-                                                       const double *__restrict__ Zt,
-                                                       double *__restrict__ snapC,
-                                                       double *__restrict__ snapZ, long elems,
-                                                       const double *__restrict__ alpha,
+                                                       const double *__restrict__ a, double *__restrict__ sa,
+                                                       long na, const double *__restrict__ b,
+                                                       double *__restrict__ sb, long nb,
+                                                       const double *__restrict__ alpha /* nullable */,
                                                        double *__restrict__ snapAlpha, int KP)
 {
     if (!st->stop || st->stop_iter != it) return;
-    if (blockIdx.x == 0 && (int)threadIdx.x < KP) snapAlpha[threadIdx.x] = alpha[threadIdx.x];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < elems; i += (long)gridDim.x * 256) {
-        snapC[i] = Ct[i];
-        snapZ[i] = Zt[i];
-    }
+    if (alpha && blockIdx.x == 0 && (int)threadIdx.x < KP) snapAlpha[threadIdx.x] = alpha[threadIdx.x];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < na; i += (long)gridDim.x * 256) sa[i] = a[i];
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nb; i += (long)gridDim.x * 256) sb[i] = b[i];
 }
 
 // costs[slot] = the previous entry (an update that is switched off leaves the cost unchanged)
@@ -3233,17 +3237,22 @@ __global__ void k_cost_carry(double *__restrict__ costs, int *__restrict__ slot,
     costs[idx] = idx == 0 ? cost0 : costs[idx - 1];
 }
 
-int launch_iter_judge(Ctx *c, int it, double cost0, const double *costs, IterState *st,
-                      const aa_iter_params *ip, bool judged)
+int launch_iter_judge(Ctx *c, const LoopJudge &jd, const double *costs, bool judged, bool wide_dict)
 {
     if (!judged)                                   // else: done by the cost kernel before it
-        hipLaunchKernelGGL(k_iter_judge, dim3(1), dim3(64), 0, c->stream, it, cost0, costs, st, ip->tolerance,
-                           ip->mono_tolerance, ip->criterion, ip->require_monotonic, ip->update_dictionary,
-                           ip->update_weights, (const double *)c->scalars.as<double>(), 1);
-    hipLaunchKernelGGL(k_iter_snapshot, dim3(512), dim3(256), 0, c->stream, it, (const IterState *)st,
-                       (const double *)c->Ct.as<double>(), (const double *)c->Zt.as<double>(),
-                       c->snapC.as<double>(), c->snapZ.as<double>(), (long)c->n_pad * c->KP,
-                       (const double *)c->alphaDev.as<double>(), c->snapAlpha.as<double>(), c->KP);
+        hipLaunchKernelGGL(k_iter_judge, dim3(1), dim3(64), 0, c->stream, jd, costs,
+                           (const double *)c->scalars.as<double>());
+    const long tall = (long)c->n_pad * c->KP;
+    if (wide_dict)                                 // GPNH: Z and W'
+        hipLaunchKernelGGL(k_iter_snapshot, dim3(256), dim3(256), 0, c->stream, jd.it, (const IterState *)jd.st,
+                           (const double *)c->Zt.as<double>(), c->snapZ.as<double>(), tall,
+                           (const double *)c->P.as<double>(), c->snapC.as<double>(), (long)c->KP * c->p_pad,
+                           (const double *)nullptr, (double *)nullptr, c->KP);
+    else                                           // AA: C', Z and the scale factors
+        hipLaunchKernelGGL(k_iter_snapshot, dim3(512), dim3(256), 0, c->stream, jd.it, (const IterState *)jd.st,
+                           (const double *)c->Ct.as<double>(), c->snapC.as<double>(), tall,
+                           (const double *)c->Zt.as<double>(), c->snapZ.as<double>(), tall,
+                           (const double *)c->alphaDev.as<double>(), c->snapAlpha.as<double>(), c->KP);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
@@ -3447,7 +3456,7 @@ __global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ Zt
                                                    int *__restrict__ slot_counter,
                                                    const double *__restrict__ ZtX,
                                                    const double *__restrict__ Wt, int ld,
-                                                   double *WtW_out, GpnhJudge jd)
+                                                   double *WtW_out, LoopJudge jd)
 {
     __shared__ double sm[256], sm2[256], sm3[256];
     __shared__ double wl[4096 + 64];
@@ -3461,31 +3470,19 @@ __global__ __launch_bounds__(256) void k_gpnh_cost(const double *__restrict__ Zt
         const double s1 = ZtX ? sm3[0] : scal[slot];    // its own: without ZtX, tr(W'X'Z) was left in scal[slot]
         out[idx] = gpnh_cost_value(trace, s1, sm[0], sm2[0], k, p, n_samples, lambda);
         // the outer iteration's judge (monotonicity, stopping rule) rides along with its last cost
-        if (jd.on)
-            iter_judge_thread0(jd.it, jd.cost0, out, jd.st, jd.tol, jd.mono_tol, jd.criterion, jd.require,
-                               jd.upd_dict, jd.upd_w, scal, 0);
+        if (jd.on) iter_judge_thread0(jd, out, scal);
     }
 }
 
-__global__ __launch_bounds__(256) void k_copy2(const IterState *__restrict__ st, int it,
-                                               const double *__restrict__ a, double *__restrict__ sa,
-                                               long na, const double *__restrict__ b,
-                                               double *__restrict__ sb, long nb)
-{
-    if (st && (!st->stop || st->stop_iter != it)) return;
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < na; i += (long)gridDim.x * 256) sa[i] = a[i];
-    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < nb; i += (long)gridDim.x * 256) sb[i] = b[i];
-}
-
 // ---------------------------------------------------------------- GPNH, R restarts side by side
-// (the layout, GpnhSlots and slot_record: above k_linesearch_fin)
+// (the layout, RestartSlots and slot_record: above k_linesearch_fin)
 // gpnh_solve_body on the slot's block of Z'Z and its rows of Z'X and W'; `bad` goes to the slot's status record
 template <int KM>
 __global__ __launch_bounds__(256) void k_gpnh_solve_slots(const double *__restrict__ ZtZ /*[KP][KP]*/,
                                                           const double *__restrict__ ZtX /*[KP][ld]*/,
                                                           int ld, int p, int KP, double n_samples,
                                                           double lambda, double *__restrict__ Wt,
-                                                          float *__restrict__ WtF, GpnhSlots sl)
+                                                          float *__restrict__ WtF, RestartSlots sl)
 {
     extern __shared__ double L[];                 // k x k, row-major, lower triangle
     __shared__ double dmax_s;
@@ -3494,7 +3491,7 @@ __global__ __launch_bounds__(256) void k_gpnh_solve_slots(const double *__restri
     if (gpnh_solve_body<KM>(ZtZ + (size_t)o * KP + o, ZtX + (long)o * ld, ld, p, k, KP, n_samples, lambda,
                             Wt + (long)o * ld, WtF ? WtF + (long)o * ld : nullptr, L, &dmax_s, &bad)) {
         // its own: this slot only, its dictionary stays as it is
-        if (threadIdx.x == 0 && blockIdx.x == 0) sl.st[r].pad0 = 1;
+        if (threadIdx.x == 0 && blockIdx.x == 0) sl.st[r].not_definite = 1;
     }
     // (no padding rows: component slots beyond R k are zero since aa_gpnh_slots_begin and are never written)
 }
@@ -3509,9 +3506,8 @@ __global__ __launch_bounds__(256) void k_gpnh_solve_slots(const double *__restri
 __global__ __launch_bounds__(256) void k_gpnh_cost_slots(const double *__restrict__ ZtZ, double *WtW,
                                                          int KP, int p, double trace, double n_samples,
                                                          double lambda, const double *__restrict__ ZtX,
-                                                         const double *__restrict__ Wt, int ld, GpnhSlots sl,
-                                                         unsigned mask, int what, double tol, double mono_tol,
-                                                         int criterion, int require, int form_gram)
+                                                         const double *__restrict__ Wt, int ld, RestartSlots sl,
+                                                         unsigned mask, int what, JudgeRule rule, int form_gram)
 {
     __shared__ double sm[256], sm2[256], sm3[256];
     __shared__ double wl[4096 + 64];
@@ -3523,7 +3519,7 @@ __global__ __launch_bounds__(256) void k_gpnh_cost_slots(const double *__restric
     if (threadIdx.x == 0) {
         const double cost = gpnh_cost_value(trace, sm3[0], sm[0], sm2[0], k, p, n_samples, lambda);
         if (what == 0) sl.cost0[r] = cost;            // its own: the initial cost is no entry of the record
-        else slot_record(sl, r, cost, what, tol, mono_tol, criterion, require, nullptr, 0);
+        else slot_record(sl, r, cost, what, rule, nullptr);
     }
 }
 
@@ -3531,7 +3527,7 @@ __global__ __launch_bounds__(256) void k_gpnh_cost_slots(const double *__restric
 // iteration): its columns of Z and its rows of W' into the snapshot arrays
 __global__ __launch_bounds__(256) void k_gpnh_snap_slots(const double *__restrict__ Zt, double *__restrict__ snapZ,
                                                          long n_pad, int KP, const double *__restrict__ Wt,
-                                                         double *__restrict__ snapW, int ld, GpnhSlots sl)
+                                                         double *__restrict__ snapW, int ld, RestartSlots sl)
 {
     for (int r = 0; r < sl.R; ++r) {
         const IterState st = sl.st[r];
@@ -3567,12 +3563,10 @@ int launch_gpnh_solve(Ctx *c, double lambda, int *ok_dev)
 bool gpnh_cost_can_gram(const Ctx *c) { return c->k * c->k <= 256 && (long)c->k * c->p_pad <= 4096; }
 
 int launch_gpnh_cost(Ctx *c, double lambda, double *out_dev, int *slot_counter, bool from_wide, bool gram_w,
-                     const GpnhJudge *judge)
+                     const LoopJudge *judge)
 {
     double *gs = c->gramState.as<double>();
-    GpnhJudge jd;
-    memset(&jd, 0, sizeof(jd));
-    if (judge) jd = *judge;
+    const LoopJudge jd = judge ? *judge : LoopJudge{};
     hipLaunchKernelGGL(k_gpnh_cost, dim3(1), dim3(256), 0, c->stream, (const double *)gs,
                        (const double *)(gs + (size_t)c->KP * c->KP),
                        (const double *)c->scalars.as<double>(), (int)SC_S1, c->k, c->KP, (int)c->p, c->trace,
@@ -3584,36 +3578,20 @@ int launch_gpnh_cost(Ctx *c, double lambda, double *out_dev, int *slot_counter, 
     return AA_OK;
 }
 
-// GPNH flavour of launch_iter_judge: the snapshot keeps Z and the dictionary (W', wide)
-int launch_gpnh_judge(Ctx *c, int it, double cost0, const double *costs, IterState *st,
-                      const aa_iter_params *ip, bool judged)
-{
-    if (!judged)                                   // else: done by the cost kernel before it
-        hipLaunchKernelGGL(k_iter_judge, dim3(1), dim3(64), 0, c->stream, it, cost0, costs, st, ip->tolerance,
-                           ip->mono_tolerance, ip->criterion, ip->require_monotonic, ip->update_dictionary,
-                           ip->update_weights, (const double *)c->scalars.as<double>(), 0 /* no SPG behind it */);
-    hipLaunchKernelGGL(k_copy2, dim3(256), dim3(256), 0, c->stream, (const IterState *)st, it,
-                       (const double *)c->Zt.as<double>(), c->snapZ.as<double>(), (long)c->n_pad * c->KP,
-                       (const double *)c->P.as<double>(), c->snapC.as<double>(), (long)c->KP * c->p_pad);
-    AA_CHECK_HIP(hipGetLastError());
-    return AA_OK;
-}
-
 // AA restarts side by side: cost of slot blockIdx.x from the diagonal blocks of the Gram state
 // (aa_cost_body); what = 0: initial cost -> cost0[r]; what = 2: the cost after the weights
 // update -> the slot's record, then its judge (the iteration index is the record's)
 __global__ __launch_bounds__(256) void k_aa_cost_slots(const double *__restrict__ state,
                                                        const double *__restrict__ alpha, int KP, double trace,
                                                        double n_global, const double *__restrict__ scal,
-                                                       GpnhSlots sl, int what, double tol, double mono_tol,
-                                                       int criterion, int require)
+                                                       RestartSlots sl, int what, JudgeRule rule)
 {
     __shared__ double sm[256];
     const int r = blockIdx.x, k = sl.k, o = r * k;
     const double cost = aa_cost_body(state + (size_t)o * KP + o, alpha + o, k, KP, trace, n_global, sm);
     if (threadIdx.x == 0) {
         if (what == 0) sl.cost0[r] = cost;            // its own: the initial cost is no entry of the record
-        else slot_record(sl, r, cost, what, tol, mono_tol, criterion, require, scal + (size_t)r * AA_SC_STRIDE, 1);
+        else slot_record(sl, r, cost, what, rule, scal + (size_t)r * AA_SC_STRIDE);
     }
 }
 
@@ -3621,7 +3599,7 @@ __global__ __launch_bounds__(256) void k_aa_cost_slots(const double *__restrict_
 __global__ __launch_bounds__(256) void k_aa_snap_slots(const double *__restrict__ Ct, double *__restrict__ snapC,
                                                        const double *__restrict__ Zt, double *__restrict__ snapZ,
                                                        long n_pad, int KP, const double *__restrict__ P,
-                                                       double *__restrict__ snapP, int ld, GpnhSlots sl,
+                                                       double *__restrict__ snapP, int ld, RestartSlots sl,
                                                        const double *__restrict__ alpha,
                                                        double *__restrict__ snapAlpha)
 {
@@ -3645,9 +3623,9 @@ __global__ __launch_bounds__(256) void k_aa_snap_slots(const double *__restrict_
 }
 
 // ---- launchers of the slot kernels (solver.hip: aa_gpnh_slots_*)
-static GpnhSlots slots_of(Ctx *c)
+static RestartSlots slots_of(Ctx *c)
 {
-    GpnhSlots sl;
+    RestartSlots sl;
     sl.R = c->slots_R;
     sl.k = c->slots_k;
     sl.costs = c->slotCosts.as<double>();
@@ -3659,13 +3637,12 @@ static GpnhSlots slots_of(Ctx *c)
     return sl;
 }
 
-int launch_aa_cost_slots(Ctx *c, int what, const aa_iter_params *ip)
+int launch_aa_cost_slots(Ctx *c, int what, const JudgeRule &rule)
 {
     hipLaunchKernelGGL(k_aa_cost_slots, dim3((unsigned)c->slots_R), dim3(256), 0, c->stream,
                        (const double *)c->gramState.as<double>(), (const double *)c->alphaDev.as<double>(), c->KP,
                        c->trace, (double)c->n_global, (const double *)c->scalars.as<double>(), slots_of(c), what,
-                       ip ? ip->tolerance : 0.0, ip ? ip->mono_tolerance : 0.0, ip ? ip->criterion : 0,
-                       ip ? ip->require_monotonic : 0);
+                       rule);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
@@ -3683,7 +3660,7 @@ int launch_aa_snap_slots(Ctx *c)
 int launch_gpnh_solve_slots(Ctx *c, double lambda)
 {
     const size_t lds = (size_t)c->slots_k * c->slots_k * sizeof(double);
-    const GpnhSlots sl = slots_of(c);
+    const RestartSlots sl = slots_of(c);
 #define GPS(KMV)                                                                                        \
     hipLaunchKernelGGL(k_gpnh_solve_slots<KMV>, dim3((unsigned)((c->p_pad + 255) / 256), (unsigned)sl.R), dim3(256), lds, c->stream, \
                        (const double *)c->gramState.as<double>(), (const double *)c->ZtX.as<double>(),      \
@@ -3696,14 +3673,13 @@ int launch_gpnh_solve_slots(Ctx *c, double lambda)
     return AA_OK;
 }
 
-int launch_gpnh_cost_slots(Ctx *c, double lambda, unsigned mask, int what, const aa_iter_params *ip, bool form_gram)
+int launch_gpnh_cost_slots(Ctx *c, double lambda, unsigned mask, int what, const JudgeRule &rule, bool form_gram)
 {
     double *gs = c->gramState.as<double>();
     hipLaunchKernelGGL(k_gpnh_cost_slots, dim3((unsigned)c->slots_R), dim3(256), 0, c->stream, (const double *)gs,
                        gs + (size_t)c->KP * c->KP, c->KP, (int)c->p, c->trace, (double)c->n_global, lambda,
                        (const double *)c->ZtX.as<double>(), (const double *)c->P.as<double>(), (int)c->p_pad,
-                       slots_of(c), mask, what, ip ? ip->tolerance : 0.0, ip ? ip->mono_tolerance : 0.0,
-                       ip ? ip->criterion : 0, ip ? ip->require_monotonic : 0, form_gram ? 1 : 0);
+                       slots_of(c), mask, what, rule, form_gram ? 1 : 0);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
@@ -3726,11 +3702,9 @@ int launch_scale_gram(Ctx *c, double *dst, const double *src)
     return AA_OK;
 }
 
-int launch_aa_cost(Ctx *c, double *out_dev, int *slot_counter_dev, const GpnhJudge *judge)
+int launch_aa_cost(Ctx *c, double *out_dev, int *slot_counter_dev, const LoopJudge *judge)
 {
-    GpnhJudge jd;
-    memset(&jd, 0, sizeof(jd));
-    if (judge) jd = *judge;
+    const LoopJudge jd = judge ? *judge : LoopJudge{};
     hipLaunchKernelGGL(k_aa_cost, dim3(1), dim3(256), 0, c->stream,
                        (const double *)c->gramState.as<double>(),
                        (const double *)c->alphaDev.as<double>(), c->k, c->KP, c->trace,

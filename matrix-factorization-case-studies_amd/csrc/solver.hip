@@ -18,6 +18,7 @@
 #include "aa_internal.h"
 
 #include <climits>
+#include <functional>
 #include <mutex>
 
 namespace aa {
@@ -1204,6 +1205,48 @@ int aa_weights_update(aa_ctx *h, const aa_qp_params *params, aa_qp_stats *stats)
     return weights_update(&h->c, params, stats);
 }
 
+// One outer iteration of AA, enqueued: the scale-factor stage (scale_spg set), the dictionary update or
+// the carry of its cost, the weights update or the carry of its cost.  cd == nullptr: no cost is
+// recorded.  jd: the iteration's judge -- it rides in the kernel of the iteration's last cost, or
+// stands alone behind the carry -- and the snapshot behind it; nullptr (aa_outer_iterations: both
+// updates, no loop control): neither.
+static int aa_enqueue_iteration(Ctx *c, const aa_spg_params *spg, const aa_qp_params *qp,
+                                const aa_spg_params *scale_spg, double delta, bool upd_dict, bool upd_w,
+                                double *cd, int *slot, const LoopJudge *jd)
+{
+    AA_REQUIRE(jd || (upd_dict && upd_w && !scale_spg), AA_ERR_ARG,
+               "an AA iteration without a judge runs both updates and no scale-factor stage");
+    if (scale_spg) {
+        // archetypal_analysis.py:590-609: the Gram state of the previous weights refresh
+        // (Z'Z, C K C', C K Z) is what the k-vector problem is made of
+        AA_CHECK(ensure_ckz(c));
+        AA_CHECK(launch_scale_factors(c, scale_spg, delta, *jd, cd, slot));
+    }
+    if (upd_dict) {
+        bool recorded = false;
+        c->weights_follow = upd_w;
+        const int rcd = dictionary_update(c, spg, nullptr, true, cd, slot, &recorded);
+        c->weights_follow = false;
+        AA_CHECK(rcd);
+        if (cd && !recorded) {
+            AA_CHECK(ensure_ckz(c));
+            AA_CHECK(launch_aa_cost(c, cd, slot));
+        }
+    } else {
+        AA_CHECK(launch_cost_carry(c, cd, slot, jd->cost0));
+    }
+    if (upd_w) {
+        AA_CHECK(weights_update(c, qp, nullptr));
+        if (cd) AA_CHECK(launch_aa_cost(c, cd, slot, jd));
+        if (jd) AA_CHECK(launch_iter_judge(c, *jd, cd, true, false));
+    } else {
+        AA_CHECK(join_side(c));                    // the snapshot reads the dictionary the side stream steps
+        AA_CHECK(launch_cost_carry(c, cd, slot, jd->cost0));
+        AA_CHECK(launch_iter_judge(c, *jd, cd, false, false));
+    }
+    return AA_OK;
+}
+
 int aa_outer_iterations(aa_ctx *h, int n_outer, const aa_spg_params *spg, const aa_qp_params *qp,
                         double *costs)
 {
@@ -1217,18 +1260,7 @@ int aa_outer_iterations(aa_ctx *h, int n_outer, const aa_spg_params *spg, const 
     double *cd = c->costDev.as<double>();
     AA_CHECK_HIP(hipMemsetAsync(slot, 0, sizeof(int), c->stream));
     auto one_iteration = [&]() -> int {
-        bool recorded = false;
-        c->weights_follow = true;
-        const int rcd = dictionary_update(c, spg, nullptr, true, costs ? cd : nullptr, slot, &recorded);
-        c->weights_follow = false;
-        AA_CHECK(rcd);
-        if (costs && !recorded) {
-            AA_CHECK(ensure_ckz(c));
-            AA_CHECK(launch_aa_cost(c, cd, slot));
-        }
-        AA_CHECK(weights_update(c, qp, nullptr));
-        if (costs) AA_CHECK(launch_aa_cost(c, cd, slot));
-        return AA_OK;
+        return aa_enqueue_iteration(c, spg, qp, nullptr, 0.0, true, true, costs ? cd : nullptr, slot, nullptr);
     };
     // An outer iteration with one SPG iteration per dictionary update is a fixed sequence
     // of ~56 launches without host decisions, two thirds of them small dependent kernels:
@@ -1277,6 +1309,79 @@ int aa_outer_iterations(aa_ctx *h, int n_outer, const aa_spg_params *spg, const 
     return AA_OK;
 }
 
+// ------------------------------------------------------------------ the device loop of a single fit
+// (aa_iterate, aa_gpnh_iterate.)  The host enqueues check_every iterations at a time; every iteration
+// ends with its judge and the conditional snapshot (launch_iter_judge), and the host reads the status
+// record once per batch.
+struct LoopRecords {
+    double *cd;             // costDev: two costs per iteration (64 spare entries behind them)
+    int *slot;              // costSlot: the next free entry of cd
+    IterState *st;
+};
+
+// the records of a loop of at most n_max iterations; counter and status zeroed on the stream.  Apart from
+// run_device_loop because a family may have launches of its own between the two (GPNH: its initial cost)
+static int loop_records_begin(Ctx *c, int n_max, LoopRecords *rec)
+{
+    AA_CHECK(c->costDev.alloc((size_t)(2 * n_max + 64) * sizeof(double)));
+    AA_CHECK(c->costSlot.alloc(64));
+    AA_CHECK(c->iterState.alloc(sizeof(IterState)));
+    rec->cd = c->costDev.as<double>();
+    rec->slot = c->costSlot.as<int>();
+    rec->st = c->iterState.as<IterState>();
+    AA_CHECK_HIP(hipMemsetAsync(rec->slot, 0, sizeof(int), c->stream));
+    AA_CHECK_HIP(hipMemsetAsync(rec->st, 0, sizeof(IterState), c->stream));
+    return AA_OK;
+}
+
+// enqueue(it): one outer iteration, judge and snapshot included.  restore(): the loop stopped behind the
+// last iteration enqueued -- put the kept factors back and rebuild what depends on them.
+// poll_multirank: every poll also reads the projections' deferred overflow state (AA).
+// stop_not_definite: a set IterState::not_definite ends the loop as error stage 3 -- nothing is kept, the
+// caller takes another route (GPNH).  *restored (nullable): whether restore() ran.
+static int run_device_loop(Ctx *c, const LoopRecords &rec, const aa_iter_params *ip, double cost0, double *costs,
+                           aa_iter_stats *stats, bool poll_multirank, bool stop_not_definite,
+                           const std::function<int(int)> &enqueue, const std::function<int()> &restore,
+                           bool *restored = nullptr)
+{
+    const int n_max = ip->max_outer;
+    if (restored) *restored = false;
+    IterState hs;
+    memset(&hs, 0, sizeof(hs));
+    int done = 0;
+    while (done < n_max) {
+        const int batch = n_max - done < ip->check_every ? n_max - done : ip->check_every;
+        for (int b = 0; b < batch; ++b) AA_CHECK(enqueue(done + b));
+        done += batch;
+        AA_CHECK_HIP(hipMemcpyAsync(&hs, rec.st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
+        AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+        if (poll_multirank) AA_CHECK(proj_poll_multirank(c));
+        if (hs.stop || (stop_not_definite && hs.not_definite)) break;
+    }
+    memset(stats, 0, sizeof(*stats));
+    stats->reserved = done;                      /* iterations enqueued (>= n_iter + 1) */
+    if (stop_not_definite && hs.not_definite) {
+        stats->error_stage = 3;
+        stats->n_iter = -1;
+        stats->cost = cost0;
+        return AA_OK;
+    }
+    const int last = hs.stop ? hs.stop_iter : n_max - 1;
+    AA_CHECK_HIP(ctx_memcpy(c, costs, rec.cd, (size_t)2 * (last + 1) * sizeof(double), hipMemcpyDeviceToHost));
+    stats->n_iter = last;
+    stats->converged = hs.converged;
+    stats->error_stage = hs.error_stage;
+    stats->error_iter = hs.error_stage ? hs.stop_iter : -1;
+    stats->spg_flags = hs.spg_flags;
+    stats->cost = costs[2 * last + 1];
+    // iterations behind the stopping one have run: their factors give way to the kept ones
+    if (hs.stop && hs.stop_iter < done - 1 && !hs.error_stage) {
+        AA_CHECK(restore());
+        if (restored) *restored = true;
+    }
+    return AA_OK;
+}
+
 int aa_iterate(aa_ctx *h, const aa_iter_params *ip, const aa_spg_params *spg, const aa_qp_params *qp,
                const aa_spg_params *scale_spg, double cost0, double *costs, aa_iter_stats *stats)
 {
@@ -1286,95 +1391,28 @@ int aa_iterate(aa_ctx *h, const aa_iter_params *ip, const aa_spg_params *spg, co
     Ctx *c = &h->c;
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->have_state && c->grams_valid, AA_ERR_STATE, "aa_iterate needs aa_prepare first");
-    const int n_max = ip->max_outer;
     const size_t tall_bytes = (size_t)c->n_pad * c->KP * sizeof(double);
-    AA_CHECK(c->costDev.alloc((size_t)(2 * n_max + 64) * sizeof(double)));
-    AA_CHECK(c->costSlot.alloc(64));
-    AA_CHECK(c->iterState.alloc(sizeof(IterState)));
     AA_CHECK(c->snapC.alloc(tall_bytes));
     AA_CHECK(c->snapZ.alloc(tall_bytes));
     AA_CHECK(c->snapAlpha.alloc(64 * sizeof(double)));
-    int *slot = c->costSlot.as<int>();
-    double *cd = c->costDev.as<double>();
-    IterState *st = c->iterState.as<IterState>();
-    AA_CHECK_HIP(hipMemsetAsync(slot, 0, sizeof(int), c->stream));
-    AA_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(IterState), c->stream));
+    LoopRecords rec;
+    AA_CHECK(loop_records_begin(c, ip->max_outer, &rec));
     const bool scale = scale_spg != nullptr && ip->delta != 0.0;
     if (scale) AA_REQUIRE(scale_spg->memory <= 16, AA_ERR_ARG, "spg memory > 16 unsupported");
-    IterState hs;
-    memset(&hs, 0, sizeof(hs));
-    int done = 0;
-    while (done < n_max) {
-        const int batch = n_max - done < ip->check_every ? n_max - done : ip->check_every;
-        for (int b = 0; b < batch; ++b) {
-            if (scale) {
-                // archetypal_analysis.py:590-609: the Gram state of the previous weights refresh
-                // (Z'Z, C K C', C K Z) is what the k-vector problem is made of
-                AA_CHECK(ensure_ckz(c));
-                AA_CHECK(launch_scale_factors(c, scale_spg, ip->delta, done + b, cost0, cd, slot, st,
-                                              ip->mono_tolerance, ip->require_monotonic));
-            }
-            if (ip->update_dictionary) {
-                bool recorded = false;
-                c->weights_follow = ip->update_weights != 0;
-                const int rcd = dictionary_update(c, spg, nullptr, true, cd, slot, &recorded);
-                c->weights_follow = false;
-                AA_CHECK(rcd);
-                if (!recorded) {
-                    AA_CHECK(ensure_ckz(c));
-                    AA_CHECK(launch_aa_cost(c, cd, slot));
-                }
-            } else {
-                AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
-            }
-            if (ip->update_weights) {
-                AA_CHECK(weights_update(c, qp, nullptr));
-                GpnhJudge jd;                          // the judge rides in the cost kernel
-                memset(&jd, 0, sizeof(jd));
-                jd.on = 1;
-                jd.it = done + b;
-                jd.cost0 = cost0;
-                jd.tol = ip->tolerance;
-                jd.mono_tol = ip->mono_tolerance;
-                jd.criterion = ip->criterion;
-                jd.require = ip->require_monotonic;
-                jd.upd_dict = ip->update_dictionary;
-                jd.upd_w = ip->update_weights;
-                jd.st = st;
-                jd.track_spg = 1;
-                AA_CHECK(launch_aa_cost(c, cd, slot, &jd));
-                AA_CHECK(launch_iter_judge(c, done + b, cost0, cd, st, ip, true));
-            } else {
-                AA_CHECK(join_side(c));                // the snapshot reads the dictionary the side stream steps
-                AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
-                AA_CHECK(launch_iter_judge(c, done + b, cost0, cd, st, ip));
-            }
-        }
-        done += batch;
-        AA_CHECK_HIP(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-        AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-        AA_CHECK(proj_poll_multirank(c));
-        if (hs.stop) break;
-    }
-    const int last = hs.stop ? hs.stop_iter : n_max - 1;
-    AA_CHECK_HIP(ctx_memcpy(c, costs, cd, (size_t)2 * (last + 1) * sizeof(double), hipMemcpyDeviceToHost));
-    stats->n_iter = last;
-    stats->converged = hs.converged;
-    stats->error_stage = hs.error_stage;
-    stats->error_iter = hs.error_stage ? hs.stop_iter : -1;
-    stats->spg_flags = hs.spg_flags;
-    stats->reserved = done;                      /* iterations enqueued (>= n_iter + 1) */
-    stats->cost = costs[2 * last + 1];
-    const bool restore = hs.stop && hs.stop_iter < done - 1 && !hs.error_stage;
-    if (scale) {                                 /* the host copy of alpha follows the device's */
+    auto enqueue = [&](int it) -> int {
+        const LoopJudge jd = loop_judge(ip, it, cost0, rec.st, 1);
+        return aa_enqueue_iteration(c, spg, qp, scale ? scale_spg : nullptr, ip->delta, ip->update_dictionary != 0,
+                                    ip->update_weights != 0, rec.cd, rec.slot, &jd);
+    };
+    auto read_alpha = [&](const DevBuf &src) -> int {    // the host copy of alpha follows the device's
         std::vector<double> a(c->KP, 1.0);
-        AA_CHECK_HIP(ctx_memcpy(c, a.data(), restore ? c->snapAlpha.p : c->alphaDev.p, (size_t)c->KP * sizeof(double),
-                               hipMemcpyDeviceToHost));
+        AA_CHECK_HIP(ctx_memcpy(c, a.data(), src.p, (size_t)c->KP * sizeof(double), hipMemcpyDeviceToHost));
         for (int i = 0; i < c->k; ++i) c->alpha[i] = a[i];
-    }
-    if (hs.stop && hs.stop_iter < done - 1 && !hs.error_stage) {
-        // iterations behind the stopping one have run: restore its factors and rebuild the
-        // products from them (four passes over the data, once per fit)
+        return AA_OK;
+    };
+    auto restore = [&]() -> int {
+        // the kept factors, and the products rebuilt from them (four passes over the data, once per fit)
+        if (scale) AA_CHECK(read_alpha(c->snapAlpha));
         AA_CHECK_HIP(ctx_memcpy(c, c->Ct.p, c->snapC.p, tall_bytes, hipMemcpyDeviceToDevice));
         AA_CHECK_HIP(ctx_memcpy(c, c->Zt.p, c->snapZ.p, tall_bytes, hipMemcpyDeviceToDevice));
         c->products_valid = false;
@@ -1382,7 +1420,11 @@ int aa_iterate(aa_ctx *h, const aa_iter_params *ip, const aa_spg_params *spg, co
         c->qp_iters_valid = false;
         AA_CHECK(prepare(c, nullptr));
         c->x_feasible = true;                    // came out of our own update
-    }
+        return AA_OK;
+    };
+    bool restored = false;
+    AA_CHECK(run_device_loop(c, rec, ip, cost0, costs, stats, true, false, enqueue, restore, &restored));
+    if (scale && !restored) AA_CHECK(read_alpha(c->alphaDev));
     return AA_OK;
 }
 
@@ -1561,20 +1603,16 @@ int aa_gpnh_iterate(aa_ctx *h, const aa_gpnh_params *gp, const aa_qp_params *qp,
     const double lambda = gp->lambda_W;
     size_t snap_bytes = (size_t)c->n_pad * KP * sizeof(double);
     if ((size_t)KP * c->p_pad * sizeof(double) > snap_bytes) snap_bytes = (size_t)KP * c->p_pad * sizeof(double);
-    AA_CHECK(c->costDev.alloc((size_t)(2 * n_max + 64) * sizeof(double)));
-    AA_CHECK(c->costSlot.alloc(64));
-    AA_CHECK(c->iterState.alloc(sizeof(IterState)));
     AA_CHECK(c->snapC.alloc(snap_bytes));
     AA_CHECK(c->snapZ.alloc(snap_bytes));
     AA_CHECK(c->qpIters.alloc((size_t)c->n * sizeof(int)));
     AA_CHECK(ensure_trace(c));
     for (int i = 0; i < c->k; ++i) c->alpha[i] = 1.0;            // the QP set-up scales by alpha
     AA_CHECK(upload_alpha(c));
-    int *slot = c->costSlot.as<int>();
-    double *cd = c->costDev.as<double>();
-    IterState *st = c->iterState.as<IterState>();
-    AA_CHECK_HIP(hipMemsetAsync(slot, 0, sizeof(int), c->stream));
-    AA_CHECK_HIP(hipMemsetAsync(st, 0, sizeof(IterState), c->stream));
+    LoopRecords rec;
+    AA_CHECK(loop_records_begin(c, n_max, &rec));
+    double *cd = rec.cd;
+    int *slot = rec.slot;
     // Gram state: [0] = Z'Z, [1] = W'W; scal[SC_S1] = tr(W'X'Z) = <XW, Z>
     AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
     AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), dev_CKCt(c)));
@@ -1591,79 +1629,46 @@ int aa_gpnh_iterate(aa_ctx *h, const aa_gpnh_params *gp, const aa_qp_params *qp,
     c->ckz_valid = false;
     c->host_grams_valid = false;
 
-    IterState hs;
-    memset(&hs, 0, sizeof(hs));
-    int done = 0;
-    while (done < n_max) {
-        const int batch = n_max - done < ip->check_every ? n_max - done : ip->check_every;
-        for (int b = 0; b < batch; ++b) {
-            if (ip->update_dictionary) {
-                if (!ztx_current) AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));
-                ztx_current = true;
-                AA_CHECK(launch_gpnh_solve(c, lambda, &st->pad0));                      // W'
-                AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));   // X W
-                const bool gram_in_cost = gpnh_cost_can_gram(c);
-                if (!gram_in_cost) AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), dev_CKCt(c)));
-                AA_CHECK(launch_gpnh_cost(c, lambda, cd, slot, true, gram_in_cost));
-            } else {
-                AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
-            }
-            if (ip->update_weights) {
-                AA_CHECK(launch_qp(c, nullptr, c->Gr.as<double>(), 1, KP, nullptr, c->Zt.as<double>(), KP, c->n,
-                                   c->k, qp, c->qpIters.as<int>(), nullptr, dev_CKCt(c)));
-                c->qp_iters_valid = true;
-                AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
-                AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));   // also the next solve's
-                ztx_current = true;
-                GpnhJudge jd;
-                memset(&jd, 0, sizeof(jd));
-                jd.on = 1;
-                jd.it = done + b;
-                jd.cost0 = cost0;
-                jd.tol = ip->tolerance;
-                jd.mono_tol = ip->mono_tolerance;
-                jd.criterion = ip->criterion;
-                jd.require = ip->require_monotonic;
-                jd.upd_dict = ip->update_dictionary;
-                jd.upd_w = ip->update_weights;
-                jd.st = st;
-                AA_CHECK(launch_gpnh_cost(c, lambda, cd, slot, true, false, &jd));
-                AA_CHECK(launch_gpnh_judge(c, done + b, cost0, cd, st, ip, true));
-            } else {
-                AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
-                AA_CHECK(launch_gpnh_judge(c, done + b, cost0, cd, st, ip));
-            }
+    auto enqueue = [&](int it) -> int {
+        const LoopJudge jd = loop_judge(ip, it, cost0, rec.st, 0 /* no SPG behind the dictionary */);
+        if (ip->update_dictionary) {
+            if (!ztx_current) AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));
+            ztx_current = true;
+            AA_CHECK(launch_gpnh_solve(c, lambda, &rec.st->not_definite));              // W'
+            AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));   // X W
+            const bool gram_in_cost = gpnh_cost_can_gram(c);
+            if (!gram_in_cost) AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), dev_CKCt(c)));
+            AA_CHECK(launch_gpnh_cost(c, lambda, cd, slot, true, gram_in_cost));
+        } else {
+            AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
         }
-        done += batch;
-        AA_CHECK_HIP(hipMemcpyAsync(&hs, st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
-        AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-        if (hs.stop || hs.pad0) break;
-    }
-    memset(stats, 0, sizeof(*stats));
-    stats->reserved = done;
-    if (hs.pad0) {                    // the normal equations were not positive definite
-        stats->error_stage = 3;
-        stats->n_iter = -1;
-        stats->cost = cost0;
+        if (ip->update_weights) {
+            AA_CHECK(launch_qp(c, nullptr, c->Gr.as<double>(), 1, KP, nullptr, c->Zt.as<double>(), KP, c->n,
+                               c->k, qp, c->qpIters.as<int>(), nullptr, dev_CKCt(c)));
+            c->qp_iters_valid = true;
+            AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
+            AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));   // also the next solve's
+            ztx_current = true;
+            AA_CHECK(launch_gpnh_cost(c, lambda, cd, slot, true, false, &jd));   // the judge rides in the cost kernel
+            AA_CHECK(launch_iter_judge(c, jd, cd, true, true));
+        } else {
+            AA_CHECK(launch_cost_carry(c, cd, slot, cost0));
+            AA_CHECK(launch_iter_judge(c, jd, cd, false, true));
+        }
         return AA_OK;
-    }
-    const int last = hs.stop ? hs.stop_iter : n_max - 1;
-    AA_CHECK_HIP(ctx_memcpy(c, costs, cd, (size_t)2 * (last + 1) * sizeof(double), hipMemcpyDeviceToHost));
-    stats->n_iter = last;
-    stats->converged = hs.converged;
-    stats->error_stage = hs.error_stage;
-    stats->error_iter = hs.error_stage ? hs.stop_iter : -1;
-    stats->cost = costs[2 * last + 1];
-    if (hs.stop && hs.stop_iter < done - 1 && !hs.error_stage) {
-        // iterations behind the stopping one have run: restore its factors, rebuild X W
+    };
+    auto restore = [&]() -> int {
+        // the kept factors, X W rebuilt from them
         AA_CHECK_HIP(ctx_memcpy(c, c->Zt.p, c->snapZ.p, (size_t)c->n_pad * KP * sizeof(double), hipMemcpyDeviceToDevice));
         AA_CHECK_HIP(ctx_memcpy(c, c->P.p, c->snapC.p, (size_t)KP * c->p_pad * sizeof(double), hipMemcpyDeviceToDevice));
         AA_CHECK(launch_wide_to_T(c, c->P.as<double>(), operandT(c, c->P, c->Pw)));
         AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));
         c->qp_iters_valid = false;
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-    }
-    return AA_OK;
+        return AA_OK;
+    };
+    // the normal equations not positive definite: the loop ends, the caller solves them another way
+    return run_device_loop(c, rec, ip, cost0, costs, stats, false, true, enqueue, restore);
 }
 
 // ------------------------------------------------------------------ restart slots: the host steps both families share
@@ -1783,7 +1788,7 @@ static int slot_fetch_record(Ctx *c, int r, double *costs, double *cost0)
 }
 
 // the tail of a run call: waits for the iterations, status of every slot out.  flags: the SPG warning
-// flags of the slot (AA) or "normal equations not positive definite" (GPNH: IterState::pad0)
+// flags of the slot (AA) or "normal equations not positive definite" (GPNH: IterState::not_definite)
 static int slots_read_status(Ctx *c, aa_slot_status *status, bool aa)
 {
     const int R = c->slots_R;
@@ -1797,7 +1802,7 @@ static int slots_read_status(Ctx *c, aa_slot_status *status, bool aa)
         status[r].converged = st[r].converged;
         status[r].error_stage = st[r].error_stage;
         status[r].stop_iter = st[r].stop_iter;
-        status[r].flags = aa ? st[r].spg_flags : st[r].pad0;
+        status[r].flags = aa ? st[r].spg_flags : st[r].not_definite;
         status[r].iterations_run = cnt[r] / 2;
     }
     return AA_OK;
@@ -1963,7 +1968,7 @@ int aa_slots_reload(aa_ctx *h, int r, const double *C, long ldc, const double *Z
     // rewritten with the same bits -- their Gram blocks are what they were)
     std::vector<double> c0(32);
     AA_CHECK_HIP(ctx_memcpy(c, c0.data(), c->slotCost0.p, 32 * sizeof(double), hipMemcpyDeviceToHost));
-    AA_CHECK(launch_aa_cost_slots(c, 0, nullptr));
+    AA_CHECK(launch_aa_cost_slots(c, 0, JudgeRule{}));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     for (int q = 0; q < c->slots_R; ++q)
         if (q != r)
@@ -1985,17 +1990,18 @@ int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
     if (!c->slots_started) {
         c->x_feasible = false;
         AA_CHECK(prepare(c, nullptr));
-        AA_CHECK(launch_aa_cost_slots(c, 0, nullptr));
+        AA_CHECK(launch_aa_cost_slots(c, 0, JudgeRule{}));
         c->slots_started = true;
         c->slots_cold = slots_all_mask(c);
         c->slots_cold_cols = 0xffffffffu;
     }
+    // the rule of every slot's judge; iteration, initial cost and status are the slot's own
+    const LoopJudge slots_judge = loop_judge(&c->slots_ip, 0, 0.0, nullptr, 1);
     bool recorded = false;
     for (int it = 0; it < n_iters; ++it) {
         if (c->slots_ip.delta != 0.0) {           // archetypal_analysis.py:590-609, once per slot
             AA_CHECK(ensure_ckz(c));
-            AA_CHECK(launch_scale_factors(c, &c->slots_scale_sp, c->slots_ip.delta, 0, 0.0, nullptr, nullptr, nullptr,
-                                          c->slots_ip.mono_tolerance, c->slots_ip.require_monotonic));
+            AA_CHECK(launch_scale_factors(c, &c->slots_scale_sp, c->slots_ip.delta, slots_judge, nullptr, nullptr));
         }
         if (c->slots_cold) {                      // (aa_slots_reload) the cold update of the freshly loaded slots
             c->x_feasible = false;
@@ -2007,7 +2013,7 @@ int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
         c->slots_cold = 0;
         c->slots_cold_cols = 0xffffffffu;
         AA_CHECK(weights_update(c, &c->slots_qp, nullptr));
-        AA_CHECK(launch_aa_cost_slots(c, 2, &c->slots_ip));
+        AA_CHECK(launch_aa_cost_slots(c, 2, slots_judge.rule));
         AA_CHECK(launch_aa_snap_slots(c));
     }
     return slots_read_status(c, status, true);
@@ -2065,7 +2071,7 @@ int aa_slots_end(aa_ctx *h)
 }
 
 // ------------------------------------------------------------------ GPNH restarts side by side
-// (kernels_tall.hip: GpnhSlots; convex_dim_red/restarts.py drives it).  begin: R empty slots of k
+// (kernels_tall.hip: RestartSlots; convex_dim_red/restarts.py drives it).  begin: R empty slots of k
 // components each in one set of arrays; load: a restart's start factors into a slot, its initial
 // cost; run: outer iterations for all slots, status of every slot back; fetch: factors and cost
 // record of a slot that has stopped.  Single rank.
@@ -2124,7 +2130,7 @@ int aa_gpnh_slots_load(aa_ctx *h, int r, const double *Wt, long ld, const double
     AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
     AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), dev_CKCt(c)));
     AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));
-    AA_CHECK(launch_gpnh_cost_slots(c, c->slots_gp.lambda_W, 1u << r, 0, nullptr, false));
+    AA_CHECK(launch_gpnh_cost_slots(c, c->slots_gp.lambda_W, 1u << r, 0, JudgeRule{}, false));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     return AA_OK;
 }
@@ -2137,7 +2143,7 @@ int aa_gpnh_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
     AA_REQUIRE(c->slots_R > 0, AA_ERR_STATE, "aa_gpnh_slots_begin first");
     const int R = c->slots_R, k = c->slots_k;
     const double lambda = c->slots_gp.lambda_W;
-    const aa_iter_params *ip = &c->slots_gp.loop;
+    const JudgeRule rule = loop_judge(&c->slots_gp.loop, 0, 0.0, nullptr, 0).rule;   // of every slot's judge
     const unsigned all = slots_all_mask(c);
     // the single fit forms W'W inside its cost kernel when the factor is small (gpnh_cost_can_gram
     // with ITS k); the slots follow the same rule so that every restart sees the same bits
@@ -2146,14 +2152,14 @@ int aa_gpnh_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
         AA_CHECK(launch_gpnh_solve_slots(c, lambda));                                      // W'
         AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));       // X W
         if (!gram_in_cost) AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), dev_CKCt(c)));
-        AA_CHECK(launch_gpnh_cost_slots(c, lambda, all, 1, ip, gram_in_cost));
+        AA_CHECK(launch_gpnh_cost_slots(c, lambda, all, 1, rule, gram_in_cost));
         // at most four SPG passes per QP: the lane-per-sample kernel, as in a single fit; more: the
         // four-lane and wave-per-sample kernels of the AA slots (the Hessian blocks are W'W's)
         if (c->slots_qp.max_iterations <= 4) AA_CHECK(launch_qp_slots(c, R, k, dev_CKCt(c), &c->slots_qp));
         else AA_CHECK(launch_qp_slots_aa(c, &c->slots_qp));
         AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
         AA_CHECK(launch_reduce_rows(c, c->Zt.as<double>(), c->ZtX.as<double>(), nullptr));
-        AA_CHECK(launch_gpnh_cost_slots(c, lambda, all, 2, ip, false));
+        AA_CHECK(launch_gpnh_cost_slots(c, lambda, all, 2, rule, false));
         AA_CHECK(launch_gpnh_snap_slots(c));
     }
     return slots_read_status(c, status, false);

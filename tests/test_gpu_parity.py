@@ -1270,6 +1270,58 @@ def test_gpnh_device_loop_matches_host_loop(cdr, orc, lam):
     _assert_simplex(Z, 1e-12)
 
 
+@pytest.mark.parametrize("lam", [0.0, 1.0])
+def test_gpnh_device_loop_kept_state_is_independent_of_poll_interval(cdr, orc, lam):
+    """The host reads the loop's status every `check_every` iterations, so the rule usually fires
+    behind the last iteration enqueued: Z and W' of the stopping iteration are snapshotted on the
+    device, restored, and T(W') and X W rebuilt from them.  check_every = 1 never runs ahead and is
+    the yardstick; every other interval must leave the same bits -- costs, factors, and two
+    follow-up calls on the same context.  The first updates the weights only: the cost of the
+    dictionary step is carried, and the QPs read the X W left behind (with W'W recomputed from
+    the kept W'), so its cost and its weights show whose X W the restore left.  (A full iteration
+    cannot: it solves a new W' and overwrites X W before anything reads it.)  The second is a
+    full iteration from there."""
+    from convex_dim_red import _backend
+    rng = np.random.RandomState(12)
+    n, p, k = 700, 45, 6
+    W0 = rng.standard_normal((p, k))
+    X = orc.right_stochastic_matrix((n, k), rng).dot(W0.T) + 0.1 * rng.standard_normal((n, p))
+    Wi = 0.5 * rng.standard_normal((p, k))
+    Zi = orc.right_stochastic_matrix((n, k), rng)
+    qp_kw = dict(max_iterations=1)
+    runs = {}
+    for check_every in (1, 3, 5, 8):
+        with _backend.Context(dtype="float64") as ctx:
+            ctx.set_data(X)
+            ctx.gpnh_set_factors(k, W=Wi, Z=Zi)
+            cost0, costs, st = ctx.gpnh_iterate(lam, 60, 1e-3, "rel_delta_f", True, True, True, qp_kw,
+                                                check_every=check_every)
+            Z, Wt = ctx.gpnh_get_weights(), ctx.gpnh_get_dictionary()
+            more = []
+            for update_dictionary in (False, True):          # weights only (reads X W), then both
+                m0, m, m_st = ctx.gpnh_iterate(lam, 1, 0.0, "rel_delta_f", False, update_dictionary, True,
+                                               qp_kw, check_every=1)
+                assert m_st.n_iter == 0 and m_st.error_stage == 0 and len(m) == 2
+                more.append(np.concatenate([[m0], m, ctx.gpnh_get_weights().ravel()]))
+            more = np.concatenate(more)
+        runs[check_every] = (cost0, costs.copy(), (st.n_iter, st.converged, st.error_stage, st.reserved),
+                             Z, Wt, more)
+    cost0, costs, (n_iter, converged, error_stage, reserved), Z, Wt, more = runs[1]
+    assert more[1] == more[0] and more[2] != more[1]          # weights-only: carried cost, then a QP step
+    assert 3 < n_iter < 59                                    # stops well inside the record
+    assert converged == 1 and error_stage == 0 and reserved == n_iter + 1
+    assert len(costs) == 2 * (n_iter + 1)
+    behind = 0
+    for check_every, (c0, cs, (ni, conv, err, res), Zr, Wr, m) in runs.items():
+        assert (ni, conv, err) == (n_iter, 1, 0), check_every
+        assert n_iter + 1 <= res < n_iter + 1 + check_every, check_every
+        behind += res > ni + 1
+        assert c0 == cost0 and np.array_equal(cs, costs), check_every
+        assert np.array_equal(Zr, Z) and np.array_equal(Wr, Wt), check_every
+        assert np.array_equal(m, more), check_every
+    assert behind >= 1                                        # the restore path did run
+
+
 def test_gpnh_unused_component_falls_back_to_lstsq(cdr, orc):
     """A weights matrix with an all-zero column makes Z'Z singular; with lambda_W = 0 the normal
     equations have no Cholesky factor, the device loop reports it and the host loop with
