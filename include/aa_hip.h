@@ -110,6 +110,17 @@ int aa_device_count(int *count);
  *   "f64_mfma"          0..3   float64 data: pass kernels on the f64 matrix cores (1, default: the
  *                               row-local one wave-streaming from 32768 rows per GPU, else
  *                               block-tiled; 2 / 3 force either) or on the f64 VALU (0)
+ *   "reduce_sparse"     0|1    1 (default): the reduce-over-rows pass of the dictionary update's SPG
+ *                               direction D'X (D K in the kernel form) reads only the aligned groups of
+ *                               4 rows in which D has an entry != 0.0 (a few hundred rows of n; flags ->
+ *                               gather kernel -> dense kernel on the slabs the gather kernel left).  The
+ *                               same bits as the dense pass for finite X; float32 data and float64 data
+ *                               with f64_mfma != 0; while aa_gemm_timing is enabled the pass runs dense,
+ *                               so that its event pairs time full passes.  0: the dense pass
+ *   "reduce_sparse_max" -1..   flagged groups per row slab up to which the gather kernel takes the slab
+ *                               (above: the dense kernel); -1 (default): a quarter (float32 data) or half
+ *                               (float64 data) of a slab's groups, where the gather kernel stopped paying
+ *                               at 100 000 x 4096 (profiles/reduce_sparse_ab.txt)
  *   "proj_mode"         0|1    column simplex projection: 0 candidate lists, 1 iterative full
  *                               passes (also the fallback of a rank whose list overflows); only 0
  *                               and 1 are accepted
@@ -531,6 +542,18 @@ int aa_kernel_transform_cost(aa_ctx *ctx, const double *A, const double *diag, d
  * solver state invalid (aa_set_state / aa_prepare must follow before any update). */
 int aa_pass_reduce_rows(aa_ctx *ctx, int k, const double *A, double *out, long ldo);
 int aa_pass_row_local(aa_ctx *ctx, int k, const double *B, long ldb, double *out);
+/* aa_pass_reduce_rows through the path of an operand that is expected to be zero in most rows (what
+ * the dictionary update does with its search direction, option "reduce_sparse"): for finite X the result
+ * equals aa_pass_reduce_rows(A) bit for bit, whatever A holds -- an entry of X that is Inf or NaN
+ * contributes NaN to the dense pass even against a zero row of A and nothing here (and the equality
+ * assumes that the matrix cores keep a subnormal accumulator through a step with a zero operand, as
+ * measured: profiles/reduce_sparse_ab.txt).  With
+ * reduce_sparse = 0, or float64 data with f64_mfma = 0, this IS the dense pass. */
+int aa_pass_reduce_rows_flagged(aa_ctx *ctx, int k, const double *A, double *out, long ldo);
+/* The row slabs of the context's most recent flagged reduce-over-rows call (aa_pass_reduce_rows_flagged,
+ * or the D'X pass of the latest dictionary update): out[0] = slabs served by the gather kernel, out[1] =
+ * slabs left to the dense kernel.  Waits for the context's stream.  Both 0 before the first such call. */
+int aa_reduce_sparse_counts(aa_ctx *ctx, long out[2]);
 
 /* Diagnostics: the scalar state of the latest dictionary SPG iteration (device-resident, see
  * csrc/aa_internal.h: ScalarSlot), copied to out[0..AA_SPG_SCALARS).  Layout: 0 tr, 1 tr(C HD),
@@ -550,7 +573,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * 8 = K Z of the implicit RBF kernel (k_rbf_kv; a context after aa_set_rbf_features + aa_set_state),
  * 9 = the cross RBF product of aa_rbf_cross (a context after aa_set_rbf_reference),
  * 10 = the scores pass of aa_gpnh_residual_scores, 11 = the residual pass of aa_gpnh_residual_cost (both
- * without the copy to the host; a context after aa_gpnh_set_factors with dictionary and weights).
+ * without the copy to the host; a context after aa_gpnh_set_factors with dictionary and weights),
+ * 12 = the flagged reduce-over-rows sequence (flags, gather, gated dense; no finish) on whatever the
+ * direction buffer holds (after aa_pass_reduce_rows_flagged or an update; with reduce_sparse = 0 the
+ * dense kernel on the same operand).
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

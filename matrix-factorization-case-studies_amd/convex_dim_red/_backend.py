@@ -168,6 +168,8 @@ _SIGNATURES = {
     "aa_slots_end": (ctypes.c_int, [_vp]),
     "aa_get_spg_scalars": (ctypes.c_int, [_vp, _dp]),
     "aa_pass_reduce_rows": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_long]),
+    "aa_pass_reduce_rows_flagged": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_long]),
+    "aa_reduce_sparse_counts": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
     "aa_pass_row_local": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, _dp]),
     "aa_time_kernel": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_int, _dp]),
     "aa_gemm_timing": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.POINTER(ctypes.c_int), _dp,
@@ -879,6 +881,22 @@ class Context(object):
         _check(self.lib.aa_pass_reduce_rows(self.h, k, _ptr(A), _ptr(out), self.p))
         self.k = k
         return out
+
+    def pass_reduce_rows_flagged(self, A):
+        """``pass_reduce_rows`` through the path for an operand that is zero in most rows (option
+        ``reduce_sparse``): the same bits for finite data."""
+        A = _c64(A)
+        k = A.shape[1]
+        out = np.empty((k, self.p))
+        _check(self.lib.aa_pass_reduce_rows_flagged(self.h, k, _ptr(A), _ptr(out), self.p))
+        self.k = k
+        return out
+
+    def reduce_sparse_counts(self):
+        """Row slabs of the latest flagged reduce-over-rows call: ``(gathered, dense)``."""
+        out = (ctypes.c_long * 2)()
+        _check(self.lib.aa_reduce_sparse_counts(self.h, out))
+        return int(out[0]), int(out[1])
 
     def pass_row_local(self, B):
         """X B' for a host k x p array B through the row-local pass kernel (n x k)."""

@@ -270,6 +270,8 @@ struct Ctx {
     DevBuf wideScratch;                        // KP x max(p_pad, n_pad) double
     // reduction scratch
     DevBuf partial;                            // GEMM split-row partials
+    DevBuf groupFlags;                         // flagged reduce-over-rows: a byte per aligned group of 4 rows of the tall operand
+    DevBuf slabMode;                           // ... a byte per slab (1: gathered, 0: dense), then the two slab counters
     DevBuf rlPartial;                          // row-local GEMM split over column chunks (short, wide data)
     DevBuf redPartial;                         // tall/wide reduction partials
     DevBuf gramOut;                            // up to 4 KPxKP results
@@ -320,8 +322,17 @@ struct Ctx {
 // ------------------------------------------------------------------ kernels_gemm.hip
 // out[KP][p_pad] (double) = sum_r A[r][i] * X[r][c];  A tall double, X T.
 // Also refreshes the T-typed operand copy outT (may alias out when T == double).
+// flag_buf (nullable; &c->groupFlags): the caller expects A_tall to be zero in most of its rows.  With
+// option reduce_sparse the call then flags the operand's non-zero groups of 4 rows (launch_group_flags),
+// gathers those in the slabs with at most reduce_sparse_max of them and runs the dense kernel on the
+// other slabs only: the same bits as the plain call for finite X (kernels_gemm.hip).  While aa_gemm_timing is on
+// the call is the plain one, so that the event pairs keep timing full passes.
 int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *outT,
-                       bool main_only = false);
+                       bool main_only = false, DevBuf *flag_buf = nullptr);
+#define AA_SLAB_MODE_BYTES 256                 // Ctx::slabMode: a mode byte per slab (nslab <= 256), then two counters
+// default reduce_sparse_max: a quarter (float32) / half (float64) of a slab's groups, the largest swept fraction at
+// which the flagged sequence beat the dense pass at the headline shape (profiles/reduce_sparse_ab.txt, section 5)
+#define REDUCE_SPARSE_DEFAULT_DEN(dtype) ((dtype) == AA_F32 ? 4 : 2)
 // second stage of the split-row reduction (after a main_only launch): sums the slab partials
 // plus `extra_slabs` further slabs appended by launch_reduce_rows_fixup
 int launch_reduce_rows_finish(Ctx *c, double *out_wide, void *outT, int extra_slabs);
@@ -342,6 +353,9 @@ int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, doubl
                 const aa_spg_params *sp = nullptr, int stage_after = -1,
                 const aa_spg_params *setup_sp = nullptr /* the update's set-up as block 0 */, double setup_fnorm = 0.0);
 int launch_tall_axpy_lambda(Ctx *c, double *x, const double *d);             // x += lambda * d
+// flags[g] = 1 if any entry of rows 4g..4g+3 of the tall array compares != 0.0 (NaN does, -0.0 does not),
+// g < n_pad / 4; also zeroes the two slab counters of the gather kernel that follows
+int launch_group_flags(Ctx *c, const double *A_tall, unsigned char *flags, unsigned int *counters);
 int launch_tall_dot_scaled(Ctx *c, const double *x, const double *H, const double *alpha_dev,
                            int slot);   // sum x*H*alpha (alpha_dev nullable => 1)
 int launch_gram_tall(Ctx *c, const double *A, const double *B, double *out_dev, bool local_only = false);
@@ -471,6 +485,7 @@ extern int g_proj_mode, g_proj_small, g_proj_list_cap, g_proj_check_always;  // 
 extern int g_fuse_finalize, g_fin_in_last, g_gram_side, g_setup_in_grad;     // kernels_tall.hip
 extern int g_pack_comm, g_pq_mfma;                                           // kernels_tall.hip
 extern int g_row_local_variant, g_row_local_split, g_row_local_acc64, g_f64_mfma;   // kernels_gemm.hip
+extern int g_reduce_sparse, g_reduce_sparse_max;                                    // kernels_gemm.hip
 extern int g_qp_pass_cap, g_qp_mode, g_qp_quad_cap, g_qp_sort;               // kernels_qp.hip
 extern int g_qp_fused_order, g_qp_wave_lazy, g_qp_quad_lazy;                 // kernels_qp.hip
 extern int g_qp_overlap_tail, g_qp_live;                                     // kernels_qp.hip

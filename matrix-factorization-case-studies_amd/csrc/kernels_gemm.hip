@@ -57,16 +57,21 @@ __device__ __forceinline__ void xcd_aware_block(int &colgroup, int &slab)
 // B-operand lane l = X[row r0+2u+(l>>5)][c0 + 4*(l&31) + m]  (one dwordx4 load feeds
 // the four MFMAs m = 0..3, whose output columns are c0 + 4*j + m).
 // ---------------------------------------------------------------------------
-template <int NCT, int U>
+// GATED: the launch behind k_reduce_rows_gather_f32 -- a slab whose mode byte says that the gather
+// kernel has written its partial block is left alone (slab_mode is not read otherwise).
+template <int NCT, int U, bool GATED = false>
 __global__ __launch_bounds__(256) void k_reduce_rows_f32(const float *__restrict__ X, long ldx,
                                                          const double *__restrict__ A,
                                                          long rows_per_slab, long n_pad, int p_pad,
-                                                         float *__restrict__ partial)
+                                                         float *__restrict__ partial,
+                                                         const unsigned char *__restrict__ slab_mode)
 {
     constexpr int KP = 32 * NCT;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int colgroup, slab;
     xcd_aware_block(colgroup, slab);
+    if constexpr (GATED)
+        if (slab_mode[slab]) return;   // block-uniform
     const int c0 = (colgroup * 4 + wave) * 128;
     if (c0 >= p_pad) return;   // wave-uniform; the kernel has no barriers
     const int h = lane >> 5, j = lane & 31;
@@ -172,16 +177,20 @@ typedef double f64x2g __attribute__((ext_vector_type(2)));
 // two 16-byte pieces of X (columns c0 + 32u + 2*(l&15) + e: the two doubles of a piece feed
 // the B operands of two different column tiles, so the loads are 256 contiguous bytes per
 // row and quarter-wave).  Two register sets, software-pipelined as in k_reduce_rows_f32.
-template <int NT>
+// GATED: as in k_reduce_rows_f32.
+template <int NT, bool GATED = false>
 __global__ __launch_bounds__(256) void k_reduce_rows_f64_mfma(const double *__restrict__ X, long ldx,
                                                               const double *__restrict__ A,
                                                               long rows_per_slab, long n_pad,
-                                                              int p_pad, double *__restrict__ partial)
+                                                              int p_pad, double *__restrict__ partial,
+                                                              const unsigned char *__restrict__ slab_mode)
 {
     constexpr int KP = 16 * NT, U = 2;
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     int colgroup, slab;
     xcd_aware_block(colgroup, slab);
+    if constexpr (GATED)
+        if (slab_mode[slab]) return;   // block-uniform
     const int c0 = (colgroup * 4 + wave) * 64;
     if (c0 >= p_pad) return;   // wave-uniform; the kernel has no barriers
     const int lc = lane & 15, lr = lane >> 4;
@@ -1105,6 +1114,285 @@ __global__ __launch_bounds__(256) void k_reduce_rows_fixup_f32(const float *__re
     }
 }
 
+// ---------------------------------------------------------------------------
+// reduce over rows for a tall operand that is zero in almost all of its rows (the SPG direction of
+// the dictionary update: about 200 non-zero rows of 100 000).  k_group_flags (kernels_tall.hip) has
+// written one byte per aligned group of 4 rows: 1 if any entry of the group compares != 0.0.  The
+// gather kernels below run on the grid of their dense twins, with the same block map and strip
+// ownership, and write the same block of `partial`; a wave issues, for every FLAGGED group of its
+// slab in ascending order, exactly the MFMA steps the dense kernel issues for those four rows (same
+// lane-to-row mapping, same conversion of the tall operand).  The steps left out have a tall operand
+// of +-0 in every lane: for finite X they add exact zeros to accumulators that never hold -0 (they
+// start at +0, and x + (-0) = x), so every accumulator chain sees the same sequence of non-trivial
+// steps on the same operands and ends in the same bits, whatever the matrix core does inside a step.
+// A slab with more than `limit` flagged groups is left to the gated dense launch that follows
+// (slab_mode[slab] = 0); the decision is taken per slab on the device, by every wave of the slab
+// alike, and recorded by wave 0 of column group 0 together with the two counters
+// counters[0] (slabs gathered) and counters[1] (slabs left to the dense kernel).
+// ---------------------------------------------------------------------------
+constexpr int GATHER_CHUNK = 512;   // groups per round of flag bytes: 8 per lane, one 8-byte load
+
+// bit b: group g0 + 8 * lane + b of the slab is flagged (ngroups and g0 are multiples of 8)
+__device__ __forceinline__ unsigned gather_flag_mask(const unsigned char *__restrict__ fl, int g0,
+                                                     int ngroups, int lane)
+{
+    const int g = g0 + 8 * lane;
+    if (g >= ngroups) return 0u;
+    const uint2 w = *reinterpret_cast<const uint2 *>(fl + g);
+    unsigned m = 0u;
+#pragma unroll
+    for (int b = 0; b < 8; ++b) {
+        const unsigned byte = ((b < 4 ? w.x : w.y) >> (8 * (b & 3))) & 0xffu;
+        m |= (byte != 0u ? 1u : 0u) << b;
+    }
+    return m;
+}
+
+// Number of flagged groups of the slab (the same value in every lane); m0 = the mask of the first
+// round, which the walk reuses.
+__device__ __forceinline__ int gather_count(const unsigned char *__restrict__ fl, int ngroups, int lane,
+                                            unsigned &m0)
+{
+    m0 = gather_flag_mask(fl, 0, ngroups, lane);
+    int cnt = __popc(m0);
+    for (int g0 = GATHER_CHUNK; g0 < ngroups; g0 += GATHER_CHUNK)
+        cnt += __popc(gather_flag_mask(fl, g0, ngroups, lane));
+#pragma unroll
+    for (int d = 32; d >= 1; d >>= 1) cnt += __shfl_xor(cnt, d, 64);
+    return cnt;
+}
+
+// The flagged groups of one round, in ascending order, into the wave's list (offsets from g0 in
+// groups); returns how many.  The list is private to the wave: LDS operations of a wave complete in
+// order, so no barrier is needed around it.
+__device__ __forceinline__ int gather_list(unsigned m, int lane, unsigned short *list)
+{
+    const int c = __popc(m);
+    int incl = c;
+#pragma unroll
+    for (int d = 1; d < 64; d <<= 1) {
+        const int t = __shfl_up(incl, d, 64);
+        if (lane >= d) incl += t;
+    }
+    const int total = __shfl(incl, 63, 64);
+    int o = incl - c;
+    while (m) {
+        const int b = __ffs((int)m) - 1;
+        list[o++] = (unsigned short)(8 * lane + b);
+        m &= m - 1u;
+    }
+    __builtin_amdgcn_wave_barrier();
+    return total;
+}
+
+// NG flagged groups of k_reduce_rows_gather_f32: the 2 * NG loads first, then their MFMA steps in
+// ascending row order -- per group the two steps (rows 4g + {0,1} and 4g + {2,3}) of the dense kernel
+template <int NCT, int NG>
+__device__ __forceinline__ void gather_groups_f32(const float *__restrict__ xp, long ldx,
+                                                  const double *__restrict__ ap, const long *rows,
+                                                  f32x16 (&acc)[NCT][4])
+{
+    constexpr int KP = 32 * NCT;
+    f32x4 xv[NG][2];
+    double av[NG][2][NCT];
+#pragma unroll
+    for (int t = 0; t < NG; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            const long row = rows[t] + 2 * s;
+            xv[t][s] = *reinterpret_cast<const f32x4 *>(xp + row * ldx);
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) av[t][s][ct] = ap[row * KP + ct * 32];
+        }
+#pragma unroll
+    for (int t = 0; t < NG; ++t)
+#pragma unroll
+        for (int s = 0; s < 2; ++s)
+#pragma unroll
+            for (int ct = 0; ct < NCT; ++ct) {
+                const float af = (float)av[t][s][ct];
+#pragma unroll
+                for (int m = 0; m < 4; ++m)
+                    acc[ct][m] = __builtin_amdgcn_mfma_f32_32x32x2f32(af, xv[t][s][m], acc[ct][m], 0, 0, 0);
+            }
+}
+
+template <int NCT>
+__global__ __launch_bounds__(256) void k_reduce_rows_gather_f32(const float *__restrict__ X, long ldx,
+                                                                const double *__restrict__ A,
+                                                                long rows_per_slab, long n_pad, int p_pad,
+                                                                float *__restrict__ partial,
+                                                                const unsigned char *__restrict__ flags,
+                                                                int limit, unsigned char *__restrict__ slab_mode,
+                                                                unsigned int *__restrict__ counters)
+{
+    constexpr int KP = 32 * NCT, NG = 4;
+    __shared__ unsigned short lists[4][GATHER_CHUNK];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int colgroup, slab;
+    xcd_aware_block(colgroup, slab);
+    const int c0 = (colgroup * 4 + wave) * 128;
+    if (c0 >= p_pad) return;   // wave-uniform; the kernel has no barriers
+    const int h = lane >> 5, j = lane & 31;
+    const long r_begin = (long)slab * rows_per_slab;
+    long r_end = r_begin + rows_per_slab;
+    if (r_end > n_pad) r_end = n_pad;
+    const int ngroups = (int)((r_end - r_begin) >> 2);       // a multiple of 8
+    const unsigned char *fl = flags + (r_begin >> 2);
+
+    unsigned m0;
+    const int cnt = gather_count(fl, ngroups, lane, m0);
+    const bool take = cnt <= limit;
+    if (colgroup == 0 && wave == 0 && lane == 0) {
+        slab_mode[slab] = take ? 1 : 0;
+        atomicAdd(counters + (take ? 0 : 1), 1u);
+    }
+    if (!take) return;         // the gated dense launch serves this slab
+
+    f32x16 acc[NCT][4];
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int m = 0; m < 4; ++m)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) acc[ct][m][e] = 0.f;
+
+    const float *xp = X + (r_begin + h) * ldx + c0 + 4 * j;
+    const double *ap = A + (r_begin + h) * KP + j;
+    unsigned short *list = lists[wave];
+    if (cnt > 0)
+        for (int g0 = 0; g0 < ngroups; g0 += GATHER_CHUNK) {
+            const int total = gather_list(g0 == 0 ? m0 : gather_flag_mask(fl, g0, ngroups, lane), lane, list);
+            int q = 0;
+            long rows[NG];
+            for (; q + NG <= total; q += NG) {
+#pragma unroll
+                for (int t = 0; t < NG; ++t)
+                    rows[t] = 4L * (g0 + __builtin_amdgcn_readfirstlane((int)list[q + t]));
+                gather_groups_f32<NCT, NG>(xp, ldx, ap, rows, acc);
+            }
+            for (; q < total; ++q) {
+                rows[0] = 4L * (g0 + __builtin_amdgcn_readfirstlane((int)list[q]));
+                gather_groups_f32<NCT, 1>(xp, ldx, ap, rows, acc);
+            }
+            __builtin_amdgcn_wave_barrier();   // the next round overwrites the list
+        }
+
+    float *out = partial + (size_t)slab * KP * p_pad;      // as in k_reduce_rows_f32
+#pragma unroll
+    for (int ct = 0; ct < NCT; ++ct)
+#pragma unroll
+        for (int reg = 0; reg < 16; ++reg) {
+            const int comp = ct * 32 + (reg & 3) + 8 * (reg >> 2) + 4 * h;
+            f32x4 v = {acc[ct][0][reg], acc[ct][1][reg], acc[ct][2][reg], acc[ct][3][reg]};
+            *reinterpret_cast<f32x4 *>(out + (size_t)comp * p_pad + c0 + 4 * j) = v;
+        }
+}
+
+// NG flagged groups of k_reduce_rows_gather_f64_mfma: one MFMA step of the dense kernel per group
+template <int NT, int NG>
+__device__ __forceinline__ void gather_groups_f64(const double *__restrict__ xp, long ldx,
+                                                  const double *__restrict__ ap, const long *rows,
+                                                  f64x4g (&acc)[NT][2][2])
+{
+    constexpr int KP = 16 * NT;
+    f64x2g xv[NG][2];
+    double av[NG][NT];
+#pragma unroll
+    for (int t = 0; t < NG; ++t) {
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+            xv[t][u] = *reinterpret_cast<const f64x2g *>(xp + rows[t] * ldx + 32 * u);
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti) av[t][ti] = ap[rows[t] * KP + 16 * ti];
+    }
+#pragma unroll
+    for (int t = 0; t < NG; ++t)
+#pragma unroll
+        for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+            for (int u = 0; u < 2; ++u)
+#pragma unroll
+                for (int e = 0; e < 2; ++e)
+                    acc[ti][u][e] = __builtin_amdgcn_mfma_f64_16x16x4f64(av[t][ti], xv[t][u][e], acc[ti][u][e],
+                                                                         0, 0, 0);
+}
+
+template <int NT>
+__global__ __launch_bounds__(256) void k_reduce_rows_gather_f64_mfma(const double *__restrict__ X, long ldx,
+                                                                     const double *__restrict__ A,
+                                                                     long rows_per_slab, long n_pad, int p_pad,
+                                                                     double *__restrict__ partial,
+                                                                     const unsigned char *__restrict__ flags,
+                                                                     int limit,
+                                                                     unsigned char *__restrict__ slab_mode,
+                                                                     unsigned int *__restrict__ counters)
+{
+    constexpr int KP = 16 * NT, NG = 4;
+    __shared__ unsigned short lists[4][GATHER_CHUNK];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    int colgroup, slab;
+    xcd_aware_block(colgroup, slab);
+    const int c0 = (colgroup * 4 + wave) * 64;
+    if (c0 >= p_pad) return;   // wave-uniform; the kernel has no barriers
+    const int lc = lane & 15, lr = lane >> 4;
+    const long r_begin = (long)slab * rows_per_slab;
+    long r_end = r_begin + rows_per_slab;
+    if (r_end > n_pad) r_end = n_pad;
+    const int ngroups = (int)((r_end - r_begin) >> 2);       // a multiple of 8
+    const unsigned char *fl = flags + (r_begin >> 2);
+
+    unsigned m0;
+    const int cnt = gather_count(fl, ngroups, lane, m0);
+    const bool take = cnt <= limit;
+    if (colgroup == 0 && wave == 0 && lane == 0) {
+        slab_mode[slab] = take ? 1 : 0;
+        atomicAdd(counters + (take ? 0 : 1), 1u);
+    }
+    if (!take) return;         // the gated dense launch serves this slab
+
+    f64x4g acc[NT][2][2];
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int e = 0; e < 2; ++e) acc[ti][u][e] = (f64x4g){0.0, 0.0, 0.0, 0.0};
+
+    const double *xp = X + (r_begin + lr) * ldx + c0 + 2 * lc;
+    const double *ap = A + (r_begin + lr) * KP + lc;
+    unsigned short *list = lists[wave];
+    if (cnt > 0)
+        for (int g0 = 0; g0 < ngroups; g0 += GATHER_CHUNK) {
+            const int total = gather_list(g0 == 0 ? m0 : gather_flag_mask(fl, g0, ngroups, lane), lane, list);
+            int q = 0;
+            long rows[NG];
+            for (; q + NG <= total; q += NG) {
+#pragma unroll
+                for (int t = 0; t < NG; ++t)
+                    rows[t] = 4L * (g0 + __builtin_amdgcn_readfirstlane((int)list[q + t]));
+                gather_groups_f64<NT, NG>(xp, ldx, ap, rows, acc);
+            }
+            for (; q < total; ++q) {
+                rows[0] = 4L * (g0 + __builtin_amdgcn_readfirstlane((int)list[q]));
+                gather_groups_f64<NT, 1>(xp, ldx, ap, rows, acc);
+            }
+            __builtin_amdgcn_wave_barrier();   // the next round overwrites the list
+        }
+
+    double *out = partial + (size_t)slab * KP * p_pad;     // as in k_reduce_rows_f64_mfma
+#pragma unroll
+    for (int ti = 0; ti < NT; ++ti)
+#pragma unroll
+        for (int u = 0; u < 2; ++u)
+#pragma unroll
+            for (int reg = 0; reg < 4; ++reg) {
+                const int comp = 16 * ti + lr + 4 * reg;
+                f64x2g v = {acc[ti][u][0][reg], acc[ti][u][1][reg]};
+                *reinterpret_cast<f64x2g *>(out + (size_t)comp * p_pad + c0 + 32 * u + 2 * lc) = v;
+            }
+}
+
 // measurement only: stream X once with 16-byte loads, no arithmetic to speak of -- the
 // read bandwidth the memory system delivers to a kernel of this shape (aa_time_kernel 2)
 template <int UNROLL>
@@ -1188,17 +1476,73 @@ static void gemm_event(Ctx *c, int which)
     }
 }
 
-int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *outT, bool main_only)
+// The flagged sequence: group flags of the tall operand -> gather kernel -> gated dense kernel.
+// Three launches with the per-slab decision on the device: nothing here waits for the device, and
+// the sequence can be captured in a graph.
+static int launch_reduce_rows_flagged(Ctx *c, const double *A_tall, DevBuf *flag_buf)
+{
+    unsigned char *flags = flag_buf->as<unsigned char>();
+    unsigned char *mode = c->slabMode.as<unsigned char>();
+    unsigned int *counters = reinterpret_cast<unsigned int *>(mode + AA_SLAB_MODE_BYTES);
+    const long gps = c->rows_per_slab / 4;                   // groups per (full) slab
+    long limit = g_reduce_sparse_max < 0 ? gps / REDUCE_SPARSE_DEFAULT_DEN(c->dtype) : (long)g_reduce_sparse_max;
+    if (limit > gps) limit = gps;
+    AA_CHECK(launch_group_flags(c, A_tall, flags, counters));
+    dim3 block(256);
+    if (c->dtype == AA_F32) {
+        dim3 grid((unsigned)((c->p_pad + 511) / 512), (unsigned)c->nslab);
+        float *part = c->partial.as<float>();
+#define RRG(NCTV)                                                                                      \
+    do {                                                                                               \
+        hipLaunchKernelGGL((k_reduce_rows_gather_f32<NCTV>), grid, block, 0, c->stream, c->X.as<float>(), \
+                           c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part,          \
+                           (const unsigned char *)flags, (int)limit, mode, counters);                  \
+        hipLaunchKernelGGL((k_reduce_rows_f32<NCTV, 4, true>), grid, block, 0, c->stream,              \
+                           c->X.as<float>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,             \
+                           (int)c->p_pad, part, (const unsigned char *)mode);                          \
+    } while (0)
+        if (c->KP == 32) RRG(1);
+        else RRG(2);
+#undef RRG
+    } else {
+        dim3 grid((unsigned)((c->p_pad + 255) / 256), (unsigned)c->nslab);
+        double *part = c->partial.as<double>();
+#define RDG(NTV)                                                                                       \
+    do {                                                                                               \
+        hipLaunchKernelGGL((k_reduce_rows_gather_f64_mfma<NTV>), grid, block, 0, c->stream,            \
+                           c->X.as<double>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,            \
+                           (int)c->p_pad, part, (const unsigned char *)flags, (int)limit, mode,        \
+                           counters);                                                                  \
+        hipLaunchKernelGGL((k_reduce_rows_f64_mfma<NTV, true>), grid, block, 0, c->stream,             \
+                           c->X.as<double>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,            \
+                           (int)c->p_pad, part, (const unsigned char *)mode);                          \
+    } while (0)
+        if (c->KP == 32) RDG(2);
+        else RDG(4);
+#undef RDG
+    }
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *outT, bool main_only,
+                       DevBuf *flag_buf)
 {
     dim3 block(256);
-    gemm_event(c, 0);
+    const unsigned char *no_mode = nullptr;
+    // The float64 VALU kernel (f64_mfma = 0) has no gather twin: it stays dense.  So does every call while
+    // aa_gemm_timing is on: its event pairs time full passes (bench.py's roofline, two per outer iteration),
+    // and the dense pass gives the same bits.
+    const bool flagged = flag_buf && g_reduce_sparse && !c->time_gemm && (c->dtype == AA_F32 || g_f64_mfma);
+    if (!flagged) gemm_event(c, 0);
     if (c->dtype == AA_F32) {
         dim3 grid((unsigned)((c->p_pad + 511) / 512), (unsigned)c->nslab);
         float *part = c->partial.as<float>();
 #define RRL(NCTV, UV)                                                                         \
     hipLaunchKernelGGL((k_reduce_rows_f32<NCTV, UV>), grid, block, 0, c->stream, c->X.as<float>(), \
-                       c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part)
-        if (c->KP == 32) RRL(1, 4);
+                       c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode)
+        if (flagged) AA_CHECK(launch_reduce_rows_flagged(c, A_tall, flag_buf));
+        else if (c->KP == 32) RRL(1, 4);
         else RRL(2, 4);
         PASS_NAME(0, "k_reduce_rows_f32<%d,4>", c->KP / 32);
 #undef RRL
@@ -1207,13 +1551,14 @@ int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *out
         double *part = c->partial.as<double>();
         if (g_f64_mfma) PASS_NAME(0, "k_reduce_rows_f64_mfma<%d>", c->KP == 32 ? 2 : 4);
         else PASS_NAME(0, "k_reduce_rows_f64<%d>", c->KP);
-        if (g_f64_mfma) {
+        if (flagged) AA_CHECK(launch_reduce_rows_flagged(c, A_tall, flag_buf));
+        else if (g_f64_mfma) {
             if (c->KP == 32)
                 hipLaunchKernelGGL(k_reduce_rows_f64_mfma<2>, grid, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
+                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode);
             else
                 hipLaunchKernelGGL(k_reduce_rows_f64_mfma<4>, grid, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
+                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode);
         } else if (c->KP == 32)
             hipLaunchKernelGGL(k_reduce_rows_f64<32>, grid, block, 0, c->stream, c->X.as<double>(),
                                c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
@@ -1222,7 +1567,7 @@ int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *out
                                c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
     }
     AA_CHECK_HIP(hipGetLastError());
-    gemm_event(c, 0);
+    if (!flagged) gemm_event(c, 0);
     if (main_only) return AA_OK;
     return launch_reduce_rows_finish(c, out_wide, outT, 0);
 }
@@ -1557,6 +1902,8 @@ int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double
 // 8: wave-streaming (wave-private X tiles, B slabs shared per block); 9: the same with LDS-DMA staging
 // and float64 sums of 32-column pieces (k <= 32).  aa_set_option.
 int g_row_local_variant = -1;   // -1: by size (wave-streaming from 32768 rows per GPU -- 9 for k <= 32, 8 above -- else 4)
+int g_reduce_sparse = 1;       // the flagged reduce-over-rows calls (the SPG direction) gather their non-zero row groups
+int g_reduce_sparse_max = -1;  // flagged groups per slab up to which the gather kernel takes the slab; -1: a quarter (float32) / half (float64) of a slab's groups
 int g_f64_mfma = 1;            // float64 data: pass kernels on the f64 matrix cores (0: f64 VALU;
                                // row-local: 1 = wave-streaming from 32768 rows, else block-tiled;
                                // 2 / 3 = always wave-streaming / always block-tiled)

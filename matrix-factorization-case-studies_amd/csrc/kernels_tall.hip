@@ -2166,6 +2166,53 @@ int tall_setup(Ctx *c)
     return AA_OK;
 }
 
+// One byte per aligned group of 4 rows of a tall array [n_pad][KP]: 1 if any of the group's 4 * KP
+// entries compares != 0.0.  A wave takes 8 consecutive groups (8 or 16 KB, all loads in flight at
+// once) and writes their 8 bytes with one store; n_pad / 4 is a multiple of 8.  Thread 0 also zeroes
+// the slab counters of the gather kernel behind it (launch_reduce_rows).
+template <int KP>
+__global__ __launch_bounds__(256) void k_group_flags(const double *__restrict__ A, long ngroups,
+                                                     unsigned char *__restrict__ flags,
+                                                     unsigned int *__restrict__ counters)
+{
+    typedef double f64x2f __attribute__((ext_vector_type(2)));
+    constexpr int L = KP / 32;                 // 16-byte loads per lane and group
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        counters[0] = 0u;
+        counters[1] = 0u;
+    }
+    const int lane = threadIdx.x & 63;
+    const long g0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+    if (g0 >= ngroups) return;                 // wave-uniform
+    f64x2f v[8][L];
+#pragma unroll
+    for (int u = 0; u < 8; ++u)
+#pragma unroll
+        for (int l = 0; l < L; ++l)
+            v[u][l] = *reinterpret_cast<const f64x2f *>(A + (g0 + u) * (4 * KP) + 2 * (l * 64 + lane));
+    unsigned long long bytes = 0ull;
+#pragma unroll
+    for (int u = 0; u < 8; ++u) {
+        bool nz = false;
+#pragma unroll
+        for (int l = 0; l < L; ++l) nz = nz || v[u][l][0] != 0.0 || v[u][l][1] != 0.0;
+        if (__ballot(nz)) bytes |= 1ull << (8 * u);
+    }
+    if (lane == 0) *reinterpret_cast<unsigned long long *>(flags + g0) = bytes;
+}
+
+int launch_group_flags(Ctx *c, const double *A_tall, unsigned char *flags, unsigned int *counters)
+{
+    const long ngroups = c->n_pad / 4;
+    const dim3 grid((unsigned)((ngroups + 31) / 32));
+    if (c->KP == 32)
+        hipLaunchKernelGGL(k_group_flags<32>, grid, dim3(256), 0, c->stream, A_tall, ngroups, flags, counters);
+    else
+        hipLaunchKernelGGL(k_group_flags<64>, grid, dim3(256), 0, c->stream, A_tall, ngroups, flags, counters);
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
 static inline double *red_buf(Ctx *c) { return c->redOut.as<double>(); }
 
 static int finalize_and_post(Ctx *c, int NV, unsigned max_mask, int kind, int mode, int slot,

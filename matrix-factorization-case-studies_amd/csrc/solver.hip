@@ -85,6 +85,8 @@ static int ensure_problem(Ctx *c, int k)
     c->rows_per_slab = rps;
     c->partial.release();
     AA_CHECK(c->partial.alloc((size_t)(nslab + QP_FIX_SLABS) * KP * c->p_pad * esize(c)));
+    AA_CHECK(c->groupFlags.alloc((size_t)c->n_pad / 4 + AA_SLACK_ROWS));
+    AA_CHECK(c->slabMode.alloc(AA_SLAB_MODE_BYTES + 2 * sizeof(unsigned int)));
     AA_CHECK(tall_setup(c));
     c->alpha.assign(k, 1.0);
     c->ZtZ.assign((size_t)k * k, 0.0);
@@ -416,7 +418,8 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
         if (multi && g_pack_comm && data && !c->slots_aa) c->ride_gather_next = c->Q.as<double>() + (size_t)KP * c->p_pad;
         AA_CHECK(launch_proj(c, x, c->gk.as<double>(), 0.0, SC_ALPHA, PROJ_DIR)); // spg.py:191-194,206
         if (data) {
-            AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr));
+            // d = P(x - alpha g) - x is zero outside supp(x) and supp(P(.)): a few hundred rows
+            AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, false, &c->groupFlags));
             if (fused) {
                 // (P Q'), (Q Q'), the line search, the Gram of the accepted point and -- with one
                 // SPG iteration per update -- the cost after the update: one launch
@@ -432,7 +435,8 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
             if (c->implicit_kernel) {
                 AA_CHECK(launch_implicit_kv(c, c->Dt.as<double>(), c->Gn.as<double>()));  // (D K)' = K D'
             } else {
-                AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->wideScratch.as<double>(), nullptr));
+                AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->wideScratch.as<double>(), nullptr, false,
+                                            &c->groupFlags));
                 AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gn.as<double>()));
             }
             AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), x, gram + GS));
@@ -554,6 +558,8 @@ static const AaOption kOptions[] = {
     {"row_local_acc64", &g_row_local_acc64, 0, 2, false},
     {"row_local_split", &g_row_local_split, 0, 1, true},
     {"f64_mfma", &g_f64_mfma, 0, 3, false},
+    {"reduce_sparse", &g_reduce_sparse, 0, 1, true},
+    {"reduce_sparse_max", &g_reduce_sparse_max, -1, INT_MAX, false},
     {"proj_mode", &g_proj_mode, 0, 1, false},
     {"proj_small", &g_proj_small, INT_MIN, INT_MAX, false},
     {"proj_list_cap", &g_proj_list_cap, 1, 2048, false},
@@ -643,7 +649,7 @@ int aa_ctx_destroy(aa_ctx *h)
     if (c->stream) (void)hipStreamSynchronize(c->stream);
     comm_destroy(c);
     DevBuf *all[] = {&c->X, &c->Ct, &c->Zt, &c->Dt, &c->Gr, &c->Gn, &c->gk, &c->gn, &c->H, &c->tmpTall,
-                     &c->P, &c->Q, &c->ZtX, &c->Pw, &c->Qw, &c->wideScratch, &c->partial, &c->rlPartial, &c->redPartial,
+                     &c->P, &c->Q, &c->ZtX, &c->Pw, &c->Qw, &c->wideScratch, &c->partial, &c->groupFlags, &c->slabMode, &c->rlPartial, &c->redPartial,
                      &c->gramOut, &c->gramState, &c->costDev, &c->costSlot, &c->redOut, &c->redGather, &c->listGather, &c->scalars, &c->proj, &c->projList, &c->projSegCnt, &c->Mdev, &c->alphaDev, &c->iterState, &c->snapC, &c->snapZ, &c->snapAlpha, &c->qpIters, &c->qpPerm, &c->fsScratch, &c->feat, &c->featNorm,
                      &c->crossX, &c->crossNorm, &c->crossV, &c->rowNorm, &c->xformCost, &c->scoreScratch,
                      &c->qpStats, &c->qpLive, &c->slotCosts, &c->slotCounters, &c->slotStates, &c->slotCost0, &c->slotSnapP, &c->slotSaveP, &c->slotSaveGr, &c->tmpTall2, &c->redPartial2, &c->redOut2, &c->proj2, &c->projList2, &c->projSegCnt2};
@@ -2387,7 +2393,8 @@ static int invalidate_solver_state(Ctx *c)
     return AA_OK;
 }
 
-int aa_pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long ldo)
+// A' X for a host operand through launch_reduce_rows; flagged: by the path of a mostly-zero operand
+static int pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long ldo, bool flagged)
 {
     AA_REQUIRE(h && A && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
@@ -2397,10 +2404,36 @@ int aa_pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long ldo
     AA_REQUIRE(ldo >= (c->form == AA_FORM_KERNEL ? c->n : c->p), AA_ERR_ARG, "ldo too small");
     AA_CHECK(invalidate_solver_state(c));
     AA_CHECK(upload_tall(c, c->Dt, A, k, 1, c->n, k));
-    AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr));
+    AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, false,
+                                flagged ? &c->groupFlags : nullptr));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     AA_CHECK_HIP(ctx_memcpy2d(c, out, (size_t)ldo * sizeof(double), c->Q.p, (size_t)c->p_pad * sizeof(double),
                              (size_t)c->p * sizeof(double), (size_t)k, hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+int aa_pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long ldo)
+{
+    return pass_reduce_rows(h, k, A, out, ldo, false);
+}
+
+int aa_pass_reduce_rows_flagged(aa_ctx *h, int k, const double *A, double *out, long ldo)
+{
+    return pass_reduce_rows(h, k, A, out, ldo, true);
+}
+
+int aa_reduce_sparse_counts(aa_ctx *h, long out[2])
+{
+    AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    out[0] = out[1] = 0;
+    if (!c->slabMode.p) return AA_OK;              // no problem size yet: no flagged call either
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    unsigned int v[2] = {0u, 0u};
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy(c, v, c->slabMode.as<unsigned char>() + AA_SLAB_MODE_BYTES, sizeof(v), hipMemcpyDeviceToHost));
+    out[0] = (long)v[0];
+    out[1] = (long)v[1];
     return AA_OK;
 }
 
@@ -2494,6 +2527,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->have_state && c->gpnh_valid &&
                        c->world == 1 && !c->force_comm,
                    AA_ERR_STATE, "aa_time_kernel 10 / 11: aa_gpnh_set_factors (dictionary and weights) first, single rank");
+    else if (which == 12)
+        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
+                   "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
     else {
         AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
         AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
@@ -2522,6 +2558,8 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                 rc = launch_residual_scores(c, nullptr, nullptr, nullptr, false);
             else if (which == 11)
                 rc = launch_residual_cost(c, c->Zt.as<double>(), c->P.as<double>(), nullptr, nullptr);
+            else if (which == 12)
+                rc = launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, true, &c->groupFlags);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
