@@ -322,6 +322,15 @@ int aa_set_linear_kernel(aa_ctx *ctx, int on);
  * aa_distance_column returns sqrt(2 - 2 K_ij).  Single rank, float64 context.  Everything downstream
  * (aa_set_state, aa_prepare, aa_iterate, aa_get_state ...) is the explicit kernel form's. */
 int aa_set_rbf_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma);
+/* The same for the polynomial kernel K_ij = (gamma x_i.x_j + coef0)^degree (scikit-learn's polynomial_kernel),
+ * never formed.  The power is degree - 1 multiplications in a fixed order, evaluated by one device function
+ * everywhere (csrc/aa_internal.h: poly_kappa).  Every product C K / K Z runs on the f64 matrix cores
+ * (csrc/kernels_gemm.hip: k_poly_kv_mfma), tr K = sum_i (gamma |x_i|^2 + coef0)^degree is summed in a fixed
+ * order, and aa_distance_column returns sqrt(max(K_ii - 2 K_ij + K_jj, 0)) with exactly 0 at i = j.
+ * AA_ERR_ARG unless gamma > 0, coef0 >= 0 (so that K is positive semi-definite), degree >= 1, all finite.
+ * Single rank, float64 context. */
+int aa_set_poly_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma, double coef0,
+                         int degree);
 
 /* Driver-side preprocessing on the device (bin/run_hadisst_aa.py:133-146 weight_and_flatten_data,
  * :196-209 NaN-column removal and training / validation split; the same steps in
@@ -529,6 +538,13 @@ int aa_gpnh_residual_scores(aa_ctx *ctx, double *col_sse, double *row_sse, doubl
 int aa_set_rbf_reference(aa_ctx *ctx, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
                          double gamma);
 int aa_rbf_cross(aa_ctx *ctx, double *XW /* nullable: m x k copy of the result, row-major */);
+/* aa_set_poly_reference / aa_poly_cross: the same pair for the polynomial kernel of aa_set_poly_features,
+ *   XW[r][i] = sum_c (gamma y_r.x_c + coef0)^degree V[c][i] (k_poly_kv_mfma, the kernel of the fit).  The
+ *   diagonal aa_kernel_transform_cost needs is d_t = (gamma |y_t|^2 + coef0)^degree.  Argument checks as
+ *   aa_set_poly_features. */
+int aa_set_poly_reference(aa_ctx *ctx, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
+                          double gamma, double coef0, int degree);
+int aa_poly_cross(aa_ctx *ctx, double *XW /* nullable: m x k copy of the result, row-major */);
 int aa_kernel_transform_cost(aa_ctx *ctx, const double *A, const double *diag, double *cost);
 
 /* ------------------------------------------------------------ the two passes, on their own */
@@ -570,8 +586,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * bandwidth the memory system delivers; reference point for the roofline) with 4 / 8 / 16 / 8
  * loads in flight per thread on 4096 / 2048 / 1024 / 8192 blocks; 6 / 7 = the load pattern
  * of the row-local kernel alone, from the row-major matrix / from a tiled view of the same bytes;
- * 8 = K Z of the implicit RBF kernel (k_rbf_kv; a context after aa_set_rbf_features + aa_set_state),
- * 9 = the cross RBF product of aa_rbf_cross (a context after aa_set_rbf_reference),
+ * 8 = K Z of the implicit kernel (k_rbf_kv after aa_set_rbf_features, k_poly_kv_mfma after
+ * aa_set_poly_features; + aa_set_state),
+ * 9 = the cross product of aa_rbf_cross / aa_poly_cross (a context after aa_set_rbf_reference /
+ * aa_set_poly_reference),
  * 10 = the scores pass of aa_gpnh_residual_scores, 11 = the residual pass of aa_gpnh_residual_cost (both
  * without the copy to the host; a context after aa_gpnh_set_factors with dictionary and weights),
  * 12 = the flagged reduce-over-rows sequence (flags, gather, gated dense; no finish) on whatever the

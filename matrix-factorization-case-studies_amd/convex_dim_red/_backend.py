@@ -113,6 +113,8 @@ _SIGNATURES = {
     "aa_data_trace": (ctypes.c_int, [_vp, _dp]),
     "aa_set_linear_kernel": (ctypes.c_int, [_vp, ctypes.c_int]),
     "aa_set_rbf_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double]),
+    "aa_set_poly_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double,
+                                            ctypes.c_double, ctypes.c_int]),
     "aa_share_data": (ctypes.c_int, [_vp, _vp]),
     "aa_set_data_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long]),
     "aa_set_data_rows_affine": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _dp, _dp]),
@@ -149,6 +151,9 @@ _SIGNATURES = {
     "aa_set_rbf_reference": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _dp,
                                             ctypes.c_long, ctypes.c_double]),
     "aa_rbf_cross": (ctypes.c_int, [_vp, _dp]),
+    "aa_set_poly_reference": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, _dp,
+                                             ctypes.c_long, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "aa_poly_cross": (ctypes.c_int, [_vp, _dp]),
     "aa_kernel_transform_cost": (ctypes.c_int, [_vp, _dp, _dp, _dp]),
     "aa_gpnh_iterate": (ctypes.c_int, [_vp, ctypes.POINTER(GPNHParams), ctypes.POINTER(QPParams), _dp, _dp,
                                        ctypes.POINTER(IterStats)]),
@@ -400,7 +405,7 @@ class Context(object):
         # row shard of a distributed fit (sharded_context): with `global_view` the factor methods
         # below take and return arrays of the WHOLE problem and slice / gather this rank's rows
         self.global_view = False
-        self.implicit = False      # an implicit kernel (set_rbf_features): no stored matrix behind the products
+        self.implicit = False      # an implicit kernel (set_rbf_features, set_poly_features): no stored matrix behind the products
         self.row_lo = 0
         self.n_global = 0
 
@@ -534,6 +539,20 @@ class Context(object):
             raise ValueError("the implicit RBF kernel needs a float64 context")
         n, p = X.shape
         _check(self.lib.aa_set_rbf_features(self.h, _ptr(X), n, p, p, float(gamma)))
+        self.n, self.p = n, n
+        self.form = FORM_KERNEL
+        self.implicit = True
+
+    def set_poly_features(self, X, gamma, coef0, degree):
+        """The implicit polynomial kernel (gamma x_i.x_j + coef0)^degree of the rows of X as this context's
+        kernel matrix (never formed): kernel form of the algorithm, float64, products on the f64 matrix cores."""
+        X = _c64(X)
+        if X.ndim != 2:
+            raise ValueError("feature matrix must be 2-D")
+        if self.dtype_code != AA_F64:
+            raise ValueError("the implicit polynomial kernel needs a float64 context")
+        n, p = X.shape
+        _check(self.lib.aa_set_poly_features(self.h, _ptr(X), n, p, p, float(gamma), float(coef0), int(degree)))
         self.n, self.p = n, n
         self.form = FORM_KERNEL
         self.implicit = True
@@ -837,7 +856,8 @@ class Context(object):
                                                 ctypes.byref(tot) if total else None))
         return col, row, (tot.value if total else None)
 
-    # -- KernelAA.transform (aa_set_rbf_reference / aa_rbf_cross / aa_kernel_transform_cost)
+    # -- KernelAA.transform (aa_set_rbf_reference / aa_rbf_cross, aa_set_poly_reference / aa_poly_cross,
+    # aa_kernel_transform_cost)
     def set_rbf_reference(self, XS, V, gamma):
         """Reference set of the cross RBF product for the resident rows Y (set_data): the training rows
         ``XS`` (s x p) and ``V`` (s x k, = D' on them).  Sizes the factor buffers for k components."""
@@ -854,6 +874,23 @@ class Context(object):
         ``fetch`` also returned (m x k)."""
         out = np.empty((self.n, self.k)) if fetch else None
         _check(self.lib.aa_rbf_cross(self.h, None if out is None else _ptr(out)))
+        return out
+
+    def set_poly_reference(self, XS, V, gamma, coef0, degree):
+        """set_rbf_reference for the polynomial kernel (gamma y.x + coef0)^degree."""
+        XS, V = _c64(XS), _c64(V)
+        if XS.ndim != 2 or V.ndim != 2 or V.shape[0] != XS.shape[0]:
+            raise ValueError("reference rows (s x p) and V (s x k) expected")
+        s, p = XS.shape
+        k = V.shape[1]
+        _check(self.lib.aa_set_poly_reference(self.h, int(k), _ptr(XS), s, p, p, _ptr(V), k, float(gamma),
+                                              float(coef0), int(degree)))
+        self.k = k
+
+    def poly_cross(self, fetch=False):
+        """XW = poly(Y, XS) V into the QP's linear-term buffer, as rbf_cross."""
+        out = np.empty((self.n, self.k)) if fetch else None
+        _check(self.lib.aa_poly_cross(self.h, None if out is None else _ptr(out)))
         return out
 
     def kernel_transform_cost(self, A, diag=None):

@@ -588,6 +588,44 @@ class _BaseAA(object):
         return cost, n_iter, avg_time, cost_deltas
 
 
+def _poly_kernel_values(dots, gamma, coef0, degree):
+    """``(gamma dots + coef0)^degree`` by repeated multiplication, in the order of the device (poly_kappa)."""
+    base = gamma * np.asarray(dots, dtype=np.float64) + coef0
+    out = base.copy()
+    for _ in range(degree - 1):
+        out = out * base
+    return out
+
+
+def _implicit_kernel_spec(which, features, gamma, kwargs):
+    """The feature-space kernel a ``KernelAA.fit_transform`` call names, checked: None for the linear kernel
+    (explicit matrix or ``features=True``), else ``dict(form=, gamma=[, coef0=, degree=])`` with ``gamma``
+    None for the default.  Pops ``degree`` / ``coef0`` from ``kwargs``; every refusal is a ValueError."""
+    given = [name for name in ('degree', 'coef0') if name in kwargs]
+    degree = kwargs.pop('degree', 3)
+    coef0 = kwargs.pop('coef0', 1)
+    if which not in ('linear', 'rbf', 'poly'):
+        raise ValueError("kernel must be 'linear', 'rbf' or 'poly' (the last two with features=True); got %r"
+                         % (which,))
+    if which != 'poly' and given:
+        raise ValueError("%s belong%s to kernel='poly'; got kernel=%r"
+                         % (' and '.join(given), 's' if len(given) == 1 else '', which))
+    if which != 'linear' and not features:
+        raise ValueError("kernel=%r is computed from the features: pass them with features=True" % (which,))
+    if which == 'linear':
+        return None
+    if which == 'rbf':
+        return dict(form='rbf', gamma=gamma)
+    if isinstance(degree, (bool, np.bool_)) or not isinstance(degree, (int, np.integer)) or degree < 1:
+        raise ValueError("degree must be an integer >= 1; got %r" % (degree,))
+    if gamma is not None and not (np.isfinite(gamma) and gamma > 0):
+        raise ValueError("gamma must be positive and finite; got %r" % (gamma,))
+    if not (np.isfinite(coef0) and coef0 >= 0):
+        raise ValueError("coef0 must be >= 0 and finite (the polynomial kernel is then positive semi-definite); "
+                         "got %r" % (coef0,))
+    return dict(form='poly', gamma=None if gamma is None else float(gamma), coef0=float(coef0), degree=int(degree))
+
+
 class KernelAA(_BaseAA):
     """Kernel archetypal analysis on a given kernel matrix (reference :673-910).
 
@@ -608,11 +646,10 @@ class KernelAA(_BaseAA):
         features = kwargs.pop('features', False)
         which = kwargs.pop('implicit_kernel', 'linear')
         gamma = kwargs.pop('gamma', None)
-        if features and which == 'rbf':
-            return self._kernel_aa_rbf(kernel, gamma, dictionary, weights, alpha, update_dictionary,
-                                       update_weights, update_scale_factors, **kwargs)
-        if which not in ('linear', 'rbf') or (which == 'rbf' and not features):
-            raise ValueError("kernel must be 'linear' or 'rbf' (with features=True); got %r" % (which,))
+        spec = _implicit_kernel_spec(which, features, gamma, kwargs)     # ValueErrors before any device call
+        if spec is not None:
+            return self._kernel_aa_implicit(kernel, spec, dictionary, weights, alpha, update_dictionary,
+                                            update_weights, update_scale_factors, **kwargs)
         if features:
             # `kernel` is the n x p feature matrix X (or a DeviceData) of the linear
             # kernel K = X X', which is never formed -- n = 100 000 would be 80 GB.  Same
@@ -664,19 +701,22 @@ class KernelAA(_BaseAA):
         self._transform_state = state
         return out
 
-    def _kernel_aa_rbf(self, X, gamma, dictionary, weights, alpha, update_dictionary, update_weights,
-                       update_scale_factors, **kwargs):
-        """SURVEY 8(f4), the alternative it names: the RBF kernel ``exp(-gamma ||x_i - x_j||^2)`` of the
-        rows of ``X``, never formed -- the kernel form of the algorithm (reference :399-531, :673-910)
-        with every product ``C K`` / ``K Z`` computed as one fused distance + exp + multiply pass over
-        the features (aa_set_rbf_features).  Same conventions, initialisers and RNG order as the
-        explicit-kernel path: ``KernelAA(...).fit_transform(rbf_kernel(X, gamma=g))`` is what it
-        reproduces (tests/test_gpu_parity.py::test_kernel_aa_on_the_implicit_rbf_kernel)."""
+    def _kernel_aa_implicit(self, X, spec, dictionary, weights, alpha, update_dictionary, update_weights,
+                            update_scale_factors, **kwargs):
+        """SURVEY 8(f4), the alternative it names: a feature-space kernel of the rows of ``X``, never formed --
+        the RBF kernel ``exp(-gamma ||x_i - x_j||^2)`` or the polynomial kernel ``(gamma x_i.x_j + coef0)^degree``
+        (``spec``: _implicit_kernel_spec).  The kernel form of the algorithm (reference :399-531, :673-910)
+        with every product ``C K`` / ``K Z`` computed as one fused pass over the features
+        (aa_set_rbf_features, aa_set_poly_features).  Same conventions, initialisers and RNG order as the
+        explicit-kernel path: ``KernelAA(...).fit_transform(rbf_kernel(X, gamma=g))`` is what it reproduces
+        (tests/test_gpu_parity.py::test_kernel_aa_on_the_implicit_rbf_kernel, tests/test_gpu_kernel_poly.py)."""
         X = np.asarray(X, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError('Expected a feature matrix (n_samples x n_features); got shape %s' % (X.shape,))
-        if gamma is None:
-            gamma = 1.0 / X.shape[1]                      # scikit-learn's rbf_kernel default
+        spec = dict(spec)
+        if spec['gamma'] is None:
+            spec['gamma'] = 1.0 / X.shape[1]              # scikit-learn's default for both kernels
+        gamma = spec['gamma']
         n_samples = X.shape[0]
         if self.n_components is None:
             self.n_components = n_samples
@@ -684,7 +724,10 @@ class KernelAA(_BaseAA):
         self._check_hyper_parameters()
         shape_only = _ShapeOnly(n_samples)
         with _backend.Context(dtype=np.float64) as ctx:
-            ctx.set_rbf_features(X, gamma)
+            if spec['form'] == 'rbf':
+                ctx.set_rbf_features(X, gamma)
+            else:
+                ctx.set_poly_features(X, gamma, spec['coef0'], spec['degree'])
 
             def init_dictionary():
                 init = 'furthest_sum' if self.init is None else self.init
@@ -718,16 +761,22 @@ class KernelAA(_BaseAA):
         # transform() needs the training rows in the support of D = diag(alpha) C only
         D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
         support = np.flatnonzero(np.any(D != 0, axis=0))
-        self._transform_state = dict(form='rbf', n_samples=n_samples, n_features=X.shape[1], A=A, gamma=float(gamma),
-                                     support=support, support_rows=np.ascontiguousarray(X[support]),
+        self._transform_state = dict(form=spec['form'], n_samples=n_samples, n_features=X.shape[1], A=A,
+                                     gamma=float(gamma), support=support,
+                                     support_rows=np.ascontiguousarray(X[support]),
                                      support_dictionary=np.ascontiguousarray(D[:, support]))
+        if spec['form'] == 'poly':
+            self._transform_state.update(coef0=spec['coef0'], degree=spec['degree'])
         return out
 
     def fit_transform(self, data, dictionary=None, weights=None, alpha=None, **kwargs):
         """Factorise the kernel matrix ``data`` (n x n) and return the weights.  With
         ``features=True`` (an extension of the reference's signature) ``data`` is the n x p
         feature matrix of the linear kernel ``data.dot(data.T)`` -- or, with ``kernel='rbf',
-        gamma=g``, of the RBF kernel ``exp(-g ||x_i - x_j||^2)`` -- which is then never formed."""
+        gamma=g``, of the RBF kernel ``exp(-g ||x_i - x_j||^2)``, or, with ``kernel='poly', degree=3,
+        gamma=None, coef0=1`` (scikit-learn's ``polynomial_kernel`` and its defaults, ``gamma = 1 /
+        n_features``), of the polynomial kernel ``(gamma x_i.x_j + coef0)^degree`` -- which is then never
+        formed."""
         if 'kernel' in kwargs:                 # (`kernel` is also the name of _kernel_aa's first argument)
             kwargs['implicit_kernel'] = kwargs.pop('kernel')
         self.cost, self.n_iter, self.avg_time_per_iter, self.cost_deltas = self._kernel_aa(
@@ -751,7 +800,8 @@ class KernelAA(_BaseAA):
           * ``features=True``: the new feature rows Y (m x n_features) -- linear kernel: ``Y (D X)'`` as in
             ``ArchetypalAnalysis.transform`` and the cost ``0.5 ||Y - W D X||^2 / m``; ``kernel='rbf'``: the RBF
             values against the training rows in the support of D on the f64 matrix cores (aa_rbf_cross),
-            the m x n cross kernel never formed.
+            the m x n cross kernel never formed; ``kernel='poly'``: the same with the polynomial kernel
+            (aa_poly_cross) and ``kappa(y, y) = (gamma |y|^2 + coef0)^degree``.
         Returns ``(weights, cost)``; ``weights`` is also stored in ``self.weights``."""
         state = getattr(self, '_transform_state', None)
         if state is None:
@@ -790,10 +840,17 @@ class KernelAA(_BaseAA):
                 ctx.gpnh_set_factors(k, W=D.T, Z=initial_weights)          # kappa(Y, X) D'
             elif form == 'linear':
                 ctx.gpnh_set_factors(k, W=state['archetypes'].T, Z=initial_weights)   # Y (D X)'
-            else:
+            elif form == 'rbf':
                 ctx.set_rbf_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'])
                 ctx.rbf_cross()                                             # kappa(Y, X_S) D_S'
                 ctx.gpnh_set_factors(k, Z=initial_weights)
+            else:
+                ctx.set_poly_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'],
+                                       state['coef0'], state['degree'])
+                ctx.poly_cross()
+                ctx.gpnh_set_factors(k, Z=initial_weights)
+                diagonal = _poly_kernel_values((data * data).sum(axis=1), state['gamma'], state['coef0'],
+                                               state['degree'])           # kappa(y, y)
             ctx.gpnh_weights_update(A, **kw)
             self.weights = ctx.gpnh_get_weights()
             if form == 'linear':
@@ -806,8 +863,8 @@ class KernelAA(_BaseAA):
         """Reconstruction scores of ``data`` (m x n_features, host array or ``DeviceData``) for a model
         fitted with ``features=True`` on the linear kernel, whose archetypes ``D X`` live in data space:
         ``validation.Scores`` of ``data - weights (D X)`` (``weights`` None: the model's own, as after
-        ``fit_transform`` or ``transform``).  Models fitted on an explicit kernel matrix or on the RBF
-        kernel have no data-space residual (their cost is the kernel form's, see ``transform``)."""
+        ``fit_transform`` or ``transform``).  Models fitted on an explicit kernel matrix or on the RBF or
+        polynomial kernel have no data-space residual (their cost is the kernel form's, see ``transform``)."""
         state = getattr(self, '_transform_state', None)
         if state is None:
             raise NotFittedError('This KernelAA instance is not fitted yet: call fit or fit_transform '
@@ -815,7 +872,8 @@ class KernelAA(_BaseAA):
         if state['form'] != 'linear':
             raise ValueError("KernelAA.score: a model fitted on %s has no data-space residual; only "
                              "features=True on the linear kernel has (archetypes D X)"
-                             % ('an explicit kernel matrix' if state['form'] == 'kernel' else 'the RBF kernel'))
+                             % {'kernel': 'an explicit kernel matrix', 'rbf': 'the RBF kernel',
+                                'poly': 'the polynomial kernel'}[state['form']])
         data, weights = _score_arguments('KernelAA', data, state['n_features'], self.n_components, weights,
                                          self.weights)
         return _residual_scores(data, np.asarray(state['archetypes'], dtype=np.float64), weights, self.dtype)

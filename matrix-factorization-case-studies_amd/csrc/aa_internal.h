@@ -55,6 +55,22 @@ void set_error(const char *fmt, ...);
 
 inline long round_up(long v, long m) { return (v + m - 1) / m * m; }
 
+// The polynomial kernel kappa(x, y) = (gamma x.y + coef0)^degree as a function of the dot product s = x.y.
+// The only place the device evaluates it: the K V products, the distance column and the trace all call
+// this, so they agree to the rounding of s.  The power is degree - 1 multiplications in a fixed order
+// (no pow()): b = gamma s + coef0 (one fma), v = b, then v = v * b.
+struct PolyKernel {
+    double gamma, coef0;
+    int degree;
+};
+__device__ __forceinline__ double poly_kappa(double s, const PolyKernel pk)
+{
+    const double b = fma(pk.gamma, s, pk.coef0);
+    double v = b;
+    for (int i = 1; i < pk.degree; ++i) v *= b;
+    return v;
+}
+
 // zero rows allocated past n_pad in X and in every tall array, so software-pipelined
 // kernels may prefetch past the end of their row range without a guard
 #define AA_SLACK_ROWS 64
@@ -176,6 +192,7 @@ inline LoopJudge loop_judge(const aa_iter_params *ip, int it, double cost0, Iter
 }
 
 // ------------------------------------------------------------------ context
+enum { IMPLICIT_RBF = 1, IMPLICIT_POLY = 2 };   // Ctx::implicit_kernel, Ctx::cross_kind
 struct Comm;   // RCCL wrapper (comm.hip)
 struct P2P;    // one-shot peer-to-peer all-reduce over IPC-mapped buffers (comm.hip)
 
@@ -289,17 +306,23 @@ struct Ctx {
     DevBuf iterState, snapC, snapZ, snapAlpha; // aa_iterate: status record, factors at the stopping iteration
     DevBuf qpIters;                            // n ints: pass counts of the latest weights update
     DevBuf qpPerm;                             // n ints: sample order of the lane kernel
-    DevBuf feat, featNorm;                     // implicit RBF kernel: features [n_pad][feat_ld] (float64) and their squared norms
+    DevBuf feat, featNorm;                     // implicit kernels: features [n_pad][feat_ld] (float64) and their squared norms
     long feat_p = 0, feat_ld = 0;
-    int implicit_kernel = 0;                   // 0: none; 1: K_ij = exp(-rbf_gamma ||x_i - x_j||^2), never formed (aa_set_rbf_features)
+    // 0: none; IMPLICIT_RBF: K_ij = exp(-rbf_gamma ||x_i - x_j||^2) (aa_set_rbf_features); IMPLICIT_POLY:
+    // K_ij = poly_kappa(x_i.x_j, poly) (aa_set_poly_features).  Never formed.  Code that only asks whether a
+    // matrix is stored tests it for non-zero; what depends on the formula dispatches on the kind.
+    int implicit_kernel = 0;
     double rbf_gamma = 0.0;
-    // KernelAA.transform on the implicit RBF kernel (aa_set_rbf_reference): the reference rows X_S
-    // [cross_s_pad][p_pad], their squared norms, V = D' on them [cross_s_pad][KP], the squared norms of the
+    PolyKernel poly = {0.0, 0.0, 1};
+    // KernelAA.transform on an implicit kernel (aa_set_rbf_reference, aa_set_poly_reference): the reference rows
+    // X_S [cross_s_pad][p_pad], their squared norms (RBF), V = D' on them [cross_s_pad][KP], the squared norms of the
     // resident rows (also the linear kernel's diagonal), and the kernel-form cost's operands
     DevBuf crossX, crossNorm, crossV, rowNorm, xformCost;
     long cross_s = 0, cross_s_pad = 0;
     int cross_k = 0;
+    int cross_kind = 0;                        // IMPLICIT_RBF (cross_gamma) or IMPLICIT_POLY (cross_poly)
     double cross_gamma = 0.0;
+    PolyKernel cross_poly = {0.0, 0.0, 1};
     DevBuf scoreScratch;                       // aa_gpnh_residual_scores: [slab][p_pad] | [split][n_pad] partials, the sums, the total
     DevBuf fsScratch;                          // FurthestSum on the device: running sums, one distance column, state, alive flags
     bool qp_iters_valid = false;               // qpIters belongs to the current rows / state
@@ -415,6 +438,8 @@ int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double
 int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall);   // out = K V for the implicit kernel (tall in, tall out)
 int launch_rbf_norms(Ctx *c);
 int launch_rbf_cross(Ctx *c);      // Gr (XW) = rbf(Y, X_S) V for the reference set of aa_set_rbf_reference
+int launch_poly_cross(Ctx *c);     // Gr (XW) = poly(Y, X_S) V for the reference set of aa_set_poly_reference
+int launch_poly_trace(Ctx *c, double *trace_out_host);   // sum_i poly_kappa(|x_i|^2) from featNorm, fixed order
 int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double *nrm);   // nrm[r] = |F_r|^2
 // sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) over the resident rows (A: KP x KP device, d: device or null = 1;
 // part: (n + 255) / 256 + 1 doubles of scratch)

@@ -1724,9 +1724,12 @@ int launch_rbf_norms(Ctx *c)
     return AA_OK;
 }
 
+static int launch_poly_kv(Ctx *c, const double *V_tall, double *out_tall);
+
 int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall)
 {
-    AA_REQUIRE(c->implicit_kernel == 1 && c->feat.p, AA_ERR_STATE, "no implicit kernel set");
+    AA_REQUIRE(c->implicit_kernel && c->feat.p, AA_ERR_STATE, "no implicit kernel set");
+    if (c->implicit_kernel == IMPLICIT_POLY) return launch_poly_kv(c, V_tall, out_tall);
     const long rtiles = c->n_pad / 64, ntile = c->n_pad / 64;
     long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU
     if (nsplit > ntile) nsplit = ntile;
@@ -1784,12 +1787,29 @@ int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall)
 // m s (2 p + 2 KP) flop (p rounded up to 4, s to 64, KP = 32 / 64).  The 32-feature chunks are read from
 // the zero-padded rows (ld = p rounded up to 128); the MFMAs stop at p rounded up to 4.
 // ---------------------------------------------------------------------------
-template <int KP>
-__global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict__ Y, const double *__restrict__ ny,
-                                                        const double *__restrict__ XS, const double *__restrict__ ns,
-                                                        const double *__restrict__ V, long ld, int pk, long m,
-                                                        long m_pad, long s_tiles, long tiles_per_split, double gamma,
-                                                        double *__restrict__ out)
+// The element-wise step is a functor of the dot product s and the two squared norms; the tile body is shared
+// by the RBF cross product and the polynomial products below (k_poly_kv_mfma).
+struct RbfTile {
+    static constexpr bool needs_norms = true;
+    double gamma;
+    __device__ __forceinline__ double operator()(double s, double nyr, double nsc) const
+    {
+        const double d2 = fmax(nyr + nsc - 2.0 * s, 0.0);
+        return exp(-gamma * d2);
+    }
+};
+struct PolyTile {
+    static constexpr bool needs_norms = false;
+    PolyKernel pk;
+    __device__ __forceinline__ double operator()(double s, double, double) const { return poly_kappa(s, pk); }
+};
+
+template <int KP, class Fn>
+__device__ __forceinline__ void kernel_tile_product(const double *__restrict__ Y, const double *__restrict__ ny,
+                                                    const double *__restrict__ XS, const double *__restrict__ ns,
+                                                    const double *__restrict__ V, long ld, int pk, long m,
+                                                    long m_pad, long s_tiles, long tiles_per_split, const Fn fn,
+                                                    double *__restrict__ out)
 {
     constexpr int NT = KP / 16, TC = 32, LS = 34, VS = KP + 16;
     __shared__ __attribute__((aligned(16))) double ys[64 * LS];
@@ -1798,7 +1818,8 @@ __global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict
     const int t = threadIdx.x, wave = t >> 6, lane = t & 63;
     const int lc = lane & 15, lr = lane >> 4;
     const long r0 = (long)blockIdx.x * 64;                // grid.x = m_pad / 64 exactly
-    const double nyr = ny[r0 + 16 * wave + lc];           // |y_r|^2 of the row this lane's S values belong to
+    double nyr = 0.0;                                     // |y_r|^2 of the row this lane's S values belong to
+    if constexpr (Fn::needs_norms) nyr = ny[r0 + 16 * wave + lc];
     f64x4g o[NT];
 #pragma unroll
     for (int nt = 0; nt < NT; ++nt) o[nt] = (f64x4g){0.0, 0.0, 0.0, 0.0};
@@ -1839,8 +1860,9 @@ __global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int cl = 16 * mt + lr + 4 * q;      // column of the tile this lane's value belongs to
-                const double d2 = fmax(nyr + ns[c0 + cl] - 2.0 * sacc[mt][q], 0.0);
-                const double ev = exp(-gamma * d2);
+                double nsc = 0.0;
+                if constexpr (Fn::needs_norms) nsc = ns[c0 + cl];
+                const double ev = fn(sacc[mt][q], nyr, nsc);
 #pragma unroll
                 for (int nt = 0; nt < NT; ++nt)
                     o[nt] = __builtin_amdgcn_mfma_f64_16x16x4f64(ev, vs[cl * VS + 16 * nt + lc], o[nt], 0, 0, 0);
@@ -1856,9 +1878,118 @@ __global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict
         }
 }
 
+template <int KP>
+__global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict__ Y, const double *__restrict__ ny,
+                                                        const double *__restrict__ XS, const double *__restrict__ ns,
+                                                        const double *__restrict__ V, long ld, int pk, long m,
+                                                        long m_pad, long s_tiles, long tiles_per_split, double gamma,
+                                                        double *__restrict__ out)
+{
+    kernel_tile_product<KP>(Y, ny, XS, ns, V, ld, pk, m, m_pad, s_tiles, tiles_per_split, RbfTile{gamma}, out);
+}
+
+// ---------------------------------------------------------------------------
+// Implicit polynomial kernel kappa(x, y) = (gamma x.y + coef0)^degree (poly_kappa, aa_internal.h), K never
+// formed:   out[r][i] = sum_c kappa(y_r, x_c) V[c][i]
+// on the tile body above, both contractions on v_mfma_f64_16x16x4_f64 and kappa(S) formed in the registers S
+// was computed in.  One kernel serves both products:
+//   * the fit (launch_implicit_kv): Y = X_S = the features of aa_set_poly_features ([n_pad][feat_ld], feat_ld =
+//     p rounded up to 32, so that the last 32-feature chunk of a row stays inside the row; zero padded),
+//     V = C' or Z.  Rows and columns are the same set and the diagonal is simply what the tile computes;
+//   * KernelAA.transform (launch_poly_cross): Y = the resident rows, X_S = the reference rows, ld = p_pad.
+// No norms are read.  Padding columns have zero rows of V (a padding column's kappa is coef0^degree, times
+// zero); padding rows are written as zeros.  n^2 (2 p + 2 KP) flop (p rounded up to 4, n to 64).
+// Per block: 64 x 34 doubles of Y and of X_S and 64 x (KP + 16) of V in LDS (58 KB at KP = 32, 74 KB at 64);
+// per lane 16 accumulators of S and KP / 4 of the output (180 / 184 VGPRs, no spills).
+// ---------------------------------------------------------------------------
+template <int KP>
+__global__ __launch_bounds__(256) void k_poly_kv_mfma(const double *__restrict__ Y, const double *__restrict__ XS,
+                                                      const double *__restrict__ V, long ld, int pk, long m,
+                                                      long m_pad, long s_tiles, long tiles_per_split,
+                                                      const PolyKernel poly, double *__restrict__ out)
+{
+    kernel_tile_product<KP>(Y, nullptr, XS, nullptr, V, ld, pk, m, m_pad, s_tiles, tiles_per_split, PolyTile{poly},
+                            out);
+}
+
+// out_tall = kappa(Y, X_S) V: rows [0, m) of Y (m_pad a multiple of 64), s_pad / 64 column tiles split over
+// grid.y as in launch_implicit_kv, the splits summed in a fixed order
+static int launch_poly_product(Ctx *c, const double *Y, const double *XS, const double *V, long ld, long p, long m,
+                               long m_pad, long s_pad, const PolyKernel &poly, double *out_tall)
+{
+    const long rtiles = m_pad / 64, stiles = s_pad / 64;
+    long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU
+    if (nsplit > stiles) nsplit = stiles;
+    if (nsplit < 1) nsplit = 1;
+    const long tps = (stiles + nsplit - 1) / nsplit;
+    nsplit = (stiles + tps - 1) / tps;
+    double *dst = out_tall;
+    if (nsplit > 1) {
+        AA_CHECK(c->rlPartial.alloc((size_t)nsplit * m_pad * c->KP * sizeof(double)));
+        dst = c->rlPartial.as<double>();
+    }
+    const dim3 grid((unsigned)rtiles, (unsigned)nsplit);
+    if (c->KP == 32)
+        hipLaunchKernelGGL(k_poly_kv_mfma<32>, grid, dim3(256), 0, c->stream, Y, XS, V, ld, (int)round_up(p, 4), m,
+                           m_pad, stiles, tps, poly, dst);
+    else
+        hipLaunchKernelGGL(k_poly_kv_mfma<64>, grid, dim3(256), 0, c->stream, Y, XS, V, ld, (int)round_up(p, 4), m,
+                           m_pad, stiles, tps, poly, dst);
+    if (nsplit > 1) {
+        const long elems = m_pad * c->KP;
+        hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
+                           (const double *)dst, elems, (int)nsplit, out_tall);
+    }
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+static int launch_poly_kv(Ctx *c, const double *V_tall, double *out_tall)
+{
+    return launch_poly_product(c, c->feat.as<double>(), c->feat.as<double>(), V_tall, c->feat_ld, c->feat_p, c->n,
+                               c->n_pad, c->n_pad, c->poly, out_tall);
+}
+
+int launch_poly_cross(Ctx *c)
+{
+    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_POLY && c->dtype == AA_F64,
+               AA_ERR_STATE, "no polynomial reference set");
+    return launch_poly_product(c, c->X.as<double>(), c->crossX.as<double>(), c->crossV.as<double>(), c->p_pad, c->p,
+                               c->n, c->n_pad, c->cross_s_pad, c->cross_poly, c->Gr.as<double>());
+}
+
+// tr K = sum_i kappa(x_i, x_i) from the squared row norms: one block, each thread a strided sum, then a tree
+// over the threads -- the same order, hence the same bits, on every call
+__global__ __launch_bounds__(256) void k_poly_trace(const double *__restrict__ nrm, long n, const PolyKernel poly,
+                                                    double *__restrict__ out)
+{
+    __shared__ double part[256];
+    double s = 0.0;
+    for (long r = threadIdx.x; r < n; r += 256) s += poly_kappa(nrm[r], poly);
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) out[0] = part[0];
+}
+
+int launch_poly_trace(Ctx *c, double *trace_out_host)
+{
+    AA_REQUIRE(c->implicit_kernel == IMPLICIT_POLY && c->featNorm.p, AA_ERR_STATE, "no implicit polynomial kernel set");
+    double *out = c->featNorm.as<double>() + c->n_pad;   // the first slack entry behind the norms (never read as one)
+    hipLaunchKernelGGL(k_poly_trace, dim3(1), dim3(256), 0, c->stream, (const double *)c->featNorm.as<double>(), c->n,
+                       c->poly, out);
+    AA_CHECK_HIP(hipGetLastError());
+    AA_CHECK_HIP(ctx_memcpy(c, trace_out_host, out, sizeof(double), hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
 int launch_rbf_cross(Ctx *c)
 {
-    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->dtype == AA_F64, AA_ERR_STATE, "no reference set");
+    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_RBF && c->dtype == AA_F64, AA_ERR_STATE,
+               "no RBF reference set");
     const long rtiles = c->n_pad / 64, stiles = c->cross_s_pad / 64;
     long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU, as launch_implicit_kv
     if (nsplit > stiles) nsplit = stiles;

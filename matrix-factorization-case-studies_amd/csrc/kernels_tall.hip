@@ -2055,6 +2055,32 @@ __global__ __launch_bounds__(256) void k_distance_rbf(const double *__restrict__
     if (lane == 0) d[r] = sqrt(fmax(2.0 - 2.0 * exp(-gamma * s), 0.0));
 }
 
+// implicit polynomial kernel: d[i] = sqrt(max(K_ii - 2 K_ij + K_jj, 0)) with K = poly_kappa of the three dot
+// products, one wave per row.  For i == j the three sums are the same operations on the same numbers, so
+// K_ii = K_ij = K_jj bit for bit and d[j] is exactly 0.  Near zero the square root amplifies the rounding
+// of K: an error e in K_ii - 2 K_ij + K_jj becomes sqrt(e) in d.
+__global__ __launch_bounds__(256) void k_distance_poly(const double *__restrict__ F, long ldf, int pf, long n, long j,
+                                                       const PolyKernel poly, double *__restrict__ d)
+{
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + wave;
+    if (r >= n) return;
+    double sii = 0.0, sij = 0.0, sjj = 0.0;
+    for (int q = lane; q < pf; q += 64) {
+        const double a = F[r * ldf + q], b = F[j * ldf + q];
+        sii = fma(a, a, sii);
+        sij = fma(a, b, sij);
+        sjj = fma(b, b, sjj);
+    }
+    sii = wave_sum(sii);
+    sij = wave_sum(sij);
+    sjj = wave_sum(sjj);
+    if (lane == 0) {
+        const double kii = poly_kappa(sii, poly), kij = poly_kappa(sij, poly), kjj = poly_kappa(sjj, poly);
+        d[r] = sqrt(fmax(kii - 2.0 * kij + kjj, 0.0));
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_distance_kernel(const T *__restrict__ K, long ldx, long n,
                                                          long j, double *__restrict__ d)
@@ -3989,7 +4015,10 @@ int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double
     (void)owner_has_row;
     (void)xj_host;
     double *dd = c->tmpTall.as<double>();
-    if (c->implicit_kernel) {
+    if (c->implicit_kernel == IMPLICIT_POLY) {
+        hipLaunchKernelGGL(k_distance_poly, dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
+                           (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->poly, dd);
+    } else if (c->implicit_kernel) {
         hipLaunchKernelGGL(k_distance_rbf, dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
                            (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->rbf_gamma, dd);
     } else if (c->form == AA_FORM_DATA) {

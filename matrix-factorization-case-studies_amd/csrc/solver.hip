@@ -189,8 +189,13 @@ static int device_cost(Ctx *c, double *cost)
 static int ensure_trace(Ctx *c)
 {
     if (c->have_trace) return AA_OK;
-    if (c->implicit_kernel) {                    // RBF: every diagonal entry is exp(0) = 1
+    if (c->implicit_kernel == IMPLICIT_RBF) {    // every diagonal entry is exp(0) = 1
         c->trace = (double)c->n_global;
+        c->have_trace = true;
+        return AA_OK;
+    }
+    if (c->implicit_kernel == IMPLICIT_POLY) {   // sum_i (gamma |x_i|^2 + coef0)^degree
+        AA_CHECK(launch_poly_trace(c, &c->trace));
         c->have_trace = true;
         return AA_OK;
     }
@@ -675,18 +680,14 @@ int aa_set_linear_kernel(aa_ctx *h, int on)
     return AA_OK;
 }
 
-int aa_set_rbf_features(aa_ctx *h, const double *X, long n, long p, long ld, double gamma)
+// the features of an implicit kernel: the kernel form of the algorithm on a virtual n x n matrix; feat_ld: the
+// leading dimension of the zero-padded feature buffer, chosen by the kernels that read it
+static int set_implicit_features(Ctx *c, const double *X, long n, long p, long ld, long feat_ld, int kind)
 {
-    AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
-    AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
     AA_CHECK_HIP(hipSetDevice(c->device));
     c->form = AA_FORM_KERNEL;                    // the kernel form of the algorithm (/k conventions, tr K)
     c->linear_kernel = false;
-    c->implicit_kernel = 1;
-    c->rbf_gamma = gamma;
+    c->implicit_kernel = kind;
     c->n = n;
     c->p = n;                                    // the (virtual) kernel matrix is n x n
     c->n_pad = round_up(n, 128);
@@ -695,7 +696,7 @@ int aa_set_rbf_features(aa_ctx *h, const double *X, long n, long p, long ld, dou
     c->row_offset = 0;
     c->X.release();                              // nothing stands in for K
     c->feat_p = p;
-    c->feat_ld = round_up(p, 2);
+    c->feat_ld = feat_ld;
     AA_CHECK(c->feat.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->feat_ld * sizeof(double)));
     AA_CHECK_HIP(ctx_memset(c, c->feat.p, 0, c->feat.bytes));
     AA_CHECK_HIP(ctx_memcpy2d(c, c->feat.p, (size_t)c->feat_ld * sizeof(double), X, (size_t)ld * sizeof(double),
@@ -709,6 +710,38 @@ int aa_set_rbf_features(aa_ctx *h, const double *X, long n, long p, long ld, dou
     c->have_state = false;
     c->grams_valid = false;
     return AA_OK;
+}
+
+int aa_set_rbf_features(aa_ctx *h, const double *X, long n, long p, long ld, double gamma)
+{
+    AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
+    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
+    c->rbf_gamma = gamma;
+    return set_implicit_features(c, X, n, p, ld, round_up(p, 2), IMPLICIT_RBF);
+}
+
+// gamma > 0, coef0 >= 0 (K positive semi-definite), degree >= 1, all finite (a NaN fails every comparison)
+static bool poly_params_ok(double gamma, double coef0, int degree)
+{
+    return gamma > 0.0 && gamma < 1e300 && coef0 >= 0.0 && coef0 < 1e300 && degree >= 1;
+}
+
+int aa_set_poly_features(aa_ctx *h, const double *X, long n, long p, long ld, double gamma, double coef0, int degree)
+{
+    AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
+    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
+               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
+               degree);
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit polynomial kernel is single-rank");
+    AA_REQUIRE(c->dtype == AA_F64, AA_ERR_STATE, "the implicit polynomial kernel needs a float64 context");
+    c->poly = PolyKernel{gamma, coef0, degree};
+    // k_poly_kv_mfma reads rows in chunks of 32 features
+    return set_implicit_features(c, X, n, p, ld, round_up(p, 32), IMPLICIT_POLY);
 }
 
 int aa_comm_get_unique_id(void *id128) { return comm_unique_id(id128); }
@@ -2211,17 +2244,9 @@ int aa_gpnh_residual_scores(aa_ctx *h, double *col_sse, double *row_sse, double 
 }
 
 // ------------------------------------------------------------------ KernelAA.transform
-int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
-                         double gamma)
+// the reference rows X_S and V = D' on them for the cross product against the resident rows (both kinds)
+static int set_cross_reference(Ctx *c, int k, const double *XS, long s, long p, long ld, const double *V, long ldv)
 {
-    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
-               "aa_set_rbf_reference needs the new samples as a float64 data matrix (aa_set_data)");
-    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
-               s, p, c->p, ld, ldv);
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
     const long s_pad = round_up(s, 64);
@@ -2234,15 +2259,32 @@ int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, lon
         for (int i = 0; i < k; ++i) v[(size_t)j * c->KP + i] = V[j * ldv + i];
     AA_CHECK(c->crossV.alloc(v.size() * sizeof(double)));
     AA_CHECK_HIP(ctx_memcpy(c, c->crossV.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
-    AA_CHECK(c->crossNorm.alloc((size_t)s_pad * sizeof(double)));
-    AA_CHECK(launch_row_norms(c, c->crossX.as<double>(), c->p_pad, p, s_pad, c->crossNorm.as<double>()));
-    AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
-    AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, p, c->n_pad, c->rowNorm.as<double>()));
     c->cross_s = s;
     c->cross_s_pad = s_pad;
     c->cross_k = k;
-    c->cross_gamma = gamma;
     c->gpnh_valid = false;
+    return AA_OK;
+}
+
+int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
+                         double gamma)
+{
+    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
+               "aa_set_rbf_reference needs the new samples as a float64 data matrix (aa_set_data)");
+    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
+               s, p, c->p, ld, ldv);
+    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    c->cross_s = 0;
+    AA_CHECK(set_cross_reference(c, k, XS, s, p, ld, V, ldv));
+    AA_CHECK(c->crossNorm.alloc((size_t)c->cross_s_pad * sizeof(double)));
+    AA_CHECK(launch_row_norms(c, c->crossX.as<double>(), c->p_pad, p, c->cross_s_pad, c->crossNorm.as<double>()));
+    AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
+    AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, p, c->n_pad, c->rowNorm.as<double>()));
+    c->cross_kind = IMPLICIT_RBF;
+    c->cross_gamma = gamma;
     return AA_OK;
 }
 
@@ -2250,10 +2292,45 @@ int aa_rbf_cross(aa_ctx *h, double *XW)
 {
     AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
     Ctx *c = &h->c;
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE,
-               "aa_set_rbf_reference first");
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k &&
+                   c->cross_kind == IMPLICIT_RBF,
+               AA_ERR_STATE, "aa_set_rbf_reference first");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(launch_rbf_cross(c));
+    c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
+    if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
+    return AA_OK;
+}
+
+int aa_set_poly_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
+                          double gamma, double coef0, int degree)
+{
+    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit polynomial kernel is single-rank");
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
+               "aa_set_poly_reference needs the new samples as a float64 data matrix (aa_set_data)");
+    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
+               s, p, c->p, ld, ldv);
+    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
+               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
+               degree);
+    c->cross_s = 0;
+    AA_CHECK(set_cross_reference(c, k, XS, s, p, ld, V, ldv));
+    c->cross_kind = IMPLICIT_POLY;
+    c->cross_poly = PolyKernel{gamma, coef0, degree};
+    return AA_OK;
+}
+
+int aa_poly_cross(aa_ctx *h, double *XW)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k &&
+                   c->cross_kind == IMPLICIT_POLY,
+               AA_ERR_STATE, "aa_set_poly_reference first");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(launch_poly_cross(c));
     c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
     if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
     return AA_OK;
@@ -2520,9 +2597,10 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     AA_REQUIRE(h && ms_avg && reps >= 1, AA_ERR_ARG, "bad arguments");
     Ctx *c = &h->c;
     if (which == 8)
-        AA_REQUIRE(c->implicit_kernel && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit RBF kernel with state");
+        AA_REQUIRE(c->implicit_kernel && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit kernel with state");
     else if (which == 9)
-        AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE, "aa_time_kernel 9: aa_set_rbf_reference first");
+        AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE,
+                   "aa_time_kernel 9: aa_set_rbf_reference or aa_set_poly_reference first");
     else if (which == 10 || which == 11)
         AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->have_state && c->gpnh_valid &&
                        c->world == 1 && !c->force_comm,
@@ -2553,7 +2631,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
             else if (which == 8)
                 rc = launch_implicit_kv(c, c->Zt.as<double>(), c->H.as<double>());
             else if (which == 9)
-                rc = launch_rbf_cross(c);
+                rc = c->cross_kind == IMPLICIT_POLY ? launch_poly_cross(c) : launch_rbf_cross(c);
             else if (which == 10)
                 rc = launch_residual_scores(c, nullptr, nullptr, nullptr, false);
             else if (which == 11)
