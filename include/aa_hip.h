@@ -307,6 +307,17 @@ int aa_data_column_moments(aa_ctx *ctx, double *mean, double *var);
 int aa_set_data_rows_affine(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, const double *shift,
                             const double *scale);
 
+/* Row gather on the device (seasonal subsets, k-fold splits, bootstrap resamples of a resident block, and the
+ * support rows KernelAA.transform keeps, `X[support]`): rows idx[0..n) of owner's resident DATA matrix, in any
+ * order and with duplicates, become ctx's data matrix exactly as after aa_set_data on the same values -- a gather
+ * kernel (csrc/kernels_tall.hip: k_gather_rows) into a zero-filled allocation of ctx's own,
+ * (n_pad + slack rows) x p_pad like aa_set_data_rows; the owner may be destroyed afterwards.  idx == NULL: rows
+ * 0..n-1 in order (n <= owner's n).  Preconditions of aa_set_data_rows (same device, data form, both single rank, no
+ * implicit kernel behind the owner); the data types are equal, or the owner is float32 and ctx float64 -- an exact
+ * widening, the only mixed case.  EVERY index is checked on the host against [0, owner's n) before anything is
+ * launched or released: a bad one is AA_ERR_ARG, the message names the first, and ctx keeps the data it had. */
+int aa_set_data_take(aa_ctx *ctx, const aa_ctx *owner, const long *idx, long n);
+
 /* KernelAA on the implicit linear kernel K = X X' (SURVEY 8(f4)): with `on` != 0 the resident
  * DATA matrix X (n x p) stands in for the n x n kernel matrix of _iterate_kernel_aa
  * (archetypal_analysis.py:399-531), which is never formed: every product with K runs as two
@@ -331,6 +342,14 @@ int aa_set_rbf_features(aa_ctx *ctx, const double *X, long n, long p, long ld, d
  * Single rank, float64 context. */
 int aa_set_poly_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma, double coef0,
                          int degree);
+/* aa_set_rbf_features / aa_set_poly_features with the features taken from owner's resident DATA matrix instead of
+ * a host array: the zero-padded float64 feature buffer is filled on the device (csrc/kernels_tall.hip:
+ * k_features_from_data, which reads owner's element type and leading dimension; float32 widens exactly), so it
+ * holds the bits the host entry points give for owner's aa_get_data, and everything downstream is unchanged.
+ * owner (another context on the same device, data form with a stored matrix, single rank) is only read and may be
+ * destroyed afterwards.  Parameter checks and refusals of the host entry points (float64 ctx, single rank). */
+int aa_set_rbf_features_resident(aa_ctx *ctx, const aa_ctx *owner, double gamma);
+int aa_set_poly_features_resident(aa_ctx *ctx, const aa_ctx *owner, double gamma, double coef0, int degree);
 
 /* Driver-side preprocessing on the device (bin/run_hadisst_aa.py:133-146 weight_and_flatten_data,
  * :196-209 NaN-column removal and training / validation split; the same steps in
@@ -546,6 +565,26 @@ int aa_set_poly_reference(aa_ctx *ctx, int k, const double *XS, long s, long p, 
                           double gamma, double coef0, int degree);
 int aa_poly_cross(aa_ctx *ctx, double *XW /* nullable: m x k copy of the result, row-major */);
 int aa_kernel_transform_cost(aa_ctx *ctx, const double *A, const double *diag, double *cost);
+/* aa_kernel_sample_residuals: the terms of that cost per sample (csrc/kernels_tall.hip:
+ *   k_kernel_sample_residuals, A in LDS): r_t = d_t - 2 w_t.XW_t + w_t' A w_t for every resident sample t, the
+ *   squared feature-space distance of kappa(y_t, .) from its reconstruction; XW is the linear-term buffer the cross
+ *   product or aa_gpnh_set_factors left behind.  sample_sse (n values, nullable) receives r_t -- not clamped, it
+ *   may be negative at rounding level --, diag_out (n values, nullable) d_t, sums[0] = sum_t r_t and sums[1] =
+ *   sum_t d_t, both reduced in a fixed order (a tree per block of 256 samples, the block partials in block order,
+ *   no atomics: two calls return the same bits).  diag_kind says where d_t comes from:
+ *     AA_DIAG_GIVEN   diag[t], a host vector of n values (explicit kernels);
+ *     AA_DIAG_ONES    1 (RBF);
+ *     AA_DIAG_POLY    (gamma |y_t|^2 + coef0)^degree with the parameters of aa_set_poly_reference, evaluated by
+ *                     the device's one polynomial function on row norms computed on the device;
+ *     AA_DIAG_LINEAR  |y_t|^2.
+ *   `diag` must be NULL unless diag_kind is AA_DIAG_GIVEN.  POLY and LINEAR read the stored float64 data matrix
+ *   (AA_ERR_STATE otherwise).  Preconditions of aa_kernel_transform_cost, which stays what it is. */
+#define AA_DIAG_GIVEN  0
+#define AA_DIAG_ONES   1
+#define AA_DIAG_POLY   2
+#define AA_DIAG_LINEAR 3
+int aa_kernel_sample_residuals(aa_ctx *ctx, const double *A, int diag_kind, const double *diag, double *sample_sse,
+                               double *diag_out, double sums[2]);
 
 /* ------------------------------------------------------------ the two passes, on their own */
 /* The two contractions against the resident matrix that every update is built from, callable
@@ -594,7 +633,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * without the copy to the host; a context after aa_gpnh_set_factors with dictionary and weights),
  * 12 = the flagged reduce-over-rows sequence (flags, gather, gated dense; no finish) on whatever the
  * direction buffer holds (after aa_pass_reduce_rows_flagged or an update; with reduce_sparse = 0 the
- * dense kernel on the same operand).
+ * dense kernel on the same operand),
+ * 13 = the row gather of aa_set_data_take on the context's own matrix (a seeded permutation of all its rows, into a
+ * scratch copy), 14 = the feature build of aa_set_poly_features_resident from it (into a scratch buffer); both
+ * need only a stored data matrix.
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

@@ -16,10 +16,10 @@ from .stochastic_matrices import left_stochastic_matrix, right_stochastic_matrix
 from ._backend import release_device_cache
 from .preprocessing import ColumnScaling, ColumnStats, DeviceData, weight_and_flatten_on_device
 from .restarts import fit_restarts
-from .validation import Scores, time_series_cross_validate, time_series_folds
+from .validation import KernelScores, Scores, time_series_cross_validate, time_series_folds
 
 __all__ = ["ArchetypalAnalysis", "KernelAA", "GPNHConvexCoding", "furthest_sum",
            "gap_statistic", "simplex_project_rows", "simplex_project_columns", "spg",
            "left_stochastic_matrix", "right_stochastic_matrix", "release_device_cache",
            "DeviceData", "weight_and_flatten_on_device", "fit_restarts",
-           "Scores", "time_series_cross_validate", "time_series_folds", "ColumnStats", "ColumnScaling"]
+           "Scores", "KernelScores", "time_series_cross_validate", "time_series_folds", "ColumnStats", "ColumnScaling"]

@@ -18,6 +18,7 @@ import numpy as np
 AA_F32, AA_F64 = 0, 1
 FORM_DATA, FORM_KERNEL = 0, 1
 MAX_K = 64
+DIAG_KINDS = ("given", "ones", "poly", "linear")     # AA_DIAG_*: where aa_kernel_sample_residuals takes kappa(y, y) from
 
 SPG_FLAG_CONVERGED = 1
 SPG_FLAG_LAMBDA_MIN = 2
@@ -115,6 +116,10 @@ _SIGNATURES = {
     "aa_set_rbf_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double]),
     "aa_set_poly_features": (ctypes.c_int, [_vp, _dp, ctypes.c_long, ctypes.c_long, ctypes.c_long, ctypes.c_double,
                                             ctypes.c_double, ctypes.c_int]),
+    "aa_set_rbf_features_resident": (ctypes.c_int, [_vp, _vp, ctypes.c_double]),
+    "aa_set_poly_features_resident": (ctypes.c_int, [_vp, _vp, ctypes.c_double, ctypes.c_double, ctypes.c_int]),
+    "aa_set_data_take": (ctypes.c_int, [_vp, _vp, ctypes.POINTER(ctypes.c_long), ctypes.c_long]),
+    "aa_kernel_sample_residuals": (ctypes.c_int, [_vp, _dp, ctypes.c_int, _dp, _dp, _dp, _dp]),
     "aa_share_data": (ctypes.c_int, [_vp, _vp]),
     "aa_set_data_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long]),
     "aa_set_data_rows_affine": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _dp, _dp]),
@@ -521,6 +526,43 @@ class Context(object):
         self.n, self.p = int(n), owner.p
         self.row_lo, self.n_global = 0, int(n)
 
+    def set_data_take(self, owner, indices=None):
+        """Rows ``indices`` (any order, duplicates allowed; None: all rows in order) of ``owner``'s resident data
+        matrix become this context's data matrix (aa_set_data_take): a device gather that owns its memory.  A
+        float32 owner widens exactly into a float64 context.  The library checks every index on the host before
+        it launches anything (error -1, this context keeps its data)."""
+        if indices is None:
+            n, ptr = owner.n, None
+        else:
+            idx = np.ascontiguousarray(indices, dtype=np.int64)
+            if idx.ndim != 1:
+                raise ValueError("a 1-D index array expected; got shape %r" % (idx.shape,))
+            n, ptr = idx.shape[0], idx.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
+        _check(self.lib.aa_set_data_take(self.h, owner.h, ptr, int(n)))
+        self.n, self.p = int(n), owner.p
+        self.row_lo, self.n_global = 0, int(n)
+
+    def _set_features_resident(self, owner, call, what):
+        if self.dtype_code != AA_F64:
+            raise ValueError("the implicit %s kernel needs a float64 context" % what)
+        _check(call())
+        self.n, self.p = owner.n, owner.n
+        self.form = FORM_KERNEL
+        self.implicit = True
+
+    def set_rbf_features_resident(self, owner, gamma):
+        """set_rbf_features with the rows of ``owner``'s resident data matrix as the features
+        (aa_set_rbf_features_resident): nothing crosses the bus; ``owner`` is only read."""
+        self._set_features_resident(
+            owner, lambda: self.lib.aa_set_rbf_features_resident(self.h, owner.h, float(gamma)), "RBF")
+
+    def set_poly_features_resident(self, owner, gamma, coef0, degree):
+        """set_poly_features with the rows of ``owner``'s resident data matrix as the features
+        (aa_set_poly_features_resident)."""
+        self._set_features_resident(
+            owner, lambda: self.lib.aa_set_poly_features_resident(self.h, owner.h, float(gamma), float(coef0),
+                                                                  int(degree)), "polynomial")
+
     def data_column_moments(self, mean=True, var=True):
         """``(mean[p], var[p])`` of the columns of the resident data matrix (aa_data_column_moments): two
         float64 sweeps, ``var`` the mean squared deviation (ddof 0); an output that is not asked for is None."""
@@ -901,6 +943,23 @@ class Context(object):
         c = ctypes.c_double(0)
         _check(self.lib.aa_kernel_transform_cost(self.h, _ptr(A), None if d is None else _ptr(d), ctypes.byref(c)))
         return c.value
+
+    def kernel_sample_residuals(self, A, kind, diag=None, samples=True, diagonal=True):
+        """The terms of kernel_transform_cost per sample (aa_kernel_sample_residuals):
+        ``(r[n], d[n], sum r, sum d)`` with r_t = d_t - 2 z_t.XW_t + z_t' A z_t; ``kind`` one of ``DIAG_KINDS``
+        ('given': d = ``diag``; 'ones'; 'poly': from the reference set's parameters; 'linear': |y_t|^2, both from
+        row norms computed on the device).  A vector that is not asked for is None."""
+        A = _c64(A)
+        d = None if diag is None else _c64(diag)
+        if d is not None and d.shape != (self.n,):
+            raise ValueError("diag: %d values expected, one per resident row; got shape %r" % (self.n, d.shape))
+        r = np.empty(self.n) if samples else None
+        dout = np.empty(self.n) if diagonal else None
+        sums = np.zeros(2)
+        _check(self.lib.aa_kernel_sample_residuals(self.h, _ptr(A), DIAG_KINDS.index(kind),
+                                                   None if d is None else _ptr(d), None if r is None else _ptr(r),
+                                                   None if dout is None else _ptr(dout), _ptr(sums)))
+        return r, dout, float(sums[0]), float(sums[1])
 
     def spg_scalars(self):
         """Scalar state of the latest dictionary SPG iteration (aa_get_spg_scalars), as a dict."""

@@ -17,6 +17,7 @@ and the trace is ||X||_F^2.
 """
 from __future__ import absolute_import, division, print_function
 
+import contextlib
 import numbers
 import time
 import warnings
@@ -31,7 +32,7 @@ from .preprocessing import DeviceData
 from .simplex_projection import simplex_project_rows  # noqa: F401  (reference re-export)
 from .spg import quad_simplex_spg, spg  # noqa: F401
 from .stochastic_matrices import right_stochastic_matrix
-from .validation import _residual_scores, _score_arguments
+from .validation import _kernel_scores_from_sums, _residual_scores, _score_arguments
 from .validation_utils import check_array_shape, check_stochastic_matrix
 
 INTEGER_TYPES = (numbers.Integral, np.integer)
@@ -597,6 +598,24 @@ def _poly_kernel_values(dots, gamma, coef0, degree):
     return out
 
 
+@contextlib.contextmanager
+def _float64_rows(data):
+    """A float64 context whose data matrix holds the rows of ``data``, which the kernel-form entry points need:
+    a host array is uploaded, a float64 ``DeviceData`` lends its own context (as ``score`` borrows it), a float32
+    one is widened on the device into a copy that lives as long as the ``with`` block (``take``, exact)."""
+    if not isinstance(data, DeviceData):
+        with _backend.Context(dtype=np.float64) as ctx:
+            ctx.set_data(data, form=_backend.FORM_DATA)
+            yield ctx
+    elif data.dtype == np.float64:
+        with data.borrow() as ctx:
+            yield ctx
+    else:
+        with data.take(None, dtype=np.float64) as wide:
+            with wide.borrow() as ctx:
+                yield ctx
+
+
 def _implicit_kernel_spec(which, features, gamma, kwargs):
     """The feature-space kernel a ``KernelAA.fit_transform`` call names, checked: None for the linear kernel
     (explicit matrix or ``features=True``), else ``dict(form=, gamma=[, coef0=, degree=])`` with ``gamma``
@@ -710,7 +729,11 @@ class KernelAA(_BaseAA):
         (aa_set_rbf_features, aa_set_poly_features).  Same conventions, initialisers and RNG order as the
         explicit-kernel path: ``KernelAA(...).fit_transform(rbf_kernel(X, gamma=g))`` is what it reproduces
         (tests/test_gpu_parity.py::test_kernel_aa_on_the_implicit_rbf_kernel, tests/test_gpu_kernel_poly.py)."""
-        X = np.asarray(X, dtype=np.float64)
+        # a DeviceData stays where it is: the feature buffer is filled from the resident block
+        # (aa_set_*_features_resident) and only the few support rows transform() keeps come back
+        on_device = isinstance(X, DeviceData)
+        if not on_device:
+            X = np.asarray(X, dtype=np.float64)
         if X.ndim != 2:
             raise ValueError('Expected a feature matrix (n_samples x n_features); got shape %s' % (X.shape,))
         spec = dict(spec)
@@ -723,11 +746,20 @@ class KernelAA(_BaseAA):
             self._n_components_defaulted_from = 'n_samples'
         self._check_hyper_parameters()
         shape_only = _ShapeOnly(n_samples)
-        with _backend.Context(dtype=np.float64) as ctx:
-            if spec['form'] == 'rbf':
-                ctx.set_rbf_features(X, gamma)
+        with contextlib.ExitStack() as stack:
+            if on_device:
+                owner = stack.enter_context(X.borrow())
+                ctx = stack.enter_context(_backend.Context(dtype=np.float64, device=owner.device))
+                if spec['form'] == 'rbf':
+                    ctx.set_rbf_features_resident(owner, gamma)
+                else:
+                    ctx.set_poly_features_resident(owner, gamma, spec['coef0'], spec['degree'])
             else:
-                ctx.set_poly_features(X, gamma, spec['coef0'], spec['degree'])
+                ctx = stack.enter_context(_backend.Context(dtype=np.float64))
+                if spec['form'] == 'rbf':
+                    ctx.set_rbf_features(X, gamma)
+                else:
+                    ctx.set_poly_features(X, gamma, spec['coef0'], spec['degree'])
 
             def init_dictionary():
                 init = 'furthest_sum' if self.init is None else self.init
@@ -761,9 +793,14 @@ class KernelAA(_BaseAA):
         # transform() needs the training rows in the support of D = diag(alpha) C only
         D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
         support = np.flatnonzero(np.any(D != 0, axis=0))
+        if on_device:
+            with X.take(support) as rows:                               # s x p values cross the bus, not n x p
+                support_rows = np.ascontiguousarray(rows.to_host())
+        else:
+            support_rows = np.ascontiguousarray(X[support])
         self._transform_state = dict(form=spec['form'], n_samples=n_samples, n_features=X.shape[1], A=A,
                                      gamma=float(gamma), support=support,
-                                     support_rows=np.ascontiguousarray(X[support]),
+                                     support_rows=support_rows,
                                      support_dictionary=np.ascontiguousarray(D[:, support]))
         if spec['form'] == 'poly':
             self._transform_state.update(coef0=spec['coef0'], degree=spec['degree'])
@@ -801,63 +838,118 @@ class KernelAA(_BaseAA):
             ``ArchetypalAnalysis.transform`` and the cost ``0.5 ||Y - W D X||^2 / m``; ``kernel='rbf'``: the RBF
             values against the training rows in the support of D on the f64 matrix cores (aa_rbf_cross),
             the m x n cross kernel never formed; ``kernel='poly'``: the same with the polynomial kernel
-            (aa_poly_cross) and ``kappa(y, y) = (gamma |y|^2 + coef0)^degree``.
+            (aa_poly_cross) and ``kappa(y, y) = (gamma |y|^2 + coef0)^degree``.  The rows may be a ``DeviceData``:
+            a float64 block lends its context, a float32 one is widened on the device (exact), the draws and the
+            weights are those of ``transform(data.to_host())``; the polynomial diagonal then comes from row norms
+            computed on the device (aa_kernel_sample_residuals), so that cost differs from the host array's at
+            rounding level.
         Returns ``(weights, cost)``; ``weights`` is also stored in ``self.weights``."""
         state = getattr(self, '_transform_state', None)
         if state is None:
             raise NotFittedError('This KernelAA instance is not fitted yet: call fit or fit_transform '
                                  'before transform')
-        if isinstance(data, DeviceData):
-            raise TypeError('KernelAA.transform takes a host array, not DeviceData')
-        data = np.asarray(data, dtype=np.float64)
+        data, diagonal = self._kernel_arguments('transform', state, data, diagonal)
+        on_device = isinstance(data, DeviceData)
         form = state['form']
-        width, what = ((state['n_samples'], 'the cross kernel kappa(Y, X_train): one column per training sample')
-                       if form == 'kernel' else
-                       (state['n_features'], 'the feature rows of the new samples'))
-        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != width:
-            raise ValueError('KernelAA.transform: expected %s, an (m, %d) array with m >= 1; got shape %s'
-                             % (what, width, data.shape))
         m, k = data.shape[0], self.n_components
-        if form == 'kernel':
-            if diagonal is None:
-                raise ValueError('KernelAA.transform: `diagonal` (kappa(y, y) of the %d new samples) is required '
-                                 'for a model fitted on an explicit kernel matrix' % m)
-            diagonal = np.asarray(diagonal, dtype=np.float64)
-            if diagonal.shape != (m,):
-                raise ValueError('KernelAA.transform: `diagonal` must hold %d values (one per row of data); '
-                                 'got shape %s' % (m, diagonal.shape))
-        elif diagonal is not None:
-            raise ValueError('KernelAA.transform: `diagonal` is only taken for a model fitted on an explicit '
-                             'kernel matrix; with features=True it follows from the features')
         kw = dict(self.weights_solver_kwargs)
         kw['max_iterations'] = self.max_iterations            # reference :1194
         A = state['A']
         initial_weights = right_stochastic_matrix((m, k), random_state=self.random_state)
-        with _backend.Context(dtype=np.float64) as ctx:
-            ctx.set_data(data, form=_backend.FORM_DATA)
-            if form == 'kernel':
-                D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
-                ctx.gpnh_set_factors(k, W=D.T, Z=initial_weights)          # kappa(Y, X) D'
-            elif form == 'linear':
-                ctx.gpnh_set_factors(k, W=state['archetypes'].T, Z=initial_weights)   # Y (D X)'
-            elif form == 'rbf':
-                ctx.set_rbf_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'])
-                ctx.rbf_cross()                                             # kappa(Y, X_S) D_S'
-                ctx.gpnh_set_factors(k, Z=initial_weights)
-            else:
-                ctx.set_poly_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'],
-                                       state['coef0'], state['degree'])
-                ctx.poly_cross()
-                ctx.gpnh_set_factors(k, Z=initial_weights)
-                diagonal = _poly_kernel_values((data * data).sum(axis=1), state['gamma'], state['coef0'],
-                                               state['degree'])           # kappa(y, y)
+        with _float64_rows(data) as ctx:
+            self._set_linear_terms(ctx, state, initial_weights)
             ctx.gpnh_weights_update(A, **kw)
             self.weights = ctx.gpnh_get_weights()
             if form == 'linear':
                 cost = ctx.gpnh_residual_cost()                             # 0.5 ||Y - W D X||^2 / m
+            elif form == 'poly' and on_device:
+                # kappa(y, y) from row norms computed on the device: the block is not downloaded for a diagonal
+                cost = 0.5 * ctx.kernel_sample_residuals(A, 'poly', samples=False, diagonal=False)[2] / m
             else:
+                if form == 'poly':
+                    diagonal = _poly_kernel_values((data * data).sum(axis=1), state['gamma'], state['coef0'],
+                                                   state['degree'])       # kappa(y, y)
                 cost = ctx.kernel_transform_cost(A, diagonal)
         return self.weights, cost
+
+    def _kernel_arguments(self, method, state, data, diagonal):
+        """Host-side checks of ``transform`` and ``kernel_scores`` (before any device call and before anything is
+        drawn): what ``data`` and ``diagonal`` have to be for the fitted form.  Returns ``(data, diagonal)``, a host
+        array as float64."""
+        form = state['form']
+        if isinstance(data, DeviceData):
+            if form == 'kernel':
+                raise TypeError('KernelAA.%s takes a host array, not DeviceData' % method)
+        else:
+            data = np.asarray(data, dtype=np.float64)
+        width, what = ((state['n_samples'], 'the cross kernel kappa(Y, X_train): one column per training sample')
+                       if form == 'kernel' else
+                       (state['n_features'], 'the feature rows of the new samples'))
+        if data.ndim != 2 or data.shape[0] < 1 or data.shape[1] != width:
+            raise ValueError('KernelAA.%s: expected %s, an (m, %d) array with m >= 1; got shape %s'
+                             % (method, what, width, tuple(data.shape)))
+        m = data.shape[0]
+        if form == 'kernel':
+            if diagonal is None:
+                raise ValueError('KernelAA.%s: `diagonal` (kappa(y, y) of the %d new samples) is required '
+                                 'for a model fitted on an explicit kernel matrix' % (method, m))
+            diagonal = np.asarray(diagonal, dtype=np.float64)
+            if diagonal.shape != (m,):
+                raise ValueError('KernelAA.%s: `diagonal` must hold %d values (one per row of data); '
+                                 'got shape %s' % (method, m, diagonal.shape))
+        elif diagonal is not None:
+            raise ValueError('KernelAA.%s: `diagonal` is only taken for a model fitted on an explicit '
+                             'kernel matrix; with features=True it follows from the features' % method)
+        return data, diagonal
+
+    def _set_linear_terms(self, ctx, state, weights):
+        """The linear terms ``XW = kappa(Y, X_train) D'`` of the rows resident in ``ctx`` (m x k, what the QPs
+        and the kernel-form costs read) and the weights ``weights``, in the call order of ``transform``."""
+        form, k = state['form'], self.n_components
+        if form == 'kernel':
+            D = np.asarray(self.alpha, dtype=np.float64)[:, np.newaxis] * self.dictionary
+            ctx.gpnh_set_factors(k, W=D.T, Z=weights)                       # kappa(Y, X) D'
+        elif form == 'linear':
+            ctx.gpnh_set_factors(k, W=state['archetypes'].T, Z=weights)     # Y (D X)'
+        elif form == 'rbf':
+            ctx.set_rbf_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'])
+            ctx.rbf_cross()                                                 # kappa(Y, X_S) D_S'
+            ctx.gpnh_set_factors(k, Z=weights)
+        else:
+            ctx.set_poly_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'],
+                                   state['coef0'], state['degree'])
+            ctx.poly_cross()
+            ctx.gpnh_set_factors(k, Z=weights)
+
+    def kernel_scores(self, data, weights=None, diagonal=None):
+        """Feature-space scores of ``data`` under the fitted model, for every fitted form:
+        ``validation.KernelScores`` of the per-sample residuals ``r_t = kappa(y_t, y_t) - 2 w_t.(D kappa(X, y_t)) +
+        w_t' A w_t`` -- the cost ``transform`` returns, a feature-space RMSE, the explained fraction
+        ``1 - sum r / sum kappa(y, y)`` and both vectors -- from one launch on the device
+        (aa_kernel_sample_residuals).  ``data`` and ``diagonal`` are what ``transform`` takes: the cross kernel
+        ``kappa(Y, X_train)`` as a host array with ``diagonal`` for a model fitted on an explicit kernel matrix;
+        the feature rows, a host array or a ``DeviceData``, without ``diagonal`` for ``features=True``.
+        ``weights`` (m x n_components) None: the model's own, as after ``fit_transform`` or ``transform`` of the
+        same rows.  No random numbers are drawn."""
+        state = getattr(self, '_transform_state', None)
+        if state is None:
+            raise NotFittedError('This KernelAA instance is not fitted yet: call fit or fit_transform '
+                                 'before kernel_scores')
+        data, diagonal = self._kernel_arguments('kernel_scores', state, data, diagonal)
+        m, k = data.shape[0], self.n_components
+        if weights is None:
+            weights = self.weights
+            if weights is None:
+                raise ValueError('KernelAA.kernel_scores: the model holds no weights; pass `weights`')
+        weights = np.asarray(weights, dtype=np.float64)
+        if weights.shape != (m, k):
+            raise ValueError('KernelAA.kernel_scores: `weights` must be (%d, %d), one row per row of data; got '
+                             'shape %s' % (m, k, weights.shape))
+        kind = {'kernel': 'given', 'linear': 'linear', 'rbf': 'ones', 'poly': 'poly'}[state['form']]
+        with _float64_rows(data) as ctx:
+            self._set_linear_terms(ctx, state, weights)
+            sample_sse, diag, sum_r, sum_d = ctx.kernel_sample_residuals(state['A'], kind, diag=diagonal)
+        return _kernel_scores_from_sums(sample_sse, diag, sum_r, sum_d)
 
     def score(self, data, weights=None):
         """Reconstruction scores of ``data`` (m x n_features, host array or ``DeviceData``) for a model

@@ -107,6 +107,52 @@ class DeviceData(object):
             raise
         return DeviceData(ctx, (hi - lo, self.shape[1]), self.valid, self.original_shape, self.scaling)
 
+    def take(self, indices, dtype=None):
+        """Rows ``indices`` as a new ``DeviceData``, ``to_host()[indices]`` without leaving the device: a gather
+        (aa_set_data_take) with a lifetime of its own -- seasonal subsets, k-fold splits, bootstrap resamples, the
+        few rows a kernel model keeps for ``transform``.  ``indices``: a 1-D sequence or array of integers in any
+        order, duplicates allowed, negative entries counting from the end as in NumPy (None: every row in order).
+        ``dtype``: None (this block's) or ``np.float64`` on a float32 block, an exact widening; narrowing is
+        refused.  Every refusal is a ``ValueError`` raised before any device call.  ``valid``, ``original_shape``
+        and ``scaling`` are inherited."""
+        n_total = self.shape[0]
+        try:
+            target = None if dtype is None else np.dtype(dtype)
+        except TypeError:
+            target = np.dtype(object)
+        if target is not None and target not in (np.dtype(np.float32), np.dtype(np.float64)):
+            raise ValueError("DeviceData.take: dtype must be float32 or float64; got %r" % (dtype,))
+        idx = None
+        if indices is not None:
+            raw = np.asarray(indices)
+            if raw.ndim != 1 or raw.size == 0:
+                raise ValueError("DeviceData.take: a non-empty 1-D sequence of row indices expected; got shape %r"
+                                 % (raw.shape,))
+            if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer):
+                raise ValueError("DeviceData.take: integer row indices expected (a boolean mask goes through "
+                                 "np.flatnonzero); got dtype %s" % raw.dtype)
+            bad = np.flatnonzero((raw < -n_total) | (raw >= n_total))
+            if bad.size:
+                raise ValueError("DeviceData.take: index %d (position %d) is outside the %d rows held"
+                                 % (int(raw[bad[0]]), bad[0], n_total))
+            idx = raw.astype(np.int64)
+            idx[idx < 0] += n_total
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        if target is None:
+            target = self.dtype
+        elif target != self.dtype and target != np.dtype(np.float64):
+            raise ValueError("DeviceData.take: a float64 block is not narrowed to float32 (only the exact widening "
+                             "float32 -> float64 is offered)")
+        ctx = _backend.Context(dtype=target, device=self._ctx.device)
+        try:
+            ctx.set_data_take(self._ctx, idx)
+        except Exception:
+            ctx.close()
+            raise
+        return DeviceData(ctx, (n_total if idx is None else idx.shape[0], self.shape[1]), self.valid,
+                          self.original_shape, self.scaling)
+
     def column_stats(self):
         """``ColumnStats(mean, std, n_samples)`` of the block's columns, from two float64 sweeps over the
         resident matrix (aa_data_column_moments); computed once (a ``DeviceData`` never changes)."""

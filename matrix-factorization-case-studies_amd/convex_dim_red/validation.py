@@ -40,6 +40,27 @@ def _scores_from_sums(column_sse, sample_sse):
                   rmse_pooled=np.sqrt(sse / (m * p)), column_sse=column_sse, sample_sse=sample_sse)
 
 
+KernelScores = namedtuple("KernelScores", ["cost", "rmse", "explained", "sample_sse", "diagonal"])
+KernelScores.__doc__ = """Feature-space scores of m samples under a kernel model (``KernelAA.kernel_scores``), with
+r_t = kappa(y_t, y_t) - 2 w_t.(D kappa(X, y_t)) + w_t' A w_t the squared feature-space distance of sample t from
+its reconstruction and d_t = kappa(y_t, y_t):
+
+``cost``        0.5 sum_t r_t / m (the kernel-form cost ``KernelAA.transform`` returns);
+``rmse``        sqrt(max(sum_t r_t, 0) / m), a distance in feature space;
+``explained``   1 - sum_t r_t / sum_t d_t;
+``sample_sse``  (m) r_t, not clamped: it may be negative at rounding level;  ``diagonal``  (m) d_t."""
+
+
+def _kernel_scores_from_sums(sample_sse, diagonal, sum_r, sum_d):
+    """The derived numbers from the two vectors and their sums (host only)."""
+    sample_sse = np.asarray(sample_sse, dtype=np.float64)
+    diagonal = np.asarray(diagonal, dtype=np.float64)
+    m = sample_sse.shape[0]
+    sum_r, sum_d = float(sum_r), float(sum_d)
+    return KernelScores(cost=0.5 * sum_r / m, rmse=float(np.sqrt(max(sum_r, 0.0) / m)),
+                        explained=1.0 - sum_r / sum_d, sample_sse=sample_sse, diagonal=diagonal)
+
+
 def _score_arguments(whom, data, n_features, n_components, weights, model_weights):
     """Host-side checks of ``score`` (before any device call); returns (data, weights)."""
     if not isinstance(data, DeviceData):
@@ -95,7 +116,18 @@ def time_series_folds(n_samples, n_folds):
     return [(start, start, start + test_size) for start in range(first, n_samples, test_size)]
 
 
-def time_series_cross_validate(make_model, data, n_folds=10, n_init=1, dtype=None):
+def _kernel_model_scores(fit_kwargs):
+    """Whether the models of a cross-validation are scored in feature space (``KernelAA`` on a non-linear
+    kernel: ``kernel_scores``) rather than in data space (``score``); refuses a ``KernelAA`` that would be
+    fitted on an explicit kernel matrix.  Host only."""
+    if not fit_kwargs.get('features', False):
+        raise ValueError("time_series_cross_validate: a KernelAA is cross-validated on feature rows "
+                         "(fit_kwargs=dict(features=True, kernel=...)); an explicit kernel matrix has no row "
+                         "blocks: its training and test parts are sub-matrices, not runs of rows")
+    return fit_kwargs.get('kernel', 'linear') != 'linear'
+
+
+def time_series_cross_validate(make_model, data, n_folds=10, n_init=1, dtype=None, fit_kwargs=None):
     """The cross-validation loop of the drivers (``bin/run_hadisst_aa.py:215-244`` with ``fit_aa_model``
     ``:149-174``) on resident data.
 
@@ -107,11 +139,19 @@ def time_series_cross_validate(make_model, data, n_folds=10, n_init=1, dtype=Non
     ``score`` of that model on the prefix with its own weights; ``transform`` of the test block;
     ``score`` on the test block.  Restarts inside a fold run one after the other on the resident prefix.
 
+    ``fit_kwargs`` (None: none) are passed to every ``fit_transform``.  With
+    ``fit_kwargs=dict(features=True, kernel='rbf' | 'poly', ...)`` ``make_model()`` may return a ``KernelAA``:
+    the same loop and draw order, the training block never leaves the device, and the two RMSEs are feature-space
+    distances, ``kernel_scores(...).rmse``, joined by ``training_explained`` / ``test_explained``; on the linear
+    kernel (``features=True`` alone) the scores are ``score``'s, as for the other estimators.  A ``KernelAA``
+    without ``features=True`` is refused before the upload: an explicit kernel matrix has no row blocks.
+
     Returns a dict of per-fold lists: ``training_cost`` (the fit's cost), ``training_rmse``,
     ``test_cost`` (what ``transform`` returned), ``test_rmse``, ``n_iter``, ``training_weights``,
     ``test_weights``, ``folds`` (``time_series_folds``) and ``models`` (the kept models)."""
     if not isinstance(n_init, (int, np.integer)) or n_init < 1:
         raise ValueError("n_init must be a positive integer; got %r" % (n_init,))
+    fit_kwargs = {} if fit_kwargs is None else dict(fit_kwargs)
     own = not isinstance(data, DeviceData)
     if own:
         data = np.asarray(data)
@@ -120,6 +160,12 @@ def time_series_cross_validate(make_model, data, n_folds=10, n_init=1, dtype=Non
     folds = time_series_folds(data.shape[0], n_folds)
     out = dict(training_cost=[], training_rmse=[], test_cost=[], test_rmse=[], n_iter=[], training_weights=[],
                test_weights=[], folds=folds, models=[])
+    # the first model is made before the upload (nothing is drawn in between), so that a kernel model that cannot
+    # be cross-validated is refused before anything reaches the device
+    first = make_model()
+    in_feature_space = hasattr(first, 'kernel_scores') and _kernel_model_scores(fit_kwargs)
+    if in_feature_space:
+        out.update(training_explained=[], test_explained=[])
     if own:
         ctx = _backend.Context(dtype=dtype)
         try:
@@ -133,18 +179,24 @@ def time_series_cross_validate(make_model, data, n_folds=10, n_init=1, dtype=Non
             with data.rows(0, train_stop) as train, data.rows(test_start, test_stop) as test:
                 best = None
                 for _ in range(n_init):
-                    model = make_model()
-                    model.fit_transform(train)
+                    model, first = (make_model(), None) if first is None else (first, None)
+                    model.fit_transform(train, **fit_kwargs)
                     if best is None or model.cost < best.cost:
                         best = deepcopy(model)
                 out["training_cost"].append(best.cost)
                 out["n_iter"].append(best.n_iter)
                 out["training_weights"].append(best.weights)
-                out["training_rmse"].append(best.score(train).rmse)
+                scores = best.kernel_scores(train) if in_feature_space else best.score(train)
+                out["training_rmse"].append(scores.rmse)
+                if in_feature_space:
+                    out["training_explained"].append(scores.explained)
                 test_weights, test_cost = best.transform(test)
                 out["test_cost"].append(test_cost)
                 out["test_weights"].append(test_weights)
-                out["test_rmse"].append(best.score(test).rmse)
+                scores = best.kernel_scores(test) if in_feature_space else best.score(test)
+                out["test_rmse"].append(scores.rmse)
+                if in_feature_space:
+                    out["test_explained"].append(scores.explained)
                 out["models"].append(best)
     finally:
         if own:

@@ -419,6 +419,12 @@ int launch_col_moments(Ctx *c, double *partial_dev /* nslab x p_pad */, double *
                        double *var_dev /* p_pad, nullable */);
 int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shift_dev /*nullable*/,
                        const double *scale_dev /*nullable*/);
+// row gather behind aa_set_data_take (idx_dev null: the rows in order) and the float64 feature buffer of an
+// implicit kernel from a resident matrix; owner_dtype / owner_ld: element type and leading dimension of owner_X
+int launch_gather_rows(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, const long *idx_dev,
+                       void *dst = nullptr /* null: c->X; else a buffer of its layout (aa_time_kernel) */);
+int launch_features_from_data(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, long n, long p, double *F,
+                              long ldf);
 int launch_gpnh_solve(Ctx *c, double lambda, int *ok_dev);
 // R restarts side by side (kernels_tall.hip: RestartSlots); rule: what the slots' judges apply (what = 2; a
 // zeroed one otherwise)
@@ -444,6 +450,11 @@ int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double
 // sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) over the resident rows (A: KP x KP device, d: device or null = 1;
 // part: (n + 255) / 256 + 1 doubles of scratch)
 int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_dev, double *part, double *out_host);
+// the same terms per sample (aa_kernel_sample_residuals): r_dev / dout_dev n doubles each, part 2 nb + 2 doubles
+// (nb = (n + 255) / 256) whose last two receive sum r and sum d; kind: AA_DIAG_*, d_dev (GIVEN) / nrm_dev (POLY
+// with c->cross_poly, LINEAR: squared row norms) n doubles.  Launches only
+int launch_kernel_sample_residuals(Ctx *c, const double *A_dev, int kind, const double *d_dev, const double *nrm_dev,
+                                   double *r_dev, double *dout_dev, double *part);
 int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n_ex, int extra_steps,
                         int *selected_host, int *tie_host);
 int launch_row_broadcast(Ctx *c, long j_local, bool own);

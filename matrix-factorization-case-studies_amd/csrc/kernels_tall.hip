@@ -3043,6 +3043,85 @@ int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shi
     return AA_OK;
 }
 
+// ---- row gather and the feature buffer of an implicit kernel, both from a resident matrix (aa_set_data_take,
+// aa_set_*_features_resident).  Y[r][j] = (TO)X[src(r)][j] for r < n, j < p, src(r) = idx ? idx[r] : r; the
+// conversion is the identity or the exact widening float -> double.  A block covers 128 adjacent columns (32
+// column lanes x 4 elements) and 8 rows at a time; columns >= p and rows >= n are not touched (Y is a zero-filled
+// allocation with a leading dimension of its own).  The caller has checked every idx[r] against the owner's rows.
+template <typename TI, typename TO>
+__device__ __forceinline__ void copy_rows(const TI *__restrict__ X, long ldx, const long *__restrict__ idx, long n,
+                                          long p, TO *__restrict__ Y, long ldy)
+{
+    const int cl = threadIdx.x & 31, rl = threadIdx.x >> 5;
+    const long col = (long)blockIdx.x * 128 + cl * 4;
+    if (col >= p) return;
+    for (long r = (long)blockIdx.y * 8 + rl; r < n; r += (long)gridDim.y * 8) {
+        const TI *src = X + (idx ? idx[r] : r) * ldx + col;
+        TO *dst = Y + r * ldy + col;
+#pragma unroll
+        for (int v = 0; v < 4; ++v)
+            if (col + v < p) dst[v] = (TO)src[v];
+    }
+}
+
+template <typename TI, typename TO>
+__global__ __launch_bounds__(256) void k_gather_rows(const TI *__restrict__ X, long ldx, const long *__restrict__ idx,
+                                                     long n, long p, TO *__restrict__ Y, long ldy)
+{
+    copy_rows<TI, TO>(X, ldx, idx, n, p, Y, ldy);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_features_from_data(const T *__restrict__ X, long ldx, long n, long p,
+                                                            double *__restrict__ F, long ldf)
+{
+    copy_rows<T, double>(X, ldx, nullptr, n, p, F, ldf);
+}
+
+static inline dim3 copy_rows_grid(long n, long p)
+{
+    const long xb = (p + 127) / 128;
+    long yb = (8192 + xb - 1) / xb;                      // enough blocks to fill the chip when there are few columns
+    if (yb > (n + 7) / 8) yb = (n + 7) / 8;
+    if (yb > 65535) yb = 65535;
+    return dim3((unsigned)xb, (unsigned)yb);
+}
+
+// c->X (zero filled, c->n x c->p_pad; or dst, of the same layout) from rows idx_dev[0 .. c->n) (null: 0, 1, ...) of
+// the owner's matrix
+int launch_gather_rows(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, const long *idx_dev, void *dst)
+{
+    const dim3 grid = copy_rows_grid(c->n, c->p);
+    if (!dst) dst = c->X.p;
+#define GR(TI, TO)                                                                                            \
+    hipLaunchKernelGGL((k_gather_rows<TI, TO>), grid, dim3(256), 0, c->stream,                                \
+                       reinterpret_cast<const TI *>(owner_X), owner_ld, idx_dev, c->n, c->p,                  \
+                       reinterpret_cast<TO *>(dst), c->p_pad)
+    if (owner_dtype == AA_F32) {
+        if (c->dtype == AA_F32) GR(float, float); else GR(float, double);
+    } else {
+        GR(double, double);
+    }
+#undef GR
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+// F (zero filled, [..][ldf] float64) from n rows of p values of the owner's matrix
+int launch_features_from_data(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, long n, long p, double *F,
+                              long ldf)
+{
+    const dim3 grid = copy_rows_grid(n, p);
+    if (owner_dtype == AA_F32)
+        hipLaunchKernelGGL(k_features_from_data<float>, grid, dim3(256), 0, c->stream,
+                           reinterpret_cast<const float *>(owner_X), owner_ld, n, p, F, ldf);
+    else
+        hipLaunchKernelGGL(k_features_from_data<double>, grid, dim3(256), 0, c->stream,
+                           reinterpret_cast<const double *>(owner_X), owner_ld, n, p, F, ldf);
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
 // ---------------------------------------------------------------- scale factors (delta != 0)
 // _update_kernel_aa_scale_factors (archetypal_analysis.py:243-258): spg() (spg.py:46-283) on the
 // k-vector alpha with the box projection clip(alpha, 1 - delta, 1 + delta), objective and gradient
@@ -4349,6 +4428,82 @@ int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_de
     AA_CHECK_HIP(hipGetLastError());
     AA_CHECK_HIP(hipMemcpyAsync(out_host, part + nb, sizeof(double), hipMemcpyDeviceToHost, c->stream));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    return AA_OK;
+}
+
+// The per-sample terms of k_kernel_transform_cost kept (aa_kernel_sample_residuals): one thread per row t,
+// d_t by `kind` (GIVEN: d[t]; ONES: 1; POLY: poly_kappa(nrm[t]); LINEAR: nrm[t], nrm = squared row norms),
+// r_t = d_t - 2 z_t.XW_t + z_t' A z_t in the arithmetic of k_kernel_transform_cost, r_out[t] / d_out[t] for
+// t < n, and the block's sums of r and of d by the same fixed tree into partial[b] / partial[nb + b].
+template <int KP>
+__global__ __launch_bounds__(256) void k_kernel_sample_residuals(const double *__restrict__ Z,
+                                                                 const double *__restrict__ XW,
+                                                                 const double *__restrict__ A, int kind,
+                                                                 const double *__restrict__ d,
+                                                                 const double *__restrict__ nrm, PolyKernel pk, long n,
+                                                                 long nb, double *__restrict__ r_out,
+                                                                 double *__restrict__ d_out,
+                                                                 double *__restrict__ partial)
+{
+    __shared__ double as[KP * KP];
+    __shared__ double red[2][256];
+    for (int e = threadIdx.x; e < KP * KP; e += 256) as[e] = A[e];
+    __syncthreads();
+    const long t = (long)blockIdx.x * 256 + threadIdx.x;
+    double v = 0.0, dt = 0.0;
+    if (t < n) {
+        double z[KP];
+#pragma unroll
+        for (int i = 0; i < KP; ++i) z[i] = Z[t * KP + i];
+        double wb = 0.0, wAw = 0.0;
+#pragma unroll 1
+        for (int i = 0; i < KP; ++i) {
+            double ai = 0.0;
+#pragma unroll
+            for (int j = 0; j < KP; ++j) ai = fma(as[i * KP + j], z[j], ai);
+            const double zi = Z[t * KP + i];
+            wAw = fma(zi, ai, wAw);
+            wb = fma(zi, XW[t * KP + i], wb);
+        }
+        dt = kind == AA_DIAG_GIVEN ? d[t] : kind == AA_DIAG_POLY ? poly_kappa(nrm[t], pk)
+                                                                  : kind == AA_DIAG_LINEAR ? nrm[t] : 1.0;
+        v = dt - 2.0 * wb + wAw;
+        r_out[t] = v;
+        d_out[t] = dt;
+    }
+    red[0][threadIdx.x] = v;
+    red[1][threadIdx.x] = dt;
+    __syncthreads();
+    for (int o = 128; o > 0; o >>= 1) {
+        if ((int)threadIdx.x < o) {
+            red[0][threadIdx.x] += red[0][threadIdx.x + o];
+            red[1][threadIdx.x] += red[1][threadIdx.x + o];
+        }
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        partial[blockIdx.x] = red[0][0];
+        partial[nb + blockIdx.x] = red[1][0];
+    }
+}
+
+// r_dev / dout_dev: c->n doubles each; part: 2 nb + 2 doubles, nb = (n + 255) / 256 (the two sums end up in
+// part[2 nb], part[2 nb + 1]); d_dev (GIVEN) / nrm_dev (POLY, LINEAR): c->n doubles
+int launch_kernel_sample_residuals(Ctx *c, const double *A_dev, int kind, const double *d_dev, const double *nrm_dev,
+                                   double *r_dev, double *dout_dev, double *part)
+{
+    const long nb = (c->n + 255) / 256;
+#define KSR(KPV)                                                                                                   \
+    hipLaunchKernelGGL(k_kernel_sample_residuals<KPV>, dim3((unsigned)nb), dim3(256), 0, c->stream,                \
+                       (const double *)c->Zt.as<double>(), (const double *)c->Gr.as<double>(), A_dev, kind, d_dev, \
+                       nrm_dev, c->cross_poly, c->n, nb, r_dev, dout_dev, part)
+    if (c->KP == 32) KSR(32); else KSR(64);
+#undef KSR
+    AA_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const double *)part, nb, part + 2 * nb);
+    hipLaunchKernelGGL(k_sum_partials, dim3(1), dim3(256), 0, c->stream, (const double *)(part + nb), nb,
+                       part + 2 * nb + 1);
+    AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
 

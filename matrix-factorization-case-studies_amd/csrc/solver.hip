@@ -681,8 +681,10 @@ int aa_set_linear_kernel(aa_ctx *h, int on)
 }
 
 // the features of an implicit kernel: the kernel form of the algorithm on a virtual n x n matrix; feat_ld: the
-// leading dimension of the zero-padded feature buffer, chosen by the kernels that read it
-static int set_implicit_features(Ctx *c, const double *X, long n, long p, long ld, long feat_ld, int kind)
+// leading dimension of the zero-padded feature buffer, chosen by the kernels that read it.  `owner` (X == nullptr):
+// the features are the rows of its resident data matrix, converted on the device
+static int set_implicit_features(Ctx *c, const double *X, long n, long p, long ld, long feat_ld, int kind,
+                                 const Ctx *owner = nullptr)
 {
     AA_CHECK_HIP(hipSetDevice(c->device));
     c->form = AA_FORM_KERNEL;                    // the kernel form of the algorithm (/k conventions, tr K)
@@ -699,8 +701,12 @@ static int set_implicit_features(Ctx *c, const double *X, long n, long p, long l
     c->feat_ld = feat_ld;
     AA_CHECK(c->feat.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->feat_ld * sizeof(double)));
     AA_CHECK_HIP(ctx_memset(c, c->feat.p, 0, c->feat.bytes));
-    AA_CHECK_HIP(ctx_memcpy2d(c, c->feat.p, (size_t)c->feat_ld * sizeof(double), X, (size_t)ld * sizeof(double),
-                              (size_t)p * sizeof(double), (size_t)n, hipMemcpyHostToDevice));
+    if (owner)
+        AA_CHECK(launch_features_from_data(c, owner->X.p, owner->dtype, owner->p_pad, n, p, c->feat.as<double>(),
+                                           c->feat_ld));
+    else
+        AA_CHECK_HIP(ctx_memcpy2d(c, c->feat.p, (size_t)c->feat_ld * sizeof(double), X, (size_t)ld * sizeof(double),
+                                  (size_t)p * sizeof(double), (size_t)n, hipMemcpyHostToDevice));
     AA_CHECK(c->featNorm.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * sizeof(double)));
     AA_CHECK(launch_rbf_norms(c));
     c->have_data = true;
@@ -709,6 +715,7 @@ static int set_implicit_features(Ctx *c, const double *X, long n, long p, long l
     c->KP = 0;
     c->have_state = false;
     c->grams_valid = false;
+    if (owner) AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // the owner has been read: it may go
     return AA_OK;
 }
 
@@ -742,6 +749,43 @@ int aa_set_poly_features(aa_ctx *h, const double *X, long n, long p, long ld, do
     c->poly = PolyKernel{gamma, coef0, degree};
     // k_poly_kv_mfma reads rows in chunks of 32 features
     return set_implicit_features(c, X, n, p, ld, round_up(p, 32), IMPLICIT_POLY);
+}
+
+// what both resident forms ask of the two contexts
+static int check_feature_owner(const aa_ctx *h, const aa_ctx *owner, const char *what)
+{
+    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    const Ctx *c = &h->c, *o = &owner->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_STATE,
+               "the implicit %s kernel is single-rank", what);
+    AA_REQUIRE(c->dtype == AA_F64, AA_ERR_STATE, "the implicit %s kernel needs a float64 context", what);
+    AA_REQUIRE(!o->implicit_kernel && o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE,
+               "the owner holds no stored data matrix (data form)");
+    AA_REQUIRE(o->device == c->device, AA_ERR_ARG, "same device needed");
+    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
+    return AA_OK;
+}
+
+int aa_set_rbf_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma)
+{
+    AA_CHECK(check_feature_owner(h, owner, "RBF"));
+    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    c->rbf_gamma = gamma;
+    return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 2), IMPLICIT_RBF, o);
+}
+
+int aa_set_poly_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma, double coef0, int degree)
+{
+    AA_CHECK(check_feature_owner(h, owner, "polynomial"));
+    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
+               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
+               degree);
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    c->poly = PolyKernel{gamma, coef0, degree};
+    return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 32), IMPLICIT_POLY, o);
 }
 
 int aa_comm_get_unique_id(void *id128) { return comm_unique_id(id128); }
@@ -968,6 +1012,65 @@ int aa_set_data_rows_affine(aa_ctx *h, const aa_ctx *owner, long row0, long n, c
     coef.release();
     if (rc == AA_OK && e != hipSuccess) {
         set_error("aa_set_data_rows_affine: %s", hipGetErrorString(e));
+        rc = AA_ERR_HIP;
+    }
+    AA_CHECK(rc);
+    c->have_data = true;
+    c->have_trace = false;
+    c->k = 0;   // forces (re)allocation of the factor buffers
+    c->KP = 0;
+    c->have_state = false;
+    c->grams_valid = false;
+    return AA_OK;
+}
+
+int aa_set_data_take(aa_ctx *h, const aa_ctx *owner, const long *idx, long n)
+{
+    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_take: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
+    AA_REQUIRE(o->device == c->device, AA_ERR_ARG, "aa_set_data_take: same device needed");
+    AA_REQUIRE(o->dtype == c->dtype || (o->dtype == AA_F32 && c->dtype == AA_F64), AA_ERR_ARG,
+               "aa_set_data_take: equal data types, or a float32 owner widened into a float64 context");
+    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
+               "aa_set_data_take is single-rank");
+    AA_REQUIRE(n >= 1 && (idx || n <= o->n), AA_ERR_ARG, "bad row count %ld (the owner holds %ld rows)", n, o->n);
+    // refused before anything of ctx is released and before any launch: the gather kernel reads whatever row it is given
+    for (long r = 0; idx && r < n; ++r)
+        AA_REQUIRE(idx[r] >= 0 && idx[r] < o->n, AA_ERR_ARG, "aa_set_data_take: idx[%ld] = %ld is outside [0, %ld)", r,
+                   idx[r], o->n);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    DevBuf didx;
+    if (idx) {
+        AA_CHECK(didx.alloc((size_t)n * sizeof(long)));
+        hipError_t eu = ctx_memcpy(c, didx.p, idx, (size_t)n * sizeof(long), hipMemcpyHostToDevice);
+        if (eu != hipSuccess) {
+            didx.release();
+            set_error("aa_set_data_take: %s", hipGetErrorString(eu));
+            return AA_ERR_HIP;
+        }
+    }
+    c->form = AA_FORM_DATA;
+    c->linear_kernel = false;
+    c->implicit_kernel = 0;
+    c->cross_s = 0;
+    c->n = n;
+    c->p = o->p;
+    c->n_pad = round_up(n, 128);
+    c->p_pad = round_up(o->p, 128);              // the context's own: a widened copy need not share the owner's
+    c->n_global = n;
+    c->row_offset = 0;
+    c->have_data = false;
+    c->X.release();
+    int rc = c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));   // zero filled: the padding of aa_set_data
+    hipError_t e = hipSuccess;
+    if (rc == AA_OK) rc = launch_gather_rows(c, o->X.p, o->dtype, o->p_pad, idx ? didx.as<long>() : (const long *)nullptr);
+    if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
+    didx.release();
+    if (rc == AA_OK && e != hipSuccess) {
+        set_error("aa_set_data_take: %s", hipGetErrorString(e));
         rc = AA_ERR_HIP;
     }
     AA_CHECK(rc);
@@ -2358,6 +2461,45 @@ int aa_kernel_transform_cost(aa_ctx *h, const double *A, const double *diag, dou
     return AA_OK;
 }
 
+int aa_kernel_sample_residuals(aa_ctx *h, const double *A, int diag_kind, const double *diag, double *sample_sse,
+                               double *diag_out, double sums[2])
+{
+    AA_REQUIRE(h && A && sums, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(diag_kind >= AA_DIAG_GIVEN && diag_kind <= AA_DIAG_LINEAR, AA_ERR_ARG, "bad diag_kind %d", diag_kind);
+    AA_REQUIRE((diag_kind == AA_DIAG_GIVEN) == (diag != nullptr), AA_ERR_ARG,
+               "a diagonal vector goes with AA_DIAG_GIVEN, and with nothing else");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_state && c->gpnh_valid, AA_ERR_STATE, "weights and linear terms first");
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the kernel-form residuals are single-rank");
+    const bool from_norms = diag_kind == AA_DIAG_POLY || diag_kind == AA_DIAG_LINEAR;
+    AA_REQUIRE(!from_norms || (c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64),
+               AA_ERR_STATE, "this diagonal is computed from a stored float64 data matrix");
+    AA_REQUIRE(diag_kind != AA_DIAG_POLY || (c->cross_s > 0 && c->cross_kind == IMPLICIT_POLY), AA_ERR_STATE,
+               "aa_set_poly_reference first");
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    const size_t GS = (size_t)c->KP * c->KP;
+    const long nb = (c->n + 255) / 256;
+    // A | d (given) | r | d (out) | block partials of r, of d | the two sums
+    AA_CHECK(c->xformCost.alloc((GS + (size_t)3 * c->n_pad + (size_t)2 * nb + 2) * sizeof(double)));
+    double *base = c->xformCost.as<double>();
+    double *d_in = base + GS, *r_dev = d_in + c->n_pad, *d_dev = r_dev + c->n_pad, *part = d_dev + c->n_pad;
+    std::vector<double> a(GS, 0.0);
+    for (int i = 0; i < c->k; ++i)
+        for (int j = 0; j < c->k; ++j) a[(size_t)i * c->KP + j] = A[(size_t)i * c->k + j];
+    AA_CHECK_HIP(ctx_memcpy(c, base, a.data(), GS * sizeof(double), hipMemcpyHostToDevice));
+    if (diag) AA_CHECK_HIP(ctx_memcpy(c, d_in, diag, (size_t)c->n * sizeof(double), hipMemcpyHostToDevice));
+    if (from_norms) {
+        AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
+        AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, c->p, c->n_pad, c->rowNorm.as<double>()));
+    }
+    AA_CHECK(launch_kernel_sample_residuals(c, base, diag_kind, diag ? d_in : nullptr,
+                                            from_norms ? c->rowNorm.as<double>() : nullptr, r_dev, d_dev, part));
+    AA_CHECK_HIP(ctx_memcpy(c, sums, part + 2 * nb, 2 * sizeof(double), hipMemcpyDeviceToHost));
+    if (sample_sse) AA_CHECK_HIP(ctx_memcpy(c, sample_sse, r_dev, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost));
+    if (diag_out) AA_CHECK_HIP(ctx_memcpy(c, diag_out, d_dev, (size_t)c->n * sizeof(double), hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
 // ------------------------------------------------------------------ stateless ops
 int aa_simplex_project_rows(int device, const double *in, double *out, long rows, long cols)
 {
@@ -2608,6 +2750,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     else if (which == 12)
         AA_REQUIRE(c->have_data && !c->implicit_kernel && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
+    else if (which == 13 || which == 14)
+        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->world == 1 && !c->force_comm,
+                   AA_ERR_STATE, "aa_time_kernel 13 / 14: a stored data matrix (data form), single rank");
     else {
         AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
         AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
@@ -2617,6 +2762,25 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     AA_CHECK_HIP(hipEventCreate(&e0));
     AA_CHECK_HIP(hipEventCreate(&e1));
     int rc = AA_OK;
+    // 13 / 14: a scratch destination of the layout the entry point fills, and a seeded permutation of the rows
+    DevBuf scratch, perm;
+    const long scratch_ld = which == 14 ? round_up(c->p, 32) : c->p_pad;
+    if (which == 13 || which == 14)
+        rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * scratch_ld * (which == 14 ? sizeof(double) : esize(c)));
+    if (which == 13 && rc == AA_OK) {
+        std::vector<long> idx((size_t)c->n);
+        for (long r = 0; r < c->n; ++r) idx[(size_t)r] = r;
+        unsigned long long state = 0x9e3779b97f4a7c15ull;
+        for (long r = c->n - 1; r > 0; --r) {            // Fisher-Yates on a 64-bit LCG
+            state = state * 6364136223846793005ull + 1442695040888963407ull;
+            std::swap(idx[(size_t)r], idx[(size_t)((state >> 33) % (unsigned long long)(r + 1))]);
+        }
+        rc = perm.alloc(idx.size() * sizeof(long));
+        if (rc == AA_OK && ctx_memcpy(c, perm.p, idx.data(), idx.size() * sizeof(long), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("aa_time_kernel 13: upload of the permutation failed");
+            rc = AA_ERR_HIP;
+        }
+    }
     // one untimed launch first
     for (int phase = 0; phase < 2 && rc == AA_OK; ++phase) {
         const int nrep = phase == 0 ? 1 : reps;
@@ -2638,6 +2802,10 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                 rc = launch_residual_cost(c, c->Zt.as<double>(), c->P.as<double>(), nullptr, nullptr);
             else if (which == 12)
                 rc = launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, true, &c->groupFlags);
+            else if (which == 13)
+                rc = launch_gather_rows(c, c->X.p, c->dtype, c->p_pad, perm.as<long>(), scratch.p);
+            else if (which == 14)
+                rc = launch_features_from_data(c, c->X.p, c->dtype, c->p_pad, c->n, c->p, scratch.as<double>(), scratch_ld);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
@@ -2657,6 +2825,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
+    if (which == 13 || which == 14) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
+    scratch.release();
+    perm.release();
     return rc;
 }
 
