@@ -228,7 +228,21 @@ int aa_ctx_p2p_init(aa_ctx *ctx, const void *handles, int rank, int world);
  * bench.py for the barrier + max-over-ranks timing); op: 0 = sum, 1 = max. */
 int aa_ctx_allreduce_host(aa_ctx *ctx, double *buf, int count, int op);
 
-/* Upload this rank's row block of the data matrix (form DATA: n x p) or kernel
+/* Installing data.  Ten entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
+ * aa_set_data_rows_affine, aa_set_data_take, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
+ * the _resident forms of the last two.  Every one of them ("an install") first checks its arguments -- a call it
+ * refuses has not touched ctx, which keeps the data it had -- and then replaces everything that belonged to the
+ * previous matrix: the form and the kind of implicit kernel (none for a stored matrix), aa_set_linear_kernel, the
+ * reference set of aa_set_{rbf,poly}_reference, the sizes and the shard, the cached trace, the factors and their
+ * Gram products (the next aa_set_state / aa_gpnh_set_factors sizes the arrays afresh), and the pass counts and
+ * sample order the QP keeps from one weights update to the next.  The matrix goes into a fresh zero-filled
+ * allocation, rows and columns padded to multiples of 128 (aa_share_data aliases the owner's instead; an implicit
+ * kernel keeps its float64 features and their squared norms, and no matrix).  What ctx does afterwards depends
+ * only on this install, not on the ones before it.  An install that fails after its argument checks (an
+ * allocation, a copy, a kernel) leaves ctx WITHOUT data (AA_ERR_STATE from whatever needs some), never with half
+ * of it.
+ *
+ * aa_set_data: upload this rank's row block of the data matrix (form DATA: n x p) or kernel
  * matrix (form KERNEL: n x n, p == n; single rank only).  host_dtype: AA_F32/AA_F64
  * element type of `X` (converted to the context dtype on upload).  The matrix stays
  * resident across restarts.  `n_global`/`row_offset` describe the shard.
@@ -278,15 +292,18 @@ int aa_weights_update(aa_ctx *ctx, const aa_qp_params *params, aa_qp_stats *stat
  * `ctx` takes the resident data matrix of `owner` (same device, same dtype, single rank) without
  * a copy -- the solver only reads it -- so several contexts, each with its own factors, streams
  * and scratch, work on ONE copy of X concurrently.  `owner` must outlive `ctx` or give it new
- * data first (aa_set_data / aa_share_data release the alias, never the owner's memory). */
+ * data first (any install releases the alias, never the owner's memory).  An install like the others
+ * ("installing data" above), of the owner's form (DATA or a stored KERNEL matrix), except that ctx also takes
+ * over the owner's cached trace, so that restart contexts do not each run a trace pass. */
 int aa_share_data(aa_ctx *ctx, const aa_ctx *owner);
 
 /* Cross-validation on resident data (bin/run_hadisst_aa.py:213-245: TimeSeriesSplit fits on growing
  * prefixes of the training rows and transforms the block behind each, `training_data[train_index]` /
  * `training_data[test_index]` being fresh host slices): rows [row0, row0 + n) of owner's resident DATA
- * matrix become ctx's data matrix, exactly as after aa_set_data on the same values -- a device-to-device
- * copy, the host is not involved.  Same device, same dtype, data form, both single rank, no implicit
- * kernel.  Unlike aa_share_data the copy owns its memory: the owner may be destroyed afterwards. */
+ * matrix become ctx's data matrix -- an install ("installing data" above) of the same values by a
+ * device-to-device copy, the host is not involved.  owner is another context on the same device with the same
+ * dtype, holding a stored matrix in data form (no kernel matrix, no implicit kernel), both single rank.  Unlike
+ * aa_share_data the copy owns its memory: the owner may be destroyed afterwards. */
 int aa_set_data_rows(aa_ctx *ctx, const aa_ctx *owner, long row0, long n);
 
 /* Column statistics and standardisation of resident data (the --standardize step of
@@ -301,21 +318,21 @@ int aa_set_data_rows(aa_ctx *ctx, const aa_ctx *owner, long row0, long n);
  * aa_set_data_rows_affine: aa_set_data_rows with Y[r][j] = (X[row0 + r][j] - shift[j]) / scale[j]: float64
  *   subtraction and a true float64 division, rounded once to the context's element type.  shift / scale: host
  *   arrays of owner's p values; NULL: 0 / 1.  A scale[j] that is zero or not finite, or a shift[j] that is not
- *   finite, is refused with AA_ERR_ARG before ctx is touched (it keeps the data it had).  Otherwise the
- *   preconditions, refusals and effects on ctx of aa_set_data_rows. */
+ *   finite, is refused with AA_ERR_ARG like any other bad argument of an install.  Otherwise the
+ *   preconditions and refusals of aa_set_data_rows. */
 int aa_data_column_moments(aa_ctx *ctx, double *mean, double *var);
 int aa_set_data_rows_affine(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, const double *shift,
                             const double *scale);
 
 /* Row gather on the device (seasonal subsets, k-fold splits, bootstrap resamples of a resident block, and the
  * support rows KernelAA.transform keeps, `X[support]`): rows idx[0..n) of owner's resident DATA matrix, in any
- * order and with duplicates, become ctx's data matrix exactly as after aa_set_data on the same values -- a gather
- * kernel (csrc/kernels_tall.hip: k_gather_rows) into a zero-filled allocation of ctx's own,
- * (n_pad + slack rows) x p_pad like aa_set_data_rows; the owner may be destroyed afterwards.  idx == NULL: rows
+ * order and with duplicates, become ctx's data matrix -- an install ("installing data" above) by a gather
+ * kernel (csrc/kernels_tall.hip: k_gather_rows); the owner may be destroyed afterwards.  idx == NULL: rows
  * 0..n-1 in order (n <= owner's n).  Preconditions of aa_set_data_rows (same device, data form, both single rank, no
  * implicit kernel behind the owner); the data types are equal, or the owner is float32 and ctx float64 -- an exact
  * widening, the only mixed case.  EVERY index is checked on the host against [0, owner's n) before anything is
- * launched or released: a bad one is AA_ERR_ARG, the message names the first, and ctx keeps the data it had. */
+ * launched or released: a bad one is AA_ERR_ARG like any other bad argument of an install, and the message names
+ * the first. */
 int aa_set_data_take(aa_ctx *ctx, const aa_ctx *owner, const long *idx, long n);
 
 /* KernelAA on the implicit linear kernel K = X X' (SURVEY 8(f4)): with `on` != 0 the resident
@@ -324,14 +341,14 @@ int aa_set_data_take(aa_ctx *ctx, const aa_ctx *owner, const long *idx, long n);
  * skinny passes over X, exactly as in the data form, and the dictionary gradient follows the
  * kernel form's convention (divided by n_components, _kernel_aa_dictionary_gradient :281-288,
  * where _aa_dictionary_gradient :291-300 divides by n_samples) -- the one place where the two
- * forms of the reference differ for K = X X'.  Reset by aa_set_data. */
+ * forms of the reference differ for K = X X'.  Reset by every install. */
 int aa_set_linear_kernel(aa_ctx *ctx, int on);
 /* KernelAA on an implicit RBF kernel (archetypal_analysis.py:673-910 with the n x n kernel
  * matrix K_ij = exp(-gamma ||x_i - x_j||^2) NEVER formed): uploads the n x p feature matrix (float64) and
  * switches the context to the kernel form of the algorithm; every product C K / K Z is one fused
  * distance + exp + multiply pass over the features (csrc/kernels_gemm.hip: k_rbf_kv), tr K = n, and
- * aa_distance_column returns sqrt(2 - 2 K_ij).  Single rank, float64 context.  Everything downstream
- * (aa_set_state, aa_prepare, aa_iterate, aa_get_state ...) is the explicit kernel form's. */
+ * aa_distance_column returns sqrt(2 - 2 K_ij).  Single rank, float64 context.  An install
+ * ("installing data" above); everything downstream (aa_set_state, aa_prepare, aa_iterate, aa_get_state ...) is the explicit kernel form's. */
 int aa_set_rbf_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma);
 /* The same for the polynomial kernel K_ij = (gamma x_i.x_j + coef0)^degree (scikit-learn's polynomial_kernel),
  * never formed.  The power is degree - 1 multiplications in a fixed order, evaluated by one device function
@@ -356,9 +373,9 @@ int aa_set_poly_features_resident(aa_ctx *ctx, const aa_ctx *owner, double gamma
  * bin/run_jra55_pca_gpnh.py).  `raw` is the flattened field, n_total x p_full, row-major
  * (float64 or float32, NaN = missing), `col_weight[p_full]` the latitude weight of every flattened
  * column (NULL: 1).  Columns with a NaN in ANY of the n_total rows are dropped, the others are
- * multiplied by their weight, and rows [row0, row0 + n) become the context's data matrix exactly
- * as after aa_set_data (data form).  valid[p_full] receives 1 / 0 per column, *p_valid the
- * number of columns kept.  The raw field crosses PCIe once; weighting, the NaN scan and the
+ * multiplied by their weight, and rows [row0, row0 + n) become the context's data matrix (data
+ * form): an install ("installing data" above), refused with AA_ERR_ARG when no column is left.
+ * valid[p_full] receives 1 / 0 per column, *p_valid the number of columns kept.  The raw field crosses PCIe once; weighting, the NaN scan and the
  * compaction run on the GPU. */
 int aa_set_data_weighted(aa_ctx *ctx, const void *raw, int host_dtype, long n_total, long p_full,
                          long ld, const double *col_weight, long row0, long n,

@@ -413,6 +413,15 @@ class Context(object):
         self.implicit = False      # an implicit kernel (set_rbf_features, set_poly_features): no stored matrix behind the products
         self.row_lo = 0
         self.n_global = 0
+        self._data_owner = None    # the context whose matrix this one aliases (share_data): kept alive
+
+    def _adopt(self, n, p, row_lo=0, n_global=None, implicit=False, owner=None):
+        """What an install left in the library (include/aa_hip.h, "installing data"); every setter of
+        the data calls this once, after the library call has succeeded."""
+        self.n, self.p = int(n), int(p)
+        self.row_lo, self.n_global = int(row_lo), int(n if n_global is None else n_global)
+        self.implicit = implicit
+        self._data_owner = owner
 
     def close(self):
         if self.h:
@@ -473,8 +482,7 @@ class Context(object):
         n, p = X.shape
         _check(self.lib.aa_set_data(self.h, X.ctypes.data_as(_vp), host, n, p, p, form,
                                     n if n_global is None else n_global, row_offset))
-        self.n, self.p = n, p
-        self.row_lo, self.n_global = int(row_offset), int(n if n_global is None else n_global)
+        self._adopt(n, p, row_offset, n_global)
 
     def _rows(self, a):
         """This rank's rows of a whole-problem array (global view only)."""
@@ -498,15 +506,13 @@ class Context(object):
         """Use ``owner``'s resident data matrix without a copy (aa_share_data); ``owner`` must stay
         open while this context uses it."""
         _check(self.lib.aa_share_data(self.h, owner.h))
-        self.n, self.p = owner.n, owner.p
-        self._data_owner = owner                  # keeps the owner alive
+        self._adopt(owner.n, owner.p, owner.row_lo, owner.n_global, owner=owner)
 
     def set_data_rows(self, owner, row0, n):
         """Rows [row0, row0 + n) of ``owner``'s resident data matrix become this context's data matrix
         (aa_set_data_rows): a device-to-device copy that owns its memory."""
         _check(self.lib.aa_set_data_rows(self.h, owner.h, int(row0), int(n)))
-        self.n, self.p = int(n), owner.p
-        self.row_lo, self.n_global = 0, int(n)
+        self._adopt(n, owner.p)
 
     def set_data_rows_affine(self, owner, row0, n, shift=None, scale=None):
         """``(owner[row0:row0 + n] - shift) / scale`` becomes this context's data matrix
@@ -523,8 +529,7 @@ class Context(object):
         _check(self.lib.aa_set_data_rows_affine(self.h, owner.h, int(row0), int(n),
                                                 None if shift is None else _ptr(shift),
                                                 None if scale is None else _ptr(scale)))
-        self.n, self.p = int(n), owner.p
-        self.row_lo, self.n_global = 0, int(n)
+        self._adopt(n, owner.p)
 
     def set_data_take(self, owner, indices=None):
         """Rows ``indices`` (any order, duplicates allowed; None: all rows in order) of ``owner``'s resident data
@@ -539,16 +544,13 @@ class Context(object):
                 raise ValueError("a 1-D index array expected; got shape %r" % (idx.shape,))
             n, ptr = idx.shape[0], idx.ctypes.data_as(ctypes.POINTER(ctypes.c_long))
         _check(self.lib.aa_set_data_take(self.h, owner.h, ptr, int(n)))
-        self.n, self.p = int(n), owner.p
-        self.row_lo, self.n_global = 0, int(n)
+        self._adopt(n, owner.p)
 
     def _set_features_resident(self, owner, call, what):
         if self.dtype_code != AA_F64:
             raise ValueError("the implicit %s kernel needs a float64 context" % what)
         _check(call())
-        self.n, self.p = owner.n, owner.n
-        self.form = FORM_KERNEL
-        self.implicit = True
+        self._adopt(owner.n, owner.n, implicit=True)
 
     def set_rbf_features_resident(self, owner, gamma):
         """set_rbf_features with the rows of ``owner``'s resident data matrix as the features
@@ -581,9 +583,7 @@ class Context(object):
             raise ValueError("the implicit RBF kernel needs a float64 context")
         n, p = X.shape
         _check(self.lib.aa_set_rbf_features(self.h, _ptr(X), n, p, p, float(gamma)))
-        self.n, self.p = n, n
-        self.form = FORM_KERNEL
-        self.implicit = True
+        self._adopt(n, n, implicit=True)
 
     def set_poly_features(self, X, gamma, coef0, degree):
         """The implicit polynomial kernel (gamma x_i.x_j + coef0)^degree of the rows of X as this context's
@@ -595,9 +595,7 @@ class Context(object):
             raise ValueError("the implicit polynomial kernel needs a float64 context")
         n, p = X.shape
         _check(self.lib.aa_set_poly_features(self.h, _ptr(X), n, p, p, float(gamma), float(coef0), int(degree)))
-        self.n, self.p = n, n
-        self.form = FORM_KERNEL
-        self.implicit = True
+        self._adopt(n, n, implicit=True)
 
     def set_linear_kernel(self, on):
         """The resident data matrix X stands in for the kernel K = X X' of KernelAA
@@ -623,7 +621,7 @@ class Context(object):
         _check(self.lib.aa_set_data_weighted(
             self.h, raw.ctypes.data_as(_vp), host, n_total, p_full, p_full, None if w is None else _ptr(w),
             int(row0), int(n), valid.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), ctypes.byref(pv)))
-        self.n, self.p = int(n), int(pv.value)
+        self._adopt(n, pv.value)
         return valid.astype(bool)
 
     def get_data(self):

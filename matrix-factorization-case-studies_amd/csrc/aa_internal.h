@@ -101,6 +101,14 @@ struct DevBuf {
     }
     template <class T> T *as() const { return reinterpret_cast<T *>(p); }
 };
+// a DevBuf that lives for one call: released on scope exit, so its function returns through AA_CHECK /
+// AA_CHECK_HIP wherever it fails.  (The members of Ctx are plain DevBufs: aa_ctx_destroy owns them.)
+struct ScopedDevBuf : DevBuf {
+    ScopedDevBuf() = default;
+    ScopedDevBuf(const ScopedDevBuf &) = delete;
+    ScopedDevBuf &operator=(const ScopedDevBuf &) = delete;
+    ~ScopedDevBuf() { release(); }
+};
 
 // ------------------------------------------------------------------ scalars
 // Device-resident scalar state of the dictionary SPG solver and the projection
@@ -341,6 +349,10 @@ struct Ctx {
     bool products_valid = false;               // P (= CX) and Gr (= C XX' or C K) match Ct
     bool ckz_valid = false;                    // gramState's C K Z matches Ct and H
 };
+
+// a stored matrix in data form: X holds the n x p rows themselves -- not a kernel matrix, and not nothing
+// behind an implicit kernel.  (An implicit kernel always comes with form == AA_FORM_KERNEL: install_begin.)
+inline bool has_stored_data(const Ctx *c) { return c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA; }
 
 // ------------------------------------------------------------------ kernels_gemm.hip
 // out[KP][p_pad] (double) = sum_r A[r][i] * X[r][c];  A tall double, X T.

@@ -680,42 +680,116 @@ int aa_set_linear_kernel(aa_ctx *h, int on)
     return AA_OK;
 }
 
-// the features of an implicit kernel: the kernel form of the algorithm on a virtual n x n matrix; feat_ld: the
-// leading dimension of the zero-padded feature buffer, chosen by the kernels that read it.  `owner` (X == nullptr):
-// the features are the rows of its resident data matrix, converted on the device
+// ------------------------------------------------------------------ installing data
+// Every entry point that gives a context its matrix is: its argument checks, install_begin, its fill of the
+// new buffer, install_commit.  Between the two the context holds no data, so a fill that fails leaves it
+// that way and never half-installed; a call refused by its argument checks has not touched the context.
+struct Install {
+    int form = AA_FORM_DATA;
+    long n = 0, p = 0, p_pad = 0;              // n_pad is roundup(n, 128) everywhere
+    long n_global = 0, row_offset = 0;
+    int implicit = 0;                          // IMPLICIT_*: feat [n_pad + slack][feat_ld] and featNorm instead of X
+    long feat_p = 0, feat_ld = 0;
+    const DevBuf *borrow = nullptr;            // aa_share_data: X aliases this buffer instead of being allocated
+};
+
+// the common shape: n rows of p columns of the context's own, data form, single rank
+static Install install_rows(long n, long p, long p_pad)
+{
+    Install in;
+    in.n = in.n_global = n;
+    in.p = p;
+    in.p_pad = p_pad;
+    return in;
+}
+
+// what a new matrix resets -- everything that belongs to the rows, the kernel or the factors of the old one
+// (buffers other than X / feat / featNorm stay allocated) -- and the zero-filled buffer it goes into
+static int install_begin(Ctx *c, const Install &in)
+{
+    c->have_data = false;
+    c->form = in.form;
+    c->linear_kernel = false;
+    c->implicit_kernel = in.implicit;
+    c->cross_s = 0;                            // a reference set belongs to the rows it was set for
+    c->n = in.n;
+    c->p = in.p;
+    c->n_pad = round_up(in.n, 128);
+    c->p_pad = in.p_pad;
+    c->n_global = in.n_global;
+    c->row_offset = in.row_offset;
+    c->have_trace = false;
+    c->k = 0;                                  // forces (re)allocation of the factor buffers
+    c->KP = 0;
+    c->have_state = false;
+    c->grams_valid = false;
+    c->qp_iters_valid = false;                 // pass counts and sample order of the previous rows
+    c->qp_perm_ready = false;
+    c->qp_perm_n = 0;
+    c->X.release();                            // (an implicit kernel: nothing stands in for K)
+    if (in.borrow) {
+        c->X.p = in.borrow->p;                 // read-only everywhere in the solver
+        c->X.bytes = in.borrow->bytes;
+        c->X.borrowed = true;
+        return AA_OK;
+    }
+    if (!in.implicit)
+        return c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));
+    c->feat_p = in.feat_p;
+    c->feat_ld = in.feat_ld;
+    AA_CHECK(c->feat.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->feat_ld * sizeof(double)));
+    AA_CHECK_HIP(ctx_memset(c, c->feat.p, 0, c->feat.bytes));
+    return c->featNorm.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * sizeof(double));
+}
+
+// after the fill and whatever it waits for have succeeded
+static void install_commit(Ctx *c) { c->have_data = true; }
+
+// What the entry points that read another context's matrix ask of the pair: two contexts, the owner holding a
+// stored matrix in data form (kernel_form_too: or a stored kernel matrix), both single rank, element types that
+// go together, one device.  `who` names the entry point; `code` is what its family returns for the rank and
+// element-type refusals (AA_ERR_ARG: rows / take / share, AA_ERR_STATE: features).
+enum OwnerDtype { DTYPE_SAME = 0, DTYPE_MAY_WIDEN = 1, DTYPE_INTO_F64 = 2 /* ctx float64, owner of either type */ };
+static int check_owner(const aa_ctx *h, const aa_ctx *owner, const char *who, int code, OwnerDtype rule,
+                       bool kernel_form_too = false)
+{
+    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "%s: two different contexts needed", who);
+    const Ctx *c = &h->c, *o = &owner->c;
+    AA_REQUIRE(kernel_form_too ? o->have_data && !o->implicit_kernel : has_stored_data(o), AA_ERR_STATE,
+               "%s: the owner holds no stored %s", who, kernel_form_too ? "matrix" : "data matrix (data form)");
+    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, code, "%s is single-rank", who);
+    static const char *const needed[] = {"same data type needed",
+                                         "equal data types, or a float32 owner widened into a float64 context",
+                                         "a float64 context needed"};
+    const bool widens = rule == DTYPE_MAY_WIDEN && o->dtype == AA_F32 && c->dtype == AA_F64;
+    AA_REQUIRE(rule == DTYPE_INTO_F64 ? c->dtype == AA_F64 : (o->dtype == c->dtype || widens), code, "%s: %s", who,
+               needed[rule]);
+    AA_REQUIRE(o->device == c->device, AA_ERR_ARG, "%s: same device needed", who);
+    return AA_OK;
+}
+
+// the features of an implicit kernel: the kernel form of the algorithm (/k conventions, tr K) on a virtual n x n
+// matrix; feat_ld: the leading dimension of the zero-padded feature buffer, chosen by the kernels that read it.
+// `owner` (X == nullptr): the features are the rows of its resident data matrix, converted on the device
 static int set_implicit_features(Ctx *c, const double *X, long n, long p, long ld, long feat_ld, int kind,
                                  const Ctx *owner = nullptr)
 {
     AA_CHECK_HIP(hipSetDevice(c->device));
-    c->form = AA_FORM_KERNEL;                    // the kernel form of the algorithm (/k conventions, tr K)
-    c->linear_kernel = false;
-    c->implicit_kernel = kind;
-    c->n = n;
-    c->p = n;                                    // the (virtual) kernel matrix is n x n
-    c->n_pad = round_up(n, 128);
-    c->p_pad = c->n_pad;
-    c->n_global = n;
-    c->row_offset = 0;
-    c->X.release();                              // nothing stands in for K
-    c->feat_p = p;
-    c->feat_ld = feat_ld;
-    AA_CHECK(c->feat.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->feat_ld * sizeof(double)));
-    AA_CHECK_HIP(ctx_memset(c, c->feat.p, 0, c->feat.bytes));
+    Install in = install_rows(n, n, round_up(n, 128));
+    in.form = AA_FORM_KERNEL;
+    in.implicit = kind;
+    in.feat_p = p;
+    in.feat_ld = feat_ld;
+    AA_CHECK(install_begin(c, in));
     if (owner)
         AA_CHECK(launch_features_from_data(c, owner->X.p, owner->dtype, owner->p_pad, n, p, c->feat.as<double>(),
                                            c->feat_ld));
     else
         AA_CHECK_HIP(ctx_memcpy2d(c, c->feat.p, (size_t)c->feat_ld * sizeof(double), X, (size_t)ld * sizeof(double),
                                   (size_t)p * sizeof(double), (size_t)n, hipMemcpyHostToDevice));
-    AA_CHECK(c->featNorm.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * sizeof(double)));
     AA_CHECK(launch_rbf_norms(c));
-    c->have_data = true;
-    c->have_trace = false;
-    c->k = 0;
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
-    if (owner) AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // the owner has been read: it may go
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // the owner has been read: it may go
+    install_commit(c);
     return AA_OK;
 }
 
@@ -751,39 +825,26 @@ int aa_set_poly_features(aa_ctx *h, const double *X, long n, long p, long ld, do
     return set_implicit_features(c, X, n, p, ld, round_up(p, 32), IMPLICIT_POLY);
 }
 
-// what both resident forms ask of the two contexts
-static int check_feature_owner(const aa_ctx *h, const aa_ctx *owner, const char *what)
-{
-    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
-    const Ctx *c = &h->c, *o = &owner->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_STATE,
-               "the implicit %s kernel is single-rank", what);
-    AA_REQUIRE(c->dtype == AA_F64, AA_ERR_STATE, "the implicit %s kernel needs a float64 context", what);
-    AA_REQUIRE(!o->implicit_kernel && o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE,
-               "the owner holds no stored data matrix (data form)");
-    AA_REQUIRE(o->device == c->device, AA_ERR_ARG, "same device needed");
-    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
-    return AA_OK;
-}
-
 int aa_set_rbf_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma)
 {
-    AA_CHECK(check_feature_owner(h, owner, "RBF"));
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    AA_CHECK(check_owner(h, owner, "aa_set_rbf_features_resident", AA_ERR_STATE, DTYPE_INTO_F64));
     Ctx *c = &h->c;
     const Ctx *o = &owner->c;
+    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
+    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
     c->rbf_gamma = gamma;
     return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 2), IMPLICIT_RBF, o);
 }
 
 int aa_set_poly_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma, double coef0, int degree)
 {
-    AA_CHECK(check_feature_owner(h, owner, "polynomial"));
+    AA_CHECK(check_owner(h, owner, "aa_set_poly_features_resident", AA_ERR_STATE, DTYPE_INTO_F64));
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
     AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
                "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
                degree);
-    Ctx *c = &h->c;
-    const Ctx *o = &owner->c;
     c->poly = PolyKernel{gamma, coef0, degree};
     return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 32), IMPLICIT_POLY, o);
 }
@@ -814,20 +875,13 @@ int aa_ctx_allreduce_host(aa_ctx *h, double *buf, int count, int op)
     Ctx *c = &h->c;
     if ((c->world <= 1 && !c->force_comm) || count == 0) return AA_OK;
     AA_CHECK_HIP(hipSetDevice(c->device));
-    DevBuf tmp;
+    ScopedDevBuf tmp;
     AA_CHECK(tmp.alloc((size_t)count * sizeof(double)));
     AA_CHECK_HIP(hipMemcpyAsync(tmp.p, buf, (size_t)count * sizeof(double), hipMemcpyHostToDevice, c->stream));
-    int rc = comm_allreduce(c, tmp.as<double>(), count, op);
-    if (rc == AA_OK) {
-        hipError_t e = hipMemcpyAsync(buf, tmp.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream);
-        if (e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        if (e != hipSuccess) {
-            set_error("allreduce_host copy back: %s", hipGetErrorString(e));
-            rc = AA_ERR_HIP;
-        }
-    }
-    tmp.release();
-    return rc;
+    AA_CHECK(comm_allreduce(c, tmp.as<double>(), count, op));
+    AA_CHECK_HIP(hipMemcpyAsync(buf, tmp.p, (size_t)count * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    return AA_OK;
 }
 
 int aa_set_data(aa_ctx *h, const void *X, int host_dtype, long n, long p, long ld, int form,
@@ -843,20 +897,12 @@ int aa_set_data(aa_ctx *h, const void *X, int host_dtype, long n, long p, long l
         AA_REQUIRE((c->world == 1 && !c->force_comm) && n == p && n_global == n && row_offset == 0, AA_ERR_ARG,
                    "kernel form needs a square matrix on a single rank");
     AA_REQUIRE(n_global >= n && row_offset >= 0 && row_offset + n <= n_global, AA_ERR_ARG, "bad shard");
-    c->form = form;
-    c->linear_kernel = false;
-    c->implicit_kernel = 0;
-    c->cross_s = 0;                              // a reference set belongs to the rows it was set for
-    c->n = n;
-    c->p = p;
-    c->n_pad = round_up(n, 128);
-    c->p_pad = round_up(p, 128);
-    if (form == AA_FORM_KERNEL) c->p_pad = c->n_pad;
-    c->n_global = n_global;
-    c->row_offset = row_offset;
+    Install in = install_rows(n, p, round_up(p, 128));   // (kernel form: p == n, so p_pad == n_pad)
+    in.form = form;
+    in.n_global = n_global;
+    in.row_offset = row_offset;
+    AA_CHECK(install_begin(c, in));
     const size_t es = esize(c);
-    c->X.release();
-    AA_CHECK(c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * es));
     const size_t hes = host_dtype == AA_F32 ? 4 : 8;
     if (host_dtype == c->dtype) {
         AA_CHECK_HIP(ctx_memcpy2d(c, c->X.p, (size_t)c->p_pad * es, X, (size_t)ld * hes, (size_t)p * es,
@@ -882,100 +928,50 @@ int aa_set_data(aa_ctx *h, const void *X, int host_dtype, long n, long p, long l
                                      (size_t)rows, hipMemcpyHostToDevice));
         }
     }
-    c->have_data = true;
-    c->have_trace = false;
-    c->k = 0;   // forces (re)allocation of the factor buffers
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
+    install_commit(c);
     return AA_OK;
 }
 
 int aa_share_data(aa_ctx *h, const aa_ctx *owner)
 {
-    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    AA_CHECK(check_owner(h, owner, "aa_share_data", AA_ERR_ARG, DTYPE_SAME, /* kernel_form_too */ true));
     Ctx *c = &h->c;
     const Ctx *o = &owner->c;
-    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_share_data: implicit kernels are not shared");
-    AA_REQUIRE(o->have_data, AA_ERR_STATE, "the owner holds no data matrix");
-    AA_REQUIRE(o->device == c->device && o->dtype == c->dtype, AA_ERR_ARG,
-               "aa_share_data: same device and same data type needed");
-    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
-               "aa_share_data is single-rank");
     AA_CHECK_HIP(hipSetDevice(c->device));
-    c->X.release();
-    c->X.p = o->X.p;                    // read-only everywhere in the solver
-    c->X.bytes = o->X.bytes;
-    c->X.borrowed = true;
-    c->form = o->form;
-    c->linear_kernel = false;
-    c->n = o->n;
-    c->p = o->p;
-    c->n_pad = o->n_pad;
-    c->p_pad = o->p_pad;
-    c->n_global = o->n_global;
-    c->row_offset = o->row_offset;
-    c->have_data = true;
-    c->have_trace = o->have_trace;
+    Install in = install_rows(o->n, o->p, o->p_pad);
+    in.form = o->form;
+    in.n_global = o->n_global;
+    in.row_offset = o->row_offset;
+    in.borrow = &o->X;
+    AA_CHECK(install_begin(c, in));
+    c->have_trace = o->have_trace;             // the owner's trace pass serves every context that shares its matrix
     c->trace = o->trace;
-    c->k = 0;
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
+    install_commit(c);
     return AA_OK;
 }
 
 int aa_set_data_rows(aa_ctx *h, const aa_ctx *owner, long row0, long n)
 {
-    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    AA_CHECK(check_owner(h, owner, "aa_set_data_rows", AA_ERR_ARG, DTYPE_SAME));
     Ctx *c = &h->c;
     const Ctx *o = &owner->c;
-    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_rows: no stored matrix behind an implicit kernel");
-    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
-    AA_REQUIRE(o->device == c->device && o->dtype == c->dtype, AA_ERR_ARG,
-               "aa_set_data_rows: same device and same data type needed");
-    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
-               "aa_set_data_rows is single-rank");
     AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
                row0 + n, o->n);
     AA_CHECK_HIP(hipSetDevice(c->device));
-    c->form = AA_FORM_DATA;
-    c->linear_kernel = false;
-    c->implicit_kernel = 0;
-    c->cross_s = 0;
-    c->n = n;
-    c->p = o->p;
-    c->n_pad = round_up(n, 128);
-    c->p_pad = o->p_pad;
-    c->n_global = n;
-    c->row_offset = 0;
-    c->have_data = false;
-    const size_t es = esize(c);
-    c->X.release();
-    AA_CHECK(c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * es));   // zero filled: the padding of aa_set_data
+    AA_CHECK(install_begin(c, install_rows(n, o->p, o->p_pad)));
     // rows are contiguous with the same leading dimension, their padding columns already zero
+    const size_t es = esize(c);
     AA_CHECK_HIP(ctx_memcpy(c, c->X.p, reinterpret_cast<const unsigned char *>(o->X.p) + (size_t)row0 * o->p_pad * es,
                             (size_t)n * c->p_pad * es, hipMemcpyDeviceToDevice));
-    c->have_data = true;
-    c->have_trace = false;
-    c->k = 0;   // forces (re)allocation of the factor buffers
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
+    install_commit(c);
     return AA_OK;
 }
 
 int aa_set_data_rows_affine(aa_ctx *h, const aa_ctx *owner, long row0, long n, const double *shift, const double *scale)
 {
-    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    AA_CHECK(check_owner(h, owner, "aa_set_data_rows_affine", AA_ERR_ARG, DTYPE_SAME));
     Ctx *c = &h->c;
     const Ctx *o = &owner->c;
-    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_rows_affine: no stored matrix behind an implicit kernel");
-    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
-    AA_REQUIRE(o->device == c->device && o->dtype == c->dtype, AA_ERR_ARG,
-               "aa_set_data_rows_affine: same device and same data type needed");
-    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
-               "aa_set_data_rows_affine is single-rank");
     AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
                row0 + n, o->n);
     // refused before anything of ctx is released: a zero or non-finite divisor, a non-finite shift
@@ -986,100 +982,39 @@ int aa_set_data_rows_affine(aa_ctx *h, const aa_ctx *owner, long row0, long n, c
                    "aa_set_data_rows_affine: shift[%ld] = %g is not finite", j, shift[j]);
     }
     AA_CHECK_HIP(hipSetDevice(c->device));
-    c->form = AA_FORM_DATA;
-    c->linear_kernel = false;
-    c->implicit_kernel = 0;
-    c->cross_s = 0;
-    c->n = n;
-    c->p = o->p;
-    c->n_pad = round_up(n, 128);
-    c->p_pad = o->p_pad;
-    c->n_global = n;
-    c->row_offset = 0;
-    c->have_data = false;
-    const size_t es = esize(c);
-    c->X.release();
-    AA_CHECK(c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * es));   // zero filled: the padding of aa_set_data
-    DevBuf coef;                                                              // shift | scale, p_pad doubles each
-    int rc = coef.alloc((size_t)2 * c->p_pad * sizeof(double));
-    hipError_t e = hipSuccess;
-    double *dshift = shift ? coef.as<double>() : nullptr, *dscale = scale ? coef.as<double>() + c->p_pad : nullptr;
-    if (rc == AA_OK && shift) e = ctx_memcpy(c, dshift, shift, (size_t)c->p * sizeof(double), hipMemcpyHostToDevice);
-    if (rc == AA_OK && e == hipSuccess && scale)
-        e = ctx_memcpy(c, dscale, scale, (size_t)c->p * sizeof(double), hipMemcpyHostToDevice);
-    if (rc == AA_OK && e == hipSuccess) rc = launch_affine_rows(c, o->X.p, row0, dshift, dscale);
-    if (rc == AA_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-    coef.release();
-    if (rc == AA_OK && e != hipSuccess) {
-        set_error("aa_set_data_rows_affine: %s", hipGetErrorString(e));
-        rc = AA_ERR_HIP;
-    }
-    AA_CHECK(rc);
-    c->have_data = true;
-    c->have_trace = false;
-    c->k = 0;   // forces (re)allocation of the factor buffers
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
+    ScopedDevBuf coef;                                                        // shift | scale, p_pad doubles each
+    AA_CHECK(coef.alloc((size_t)2 * o->p_pad * sizeof(double)));
+    double *dshift = shift ? coef.as<double>() : nullptr, *dscale = scale ? coef.as<double>() + o->p_pad : nullptr;
+    if (shift) AA_CHECK_HIP(ctx_memcpy(c, dshift, shift, (size_t)o->p * sizeof(double), hipMemcpyHostToDevice));
+    if (scale) AA_CHECK_HIP(ctx_memcpy(c, dscale, scale, (size_t)o->p * sizeof(double), hipMemcpyHostToDevice));
+    AA_CHECK(install_begin(c, install_rows(n, o->p, o->p_pad)));
+    AA_CHECK(launch_affine_rows(c, o->X.p, row0, dshift, dscale));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    install_commit(c);
     return AA_OK;
 }
 
 int aa_set_data_take(aa_ctx *h, const aa_ctx *owner, const long *idx, long n)
 {
-    AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "two different contexts needed");
+    AA_CHECK(check_owner(h, owner, "aa_set_data_take", AA_ERR_ARG, DTYPE_MAY_WIDEN));
     Ctx *c = &h->c;
     const Ctx *o = &owner->c;
-    AA_REQUIRE(!o->implicit_kernel, AA_ERR_STATE, "aa_set_data_take: no stored matrix behind an implicit kernel");
-    AA_REQUIRE(o->have_data && o->form == AA_FORM_DATA, AA_ERR_STATE, "the owner holds no data matrix (data form)");
-    AA_REQUIRE(o->device == c->device, AA_ERR_ARG, "aa_set_data_take: same device needed");
-    AA_REQUIRE(o->dtype == c->dtype || (o->dtype == AA_F32 && c->dtype == AA_F64), AA_ERR_ARG,
-               "aa_set_data_take: equal data types, or a float32 owner widened into a float64 context");
-    AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, AA_ERR_ARG,
-               "aa_set_data_take is single-rank");
     AA_REQUIRE(n >= 1 && (idx || n <= o->n), AA_ERR_ARG, "bad row count %ld (the owner holds %ld rows)", n, o->n);
     // refused before anything of ctx is released and before any launch: the gather kernel reads whatever row it is given
     for (long r = 0; idx && r < n; ++r)
         AA_REQUIRE(idx[r] >= 0 && idx[r] < o->n, AA_ERR_ARG, "aa_set_data_take: idx[%ld] = %ld is outside [0, %ld)", r,
                    idx[r], o->n);
     AA_CHECK_HIP(hipSetDevice(c->device));
-    DevBuf didx;
+    ScopedDevBuf didx;
     if (idx) {
         AA_CHECK(didx.alloc((size_t)n * sizeof(long)));
-        hipError_t eu = ctx_memcpy(c, didx.p, idx, (size_t)n * sizeof(long), hipMemcpyHostToDevice);
-        if (eu != hipSuccess) {
-            didx.release();
-            set_error("aa_set_data_take: %s", hipGetErrorString(eu));
-            return AA_ERR_HIP;
-        }
+        AA_CHECK_HIP(ctx_memcpy(c, didx.p, idx, (size_t)n * sizeof(long), hipMemcpyHostToDevice));
     }
-    c->form = AA_FORM_DATA;
-    c->linear_kernel = false;
-    c->implicit_kernel = 0;
-    c->cross_s = 0;
-    c->n = n;
-    c->p = o->p;
-    c->n_pad = round_up(n, 128);
-    c->p_pad = round_up(o->p, 128);              // the context's own: a widened copy need not share the owner's
-    c->n_global = n;
-    c->row_offset = 0;
-    c->have_data = false;
-    c->X.release();
-    int rc = c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));   // zero filled: the padding of aa_set_data
-    hipError_t e = hipSuccess;
-    if (rc == AA_OK) rc = launch_gather_rows(c, o->X.p, o->dtype, o->p_pad, idx ? didx.as<long>() : (const long *)nullptr);
-    if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
-    didx.release();
-    if (rc == AA_OK && e != hipSuccess) {
-        set_error("aa_set_data_take: %s", hipGetErrorString(e));
-        rc = AA_ERR_HIP;
-    }
-    AA_CHECK(rc);
-    c->have_data = true;
-    c->have_trace = false;
-    c->k = 0;   // forces (re)allocation of the factor buffers
-    c->KP = 0;
-    c->have_state = false;
-    c->grams_valid = false;
+    // p_pad is the context's own: a widened copy need not share the owner's
+    AA_CHECK(install_begin(c, install_rows(n, o->p, round_up(o->p, 128))));
+    AA_CHECK(launch_gather_rows(c, o->X.p, o->dtype, o->p_pad, idx ? didx.as<long>() : (const long *)nullptr));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    install_commit(c);
     return AA_OK;
 }
 
@@ -1087,32 +1022,22 @@ int aa_data_column_moments(aa_ctx *h, double *mean, double *var)
 {
     AA_REQUIRE(h, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_data_column_moments: no stored matrix behind an implicit kernel");
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA, AA_ERR_STATE, "no data matrix (data form)");
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "aa_data_column_moments: no stored data matrix (data form)");
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "aa_data_column_moments is single-rank");
     if (!mean && !var) return AA_OK;
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(join_side(c));
     long nslab = 0;
     (void)moment_slab_rows(c->n, c->p_pad, &nslab);
-    DevBuf partial, mom;                                                      // mom: mean | var, p_pad doubles each
-    int rc = partial.alloc((size_t)nslab * c->p_pad * sizeof(double));
-    if (rc == AA_OK) rc = mom.alloc((size_t)2 * c->p_pad * sizeof(double));
-    if (rc == AA_OK)
-        rc = launch_col_moments(c, partial.as<double>(), mom.as<double>(), var ? mom.as<double>() + c->p_pad : nullptr);
-    hipError_t e = hipSuccess;
-    if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
-    if (rc == AA_OK && e == hipSuccess && mean)
-        e = ctx_memcpy(c, mean, mom.p, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost);
-    if (rc == AA_OK && e == hipSuccess && var)
-        e = ctx_memcpy(c, var, mom.as<double>() + c->p_pad, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost);
-    partial.release();
-    mom.release();
-    if (rc == AA_OK && e != hipSuccess) {
-        set_error("aa_data_column_moments: %s", hipGetErrorString(e));
-        rc = AA_ERR_HIP;
-    }
-    return rc;
+    ScopedDevBuf partial, mom;                                                // mom: mean | var, p_pad doubles each
+    AA_CHECK(partial.alloc((size_t)nslab * c->p_pad * sizeof(double)));
+    AA_CHECK(mom.alloc((size_t)2 * c->p_pad * sizeof(double)));
+    double *dvar = var ? mom.as<double>() + c->p_pad : nullptr;
+    AA_CHECK(launch_col_moments(c, partial.as<double>(), mom.as<double>(), dvar));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (mean) AA_CHECK_HIP(ctx_memcpy(c, mean, mom.p, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost));
+    if (var) AA_CHECK_HIP(ctx_memcpy(c, var, dvar, (size_t)c->p * sizeof(double), hipMemcpyDeviceToHost));
+    return AA_OK;
 }
 
 int aa_set_data_weighted(aa_ctx *h, const void *raw, int host_dtype, long n_total, long p_full, long ld,
@@ -1128,94 +1053,53 @@ int aa_set_data_weighted(aa_ctx *h, const void *raw, int host_dtype, long n_tota
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "preprocessing entry point is single-rank");
     const size_t hes = host_dtype == AA_F32 ? 4 : 8;
-    DevBuf draw, dflag, didx, dw;
-    int rc = draw.alloc((size_t)n_total * p_full * hes);
-    if (rc == AA_OK) rc = dflag.alloc((size_t)p_full);
-    if (rc == AA_OK && col_weight) rc = dw.alloc((size_t)p_full * sizeof(double));
-    if (rc != AA_OK) { draw.release(); dflag.release(); dw.release(); return rc; }
-    hipError_t e = ctx_memcpy2d(c, draw.p, (size_t)p_full * hes, raw, (size_t)ld * hes, (size_t)p_full * hes,
-                               (size_t)n_total, hipMemcpyHostToDevice);
-    if (e == hipSuccess && col_weight)
-        e = ctx_memcpy(c, dw.p, col_weight, (size_t)p_full * sizeof(double), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        // the mask is taken on the weighted field (run_hadisst_aa.py:133,201)
-        rc = launch_col_has_nan(c, draw.p, host_dtype, p_full, n_total, p_full,
-                                col_weight ? dw.as<double>() : (const double *)nullptr, dflag.as<unsigned char>());
-        if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
-    }
+    ScopedDevBuf draw, dflag, didx, dw;
+    AA_CHECK(draw.alloc((size_t)n_total * p_full * hes));
+    AA_CHECK(dflag.alloc((size_t)p_full));
+    if (col_weight) AA_CHECK(dw.alloc((size_t)p_full * sizeof(double)));
+    AA_CHECK_HIP(ctx_memcpy2d(c, draw.p, (size_t)p_full * hes, raw, (size_t)ld * hes, (size_t)p_full * hes,
+                              (size_t)n_total, hipMemcpyHostToDevice));
+    if (col_weight) AA_CHECK_HIP(ctx_memcpy(c, dw.p, col_weight, (size_t)p_full * sizeof(double), hipMemcpyHostToDevice));
+    const double *w = col_weight ? dw.as<double>() : nullptr;
+    // the mask is taken on the weighted field (run_hadisst_aa.py:133,201)
+    AA_CHECK(launch_col_has_nan(c, draw.p, host_dtype, p_full, n_total, p_full, w, dflag.as<unsigned char>()));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     std::vector<unsigned char> flags((size_t)p_full);
-    if (rc == AA_OK && e == hipSuccess) e = ctx_memcpy(c, flags.data(), dflag.p, (size_t)p_full, hipMemcpyDeviceToHost);
+    AA_CHECK_HIP(ctx_memcpy(c, flags.data(), dflag.p, (size_t)p_full, hipMemcpyDeviceToHost));
     std::vector<int> idx;
-    if (rc == AA_OK && e == hipSuccess) {
-        idx.reserve((size_t)p_full);
-        for (long q = 0; q < p_full; ++q) {
-            valid[q] = flags[(size_t)q] ? 0 : 1;
-            if (!flags[(size_t)q]) idx.push_back((int)q);
-        }
-        *p_valid = (long)idx.size();
-        if (idx.empty()) {
-            set_error("every column of the field holds a NaN");
-            rc = AA_ERR_ARG;
-        }
+    idx.reserve((size_t)p_full);
+    for (long q = 0; q < p_full; ++q) {
+        valid[q] = flags[(size_t)q] ? 0 : 1;
+        if (!flags[(size_t)q]) idx.push_back((int)q);
     }
-    if (rc == AA_OK && e == hipSuccess) {
-        const long p = (long)idx.size();
-        c->form = AA_FORM_DATA;
-        c->linear_kernel = false;
-        c->n = n;
-        c->p = p;
-        c->n_pad = round_up(n, 128);
-        c->p_pad = round_up(p, 128);
-        c->n_global = n;
-        c->row_offset = 0;
-        c->X.release();
-        rc = c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));
-        if (rc == AA_OK) rc = didx.alloc(idx.size() * sizeof(int));
-        if (rc == AA_OK) e = ctx_memcpy(c, didx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice);
-        if (rc == AA_OK && e == hipSuccess)
-            rc = launch_gather_weight(c, draw.p, host_dtype, p_full, row0, n, didx.as<int>(), p,
-                                      col_weight ? dw.as<double>() : (const double *)nullptr);
-        if (rc == AA_OK && e == hipSuccess) e = hipStreamSynchronize(c->stream);
-        c->have_data = rc == AA_OK && e == hipSuccess;
-        c->have_trace = false;
-        c->k = 0;
-        c->KP = 0;
-        c->have_state = false;
-        c->grams_valid = false;
-    }
-    draw.release();
-    dflag.release();
-    didx.release();
-    dw.release();
-    if (rc == AA_OK && e != hipSuccess) {
-        set_error("aa_set_data_weighted: %s", hipGetErrorString(e));
-        rc = AA_ERR_HIP;
-    }
-    return rc;
+    const long p = (long)idx.size();
+    *p_valid = p;
+    AA_REQUIRE(p > 0, AA_ERR_ARG, "every column of the field holds a NaN");
+    AA_CHECK(didx.alloc(idx.size() * sizeof(int)));
+    AA_CHECK_HIP(ctx_memcpy(c, didx.p, idx.data(), idx.size() * sizeof(int), hipMemcpyHostToDevice));
+    AA_CHECK(install_begin(c, install_rows(n, p, round_up(p, 128))));
+    AA_CHECK(launch_gather_weight(c, draw.p, host_dtype, p_full, row0, n, didx.as<int>(), p, w));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    install_commit(c);
+    return AA_OK;
 }
 
 int aa_get_data(aa_ctx *h, double *out, long ld)
 {
     AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
+    // any stored matrix, the kernel form's too (not has_stored_data)
     AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_get_data: no stored matrix behind an implicit kernel");
     AA_REQUIRE(c->have_data, AA_ERR_STATE, "no data");
     AA_REQUIRE(ld >= c->p, AA_ERR_ARG, "ld < p");
     AA_CHECK_HIP(hipSetDevice(c->device));
-    DevBuf tmp;
+    ScopedDevBuf tmp;
     AA_CHECK(tmp.alloc((size_t)c->n * c->p * sizeof(double)));
-    int rc = launch_data_to_double(c, tmp.as<double>());
-    hipError_t e = hipSuccess;
-    if (rc == AA_OK) e = hipStreamSynchronize(c->stream);
-    if (rc == AA_OK && e == hipSuccess)
-        e = ctx_memcpy2d(c, out, (size_t)ld * sizeof(double), tmp.p, (size_t)c->p * sizeof(double),
-                        (size_t)c->p * sizeof(double), (size_t)c->n, hipMemcpyDeviceToHost);
-    tmp.release();
-    if (rc == AA_OK && e != hipSuccess) {
-        set_error("aa_get_data: %s", hipGetErrorString(e));
-        rc = AA_ERR_HIP;
-    }
-    return rc;
+    AA_CHECK(launch_data_to_double(c, tmp.as<double>()));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy2d(c, out, (size_t)ld * sizeof(double), tmp.p, (size_t)c->p * sizeof(double),
+                              (size_t)c->p * sizeof(double), (size_t)c->n, hipMemcpyDeviceToHost));
+    return AA_OK;
 }
 
 int aa_data_trace(aa_ctx *h, double *trace)
@@ -1651,7 +1535,7 @@ int aa_gpnh_set_factors(aa_ctx *h, int k, const double *Wt, long ld, const doubl
     AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
     Ctx *c = &h->c;
     AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_REQUIRE(c->form == AA_FORM_DATA, AA_ERR_STATE, "GPNH needs a data matrix");
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "GPNH needs a data matrix");
     AA_CHECK(ensure_problem(c, k));
     if (Wt) {
         AA_REQUIRE(ld >= c->p, AA_ERR_ARG, "ld < p");
@@ -1969,7 +1853,7 @@ int aa_slots_begin(aa_ctx *h, int R, int k, const aa_iter_params *ip, const aa_s
                "slots: delta != 0 needs the scale-factor SPG parameters (memory <= 16)");
     Ctx *c = &h->c;
     AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->linear_kernel, AA_ERR_STATE, "AA slots need a data matrix");
+    AA_REQUIRE(has_stored_data(c) && !c->linear_kernel, AA_ERR_STATE, "AA slots need a data matrix");
     AA_REQUIRE(c->world <= 1 && !c->force_comm, AA_ERR_STATE, "restart slots are single-rank");
     // R k <= 32: the tall kernels sum a column's rows in KP-dependent interleaved chains, so the slots
     // must run the kernels a single fit of k <= 16 components runs (KP = 32) to get its bits
@@ -2222,7 +2106,7 @@ int aa_gpnh_slots_begin(aa_ctx *h, int R, int k, const aa_gpnh_params *gp, const
     AA_REQUIRE(h && gp && qp, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA, AA_ERR_STATE, "GPNH needs a data matrix");
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "GPNH needs a data matrix");
     AA_REQUIRE(c->world <= 1 && !c->force_comm, AA_ERR_STATE, "restart slots are single-rank");
     AA_REQUIRE(R >= 1 && k >= 1 && k <= 32 && R * k <= AA_MAX_K && R <= 32, AA_ERR_ARG,
                "slots: R = %d restarts of k = %d components do not fit", R, k);
@@ -2339,8 +2223,7 @@ int aa_gpnh_residual_scores(aa_ctx *h, double *col_sse, double *row_sse, double 
     Ctx *c = &h->c;
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG,
                "aa_gpnh_residual_scores is single-rank (the multi-rank form needs an all-reduce of the column sums)");
-    AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA, AA_ERR_STATE,
-               "aa_gpnh_residual_scores needs a stored data matrix (data form)");
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "aa_gpnh_residual_scores needs a stored data matrix (data form)");
     AA_REQUIRE(c->have_state && c->gpnh_valid, AA_ERR_STATE, "set_factors first");
     AA_CHECK_HIP(hipSetDevice(c->device));
     return launch_residual_scores(c, col_sse, row_sse, sse);
@@ -2375,7 +2258,7 @@ int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, lon
     AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
+    AA_REQUIRE(has_stored_data(c) && c->dtype == AA_F64, AA_ERR_STATE,
                "aa_set_rbf_reference needs the new samples as a float64 data matrix (aa_set_data)");
     AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
                s, p, c->p, ld, ldv);
@@ -2395,9 +2278,8 @@ int aa_rbf_cross(aa_ctx *h, double *XW)
 {
     AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
     Ctx *c = &h->c;
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k &&
-                   c->cross_kind == IMPLICIT_RBF,
-               AA_ERR_STATE, "aa_set_rbf_reference first");
+    AA_REQUIRE(has_stored_data(c) && c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_RBF, AA_ERR_STATE,
+               "aa_set_rbf_reference first");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(launch_rbf_cross(c));
     c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
@@ -2411,7 +2293,7 @@ int aa_set_poly_reference(aa_ctx *h, int k, const double *XS, long s, long p, lo
     AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit polynomial kernel is single-rank");
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64, AA_ERR_STATE,
+    AA_REQUIRE(has_stored_data(c) && c->dtype == AA_F64, AA_ERR_STATE,
                "aa_set_poly_reference needs the new samples as a float64 data matrix (aa_set_data)");
     AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
                s, p, c->p, ld, ldv);
@@ -2429,9 +2311,8 @@ int aa_poly_cross(aa_ctx *h, double *XW)
 {
     AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
     Ctx *c = &h->c;
-    AA_REQUIRE(c->have_data && c->form == AA_FORM_DATA && c->cross_s > 0 && c->cross_k == c->k &&
-                   c->cross_kind == IMPLICIT_POLY,
-               AA_ERR_STATE, "aa_set_poly_reference first");
+    AA_REQUIRE(has_stored_data(c) && c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_POLY, AA_ERR_STATE,
+               "aa_set_poly_reference first");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(launch_poly_cross(c));
     c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
@@ -2472,8 +2353,8 @@ int aa_kernel_sample_residuals(aa_ctx *h, const double *A, int diag_kind, const 
     AA_REQUIRE(c->have_state && c->gpnh_valid, AA_ERR_STATE, "weights and linear terms first");
     AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the kernel-form residuals are single-rank");
     const bool from_norms = diag_kind == AA_DIAG_POLY || diag_kind == AA_DIAG_LINEAR;
-    AA_REQUIRE(!from_norms || (c->have_data && c->form == AA_FORM_DATA && !c->implicit_kernel && c->dtype == AA_F64),
-               AA_ERR_STATE, "this diagonal is computed from a stored float64 data matrix");
+    AA_REQUIRE(!from_norms || (has_stored_data(c) && c->dtype == AA_F64), AA_ERR_STATE,
+               "this diagonal is computed from a stored float64 data matrix");
     AA_REQUIRE(diag_kind != AA_DIAG_POLY || (c->cross_s > 0 && c->cross_kind == IMPLICIT_POLY), AA_ERR_STATE,
                "aa_set_poly_reference first");
     AA_CHECK_HIP(hipSetDevice(c->device));
@@ -2509,26 +2390,16 @@ int aa_simplex_project_rows(int device, const double *in, double *out, long rows
     AA_CHECK_HIP(hipGetDeviceCount(&n));
     AA_REQUIRE(n > 0 && device >= 0 && device < n, AA_ERR_HIP, "no usable HIP device");
     AA_CHECK_HIP(hipSetDevice(device));
-    DevBuf a, b;
+    ScopedDevBuf a, b;
     const size_t bytes = (size_t)rows * cols * sizeof(double);
     AA_CHECK(a.alloc(bytes));
-    int rc = b.alloc(bytes);
-    if (rc == AA_OK) {
-        // (everything of this stateless entry point runs on the null stream, waited for by the host)
-        hipError_t e = hipMemcpy(a.p, in, bytes, hipMemcpyHostToDevice);
-        if (e == hipSuccess) {
-            rc = launch_simplex_rows_generic(nullptr, a.as<double>(), b.as<double>(), rows, cols);
-            if (rc == AA_OK) e = hipDeviceSynchronize();
-            if (rc == AA_OK && e == hipSuccess) e = hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost);
-        }
-        if (e != hipSuccess) {
-            set_error("simplex_project_rows: %s", hipGetErrorString(e));
-            rc = AA_ERR_HIP;
-        }
-    }
-    a.release();
-    b.release();
-    return rc;
+    AA_CHECK(b.alloc(bytes));
+    // (everything of this stateless entry point runs on the null stream, waited for by the host)
+    AA_CHECK_HIP(hipMemcpy(a.p, in, bytes, hipMemcpyHostToDevice));
+    AA_CHECK(launch_simplex_rows_generic(nullptr, a.as<double>(), b.as<double>(), rows, cols));
+    AA_CHECK_HIP(hipDeviceSynchronize());
+    AA_CHECK_HIP(hipMemcpy(out, b.p, bytes, hipMemcpyDeviceToHost));
+    return AA_OK;
 }
 
 // the scratch contexts of the stateless QP entry, one per device (aa_quad_simplex_spg_batch, aa_qp_kernels)
@@ -2555,35 +2426,19 @@ int aa_quad_simplex_spg_batch(int device, const double *A, const double *B, long
     AA_CHECK_HIP(hipSetDevice(device));
     Ctx *c = &h->c;
     c->qp_iters_valid = false;
-    DevBuf dB, dZ, dI;
+    ScopedDevBuf dB, dZ, dI;
     const size_t extent = (size_t)((k - 1) * stride_j + (n - 1) * stride_t + 1);
-    int rc = dB.alloc(extent * sizeof(double));
-    if (rc == AA_OK) rc = dZ.alloc((size_t)n * k * sizeof(double));
-    if (rc == AA_OK) rc = dI.alloc((size_t)n * sizeof(int));
-    if (rc == AA_OK) {
-        hipError_t e = ctx_memcpy(c, dB.p, B, extent * sizeof(double), hipMemcpyHostToDevice);
-        if (e == hipSuccess) e = ctx_memcpy(c, dZ.p, Z0, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice);
-        if (e != hipSuccess) {
-            set_error("qp batch upload: %s", hipGetErrorString(e));
-            rc = AA_ERR_HIP;
-        }
-    }
-    if (rc == AA_OK)
-        rc = launch_qp(c, A, dB.as<double>(), stride_j, stride_t, nullptr, dZ.as<double>(), k, n, k, params,
-                       dI.as<int>(), (aa_qp_stats *)nullptr);
-    if (rc == AA_OK) {
-        hipError_t e = hipStreamSynchronize(c->stream);
-        if (e == hipSuccess) e = ctx_memcpy(c, Zout, dZ.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost);
-        if (e == hipSuccess && iters) e = ctx_memcpy(c, iters, dI.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost);
-        if (e != hipSuccess) {
-            set_error("qp batch: %s", hipGetErrorString(e));
-            rc = AA_ERR_HIP;
-        }
-    }
-    dB.release();
-    dZ.release();
-    dI.release();
-    return rc;
+    AA_CHECK(dB.alloc(extent * sizeof(double)));
+    AA_CHECK(dZ.alloc((size_t)n * k * sizeof(double)));
+    AA_CHECK(dI.alloc((size_t)n * sizeof(int)));
+    AA_CHECK_HIP(ctx_memcpy(c, dB.p, B, extent * sizeof(double), hipMemcpyHostToDevice));
+    AA_CHECK_HIP(ctx_memcpy(c, dZ.p, Z0, (size_t)n * k * sizeof(double), hipMemcpyHostToDevice));
+    AA_CHECK(launch_qp(c, A, dB.as<double>(), stride_j, stride_t, nullptr, dZ.as<double>(), k, n, k, params, dI.as<int>(),
+                       (aa_qp_stats *)nullptr));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy(c, Zout, dZ.p, (size_t)n * k * sizeof(double), hipMemcpyDeviceToHost));
+    if (iters) AA_CHECK_HIP(ctx_memcpy(c, iters, dI.p, (size_t)n * sizeof(int), hipMemcpyDeviceToHost));
+    return AA_OK;
 }
 
 int aa_get_spg_scalars(aa_ctx *h, double *out)
@@ -2617,6 +2472,7 @@ static int pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long
 {
     AA_REQUIRE(h && A && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
+    // the stored kernel form is served too (not has_stored_data); ensure_problem asks for the data
     AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_pass_reduce_rows: no stored matrix behind an implicit kernel");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
@@ -2660,6 +2516,7 @@ int aa_pass_row_local(aa_ctx *h, int k, const double *B, long ldb, double *out)
 {
     AA_REQUIRE(h && B && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
+    // as aa_pass_reduce_rows: either stored form
     AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_pass_row_local: no stored matrix behind an implicit kernel");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
@@ -2744,26 +2601,23 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE,
                    "aa_time_kernel 9: aa_set_rbf_reference or aa_set_poly_reference first");
     else if (which == 10 || which == 11)
-        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->have_state && c->gpnh_valid &&
-                       c->world == 1 && !c->force_comm,
-                   AA_ERR_STATE, "aa_time_kernel 10 / 11: aa_gpnh_set_factors (dictionary and weights) first, single rank");
-    else if (which == 12)
+        AA_REQUIRE(has_stored_data(c) && c->have_state && c->gpnh_valid && c->world == 1 && !c->force_comm, AA_ERR_STATE,
+                   "aa_time_kernel 10 / 11: aa_gpnh_set_factors (dictionary and weights) first, single rank");
+    else if (which == 12)                        // either stored form (not has_stored_data), like aa_pass_reduce_rows
         AA_REQUIRE(c->have_data && !c->implicit_kernel && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
     else if (which == 13 || which == 14)
-        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA && c->world == 1 && !c->force_comm,
-                   AA_ERR_STATE, "aa_time_kernel 13 / 14: a stored data matrix (data form), single rank");
-    else {
-        AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_time_kernel: no stored matrix behind an implicit kernel");
-        AA_REQUIRE(c->have_state && c->form == AA_FORM_DATA, AA_ERR_STATE, "needs data-form state");
-    }
+        AA_REQUIRE(has_stored_data(c) && c->world == 1 && !c->force_comm, AA_ERR_STATE,
+                   "aa_time_kernel 13 / 14: a stored data matrix (data form), single rank");
+    else
+        AA_REQUIRE(has_stored_data(c) && c->have_state, AA_ERR_STATE, "aa_time_kernel: needs data-form state on a stored matrix");
     AA_CHECK_HIP(hipSetDevice(c->device));
     hipEvent_t e0, e1;
     AA_CHECK_HIP(hipEventCreate(&e0));
     AA_CHECK_HIP(hipEventCreate(&e1));
     int rc = AA_OK;
     // 13 / 14: a scratch destination of the layout the entry point fills, and a seeded permutation of the rows
-    DevBuf scratch, perm;
+    ScopedDevBuf scratch, perm;
     const long scratch_ld = which == 14 ? round_up(c->p, 32) : c->p_pad;
     if (which == 13 || which == 14)
         rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * scratch_ld * (which == 14 ? sizeof(double) : esize(c)));
@@ -2826,8 +2680,6 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
     if (which == 13 || which == 14) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
-    scratch.release();
-    perm.release();
     return rc;
 }
 
