@@ -690,6 +690,37 @@ int aa_proj_counts(aa_ctx *ctx, long out[4]);
  * ran that mapping (tests/test_gpu_qp_kernels.py).  The restart-slot launches are not recorded.
  * Returns AA_ERR_ARG if `len` is too small. */
 int aa_qp_kernels(aa_ctx *ctx, int device, char *buf, int len);
+/* One device array of the context's latest dictionary update (csrc/solver.hip: dictionary_update), copied
+ * to `out` row-major over its valid extent: n x k for the tall arrays, k x k for M, k x p for Q, 16 for f_mem.  `which`:
+ *   AA_SPG_ARRAY_G       the current gradient: after an update, that of the point it returned (g_new)
+ *   AA_SPG_ARRAY_G_PREV  the gradient before it (g_old of the update's last iteration)
+ *   AA_SPG_ARRAY_D       the search direction d of the last iteration
+ *   AA_SPG_ARRAY_GR      the raw product behind AA_SPG_ARRAY_G: (C X X')' or (C K)' of the returned point
+ *   AA_SPG_ARRAY_GR_PREV the other product buffer: data form, the product behind AA_SPG_ARRAY_G_PREV;
+ *                        kernel form, K d (the returned product is the previous one + lambda times this)
+ *   AA_SPG_ARRAY_H       X X' Z or K Z, as the update read it
+ *   AA_SPG_ARRAY_M       M = D Z'Z D as the set-up formed it (k x k)
+ *   AA_SPG_ARRAY_Q       d' X of the last iteration (k x p; data form only)
+ *   AA_SPG_ARRAY_FMEM    the line search's history f_mem[0 .. 15] (spg.py:153,198-199; entry 0 is f at the
+ *                        start of the last iteration, entries beyond `memory` stay 0)
+ * Waits for the context's stream and side stream, launches nothing and steers nothing.  The element-wise
+ * suite of the SPG step compares every kernel's output with the arrays it read
+ * (tests/test_gpu_spg_step.py).  The reference has no counterpart (its arrays are NumPy locals of spg()). */
+enum { AA_SPG_ARRAY_G = 0, AA_SPG_ARRAY_G_PREV, AA_SPG_ARRAY_D, AA_SPG_ARRAY_GR, AA_SPG_ARRAY_GR_PREV,
+       AA_SPG_ARRAY_H, AA_SPG_ARRAY_M, AA_SPG_ARRAY_Q, AA_SPG_ARRAY_FMEM };
+int aa_get_spg_array(aa_ctx *ctx, int which, double *out);
+/* What the context's latest dictionary update ran, in launch order and separated by ';': the set-up
+ * ("cold": factors projected and products recomputed; "warm": products kept, one kernel per step;
+ * "fast:k_dict_setup" / "fast:in_grad": one block, on its own or as block 0 of the first gradient launch),
+ * then every gradient launch ("k_grad<KP>:nb=blocks:rpb=rows per block") and every line search with its
+ * template argument and grid: "k_gram_wide_pq_mfma<32>:nb=17:cpb=128;k_linesearch_fin" (fused; also
+ * "k_gram_wide_pq<KP>"), "k_gram_wide<32>x2;k_scalar_stage" (data form, fuse_finalize = 0),
+ * "k_gram_tall<64>x3;k_scalar_stage" (kernel form).  The string holds 511 characters: from the first entry
+ * that does not fit on, entries are dropped.  A host-side string: reading it launches nothing and it steers
+ * nothing.  A test of one path has to know that it ran that path (tests/test_gpu_spg_step.py).  The
+ * restart-slot launches are not recorded.  The reference has no counterpart (one code path).  Empty before
+ * the first update.  Returns AA_ERR_ARG if `len` is too small. */
+int aa_spg_path(aa_ctx *ctx, char *buf, int len);
 
 #ifdef __cplusplus
 }

@@ -187,6 +187,8 @@ _SIGNATURES = {
     "aa_pass_kernels": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
     "aa_proj_counts": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long)]),
     "aa_qp_kernels": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_char_p, ctypes.c_int]),
+    "aa_get_spg_array": (ctypes.c_int, [_vp, ctypes.c_int, _dp]),
+    "aa_spg_path": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_int]),
 }
 
 EXPORTED_SYMBOLS = tuple(sorted(_SIGNATURES))
@@ -1027,6 +1029,24 @@ class Context(object):
         out = (ctypes.c_long * 4)()
         _check(self.lib.aa_proj_counts(self.h, out))
         return dict(zip(("small32", "small64", "list", "iterative"), (int(v) for v in out)))
+
+    SPG_ARRAYS = ("g", "g_prev", "d", "Gr", "Gr_prev", "H", "M", "Q", "f_mem")
+
+    def spg_array(self, name):
+        """One device array of the latest dictionary update (aa_get_spg_array): ``g``, ``g_prev``, ``d``,
+        ``Gr``, ``Gr_prev``, ``H`` (n x k), ``M`` (k x k), ``Q`` (k x p, data form) or ``f_mem`` (16)."""
+        shape = {"M": (self.k, self.k), "Q": (self.k, self.p), "f_mem": (16,)}.get(name, (self.n, self.k))
+        out = np.empty(shape)
+        _check(self.lib.aa_get_spg_array(self.h, self.SPG_ARRAYS.index(name), _ptr(out)))
+        return out
+
+    def spg_path(self):
+        """Set-up and kernels of the latest dictionary update, in launch order (aa_spg_path), e.g.
+        ``["cold", "k_grad<32>:nb=1:rpb=64", "k_gram_wide_pq_mfma<32>:nb=1:cpb=128", "k_linesearch_fin",
+        "k_grad<32>:nb=1:rpb=64"]``."""
+        buf = ctypes.create_string_buffer(512)
+        _check(self.lib.aa_spg_path(self.h, buf, 512))
+        return buf.value.decode().split(";")
 
     def time_kernel(self, which, reps):
         ms = ctypes.c_double(0)

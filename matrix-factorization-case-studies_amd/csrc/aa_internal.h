@@ -234,6 +234,8 @@ struct Ctx {
     int qp_live_epoch = 0;
     char pass_names[2][48] = {{0}, {0}};       // last reduce-over-rows / row-local kernel launched (aa_pass_kernels)
     char qp_names[192] = {0};                  // what the last launch_qp launched, ';'-separated (aa_qp_kernels)
+    char spg_path[512] = {0};                  // set-up and kernels of the latest dictionary update, ';'-separated (aa_spg_path)
+    bool spg_path_full = false;                // an entry did not fit: the later ones are dropped too
     bool qp_tail_pending = false;              // stragglers run on stream2, results in tmpTall by slot
     // the residual projection of the dictionary SPG (spg.py:250-276: convergence flags only) runs on
     // the side stream beside the weights QP, on its own scratch set (launch_proj_side / join_side)
@@ -349,6 +351,12 @@ struct Ctx {
     bool products_valid = false;               // P (= CX) and Gr (= C XX' or C K) match Ct
     bool ckz_valid = false;                    // gramState's C K Z matches Ct and H
 };
+
+// What the latest dictionary update ran (aa_spg_path): a host-side string that dictionary_update, launch_grad and
+// launch_linesearch_fused write beside their launches and nothing that launches reads.  From the first entry that
+// does not fit on, entries are dropped whole (a long SPG run repeats its entries anyway).
+void spg_name(Ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
+#define SPG_NAME(...) spg_name(c, __VA_ARGS__)
 
 // a stored matrix in data form: X holds the n x p rows themselves -- not a kernel matrix, and not nothing
 // behind an implicit kernel.  (An implicit kernel always comes with form == AA_FORM_KERNEL: install_begin.)

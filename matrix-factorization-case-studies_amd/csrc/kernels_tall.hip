@@ -1466,6 +1466,8 @@ __device__ double dev_line_search_step(double lam, double delta, double f_old, d
 // barriers
 __device__ double block_trace_MG_n(const double *__restrict__ M, const double *__restrict__ G, int k,
                                    int KP, bool transposed, double *sm);
+__device__ __forceinline__ void linesearch_traces(const double *__restrict__ M, const double *G1, const double *G2,
+                                                  int k, int KP, double *smt, double *smt2);
 
 // tr(M * G) (or tr(M * G') when transposed), all 256 threads, fixed-order tree.
 __device__ double block_trace_MG(const double *__restrict__ M, const double *__restrict__ G, int k,
@@ -1565,10 +1567,16 @@ __global__ __launch_bounds__(256) void k_scalar_stage(int stage, double *__restr
     double tr0 = 0.0, tr1 = 0.0, tr2 = 0.0;
     if (stage == ST_INIT_F) {
         tr0 = block_trace_MG(M, gram, k, KP, false, sm);
+    } else if (stage == ST_LINESEARCH && cross2_is_transpose) {
+        // data form: the traces of k_linesearch_fin, by the same function -- with the LDS / VALU Grams
+        // (pq_mfma = 0) the one-kernel-per-step sequence then returns the bits of the fused one
+        __shared__ double sm2[256];
+        linesearch_traces(M, gram + GS, gram + 2 * GS, k, KP, sm, sm2);
+        tr1 = sm[0];
+        tr2 = sm2[0];
     } else if (stage == ST_LINESEARCH) {
         tr1 = block_trace_MG(M, gram + GS, k, KP, false, sm);
-        if (cross2_is_transpose) tr1 += block_trace_MG(M, gram + GS, k, KP, true, sm);
-        else tr1 += block_trace_MG(M, gram + 3 * GS, k, KP, false, sm);
+        tr1 += block_trace_MG(M, gram + 3 * GS, k, KP, false, sm);
         tr2 = block_trace_MG(M, gram + 2 * GS, k, KP, false, sm);
     }
     if (threadIdx.x != 0) return;
@@ -2593,6 +2601,23 @@ int launch_proj_side(Ctx *c, const double *x, const double *g, double a_const, i
     return rc;
 }
 
+void spg_name(Ctx *c, const char *fmt, ...)
+{
+    if (c->slots_aa) return;                     // the restart slots' launches are not recorded
+    char item[96];
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(item, sizeof(item), fmt, ap);
+    va_end(ap);
+    const size_t at = strlen(c->spg_path);
+    if (c->spg_path_full || at + strlen(item) + 2 > sizeof(c->spg_path)) {
+        c->spg_path_full = true;                 // the string stays a prefix of what ran
+        return;
+    }
+    if (at) strcat(c->spg_path, ";");
+    strcat(c->spg_path, item);
+}
+
 // xupd (nullable, needs d_for_dot): x += lambda d in the same pass.  stage_after >= 0 (with
 // sp): the scalar stage that consumes <d, g> (ST_BB) runs inside the finalize kernel.
 int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, double scale,
@@ -2622,16 +2647,19 @@ int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, doubl
     double *pdot = d_for_dot ? part : (double *)nullptr;
     const int kslot = c->slots_aa ? c->slots_k : 0;
     if (kslot && d_for_dot) pdot = c->tmpTall.as<double>();      // k_grad's mixed dot is not used: per slot below
-    if (c->KP == 32)
+    if (c->KP == 32) {
+        SPG_NAME("k_grad<32>:nb=%d:rpb=%ld", nb, rpb);
         hipLaunchKernelGGL(k_grad<32>, dim3(nb + ds.on), dim3(256), 0, c->stream, Graw, H,
                            (const double *)c->Mdev.as<double>(), (const double *)c->alphaDev.as<double>(),
                            scale, c->n, rpb, c->k, gout, d_for_dot, pdot, xupd,
                            (const double *)c->scalars.as<double>(), kslot, c->slots_R, ds);
-    else
+    } else {
+        SPG_NAME("k_grad<64>:nb=%d:rpb=%ld", nb, rpb);
         hipLaunchKernelGGL(k_grad<64>, dim3(nb + ds.on), dim3(256), 0, c->stream, Graw, H,
                            (const double *)c->Mdev.as<double>(), (const double *)c->alphaDev.as<double>(),
                            scale, c->n, rpb, c->k, gout, d_for_dot, pdot, xupd,
                            (const double *)c->scalars.as<double>(), kslot, c->slots_R, ds);
+    }
     if (kslot && d_for_dot) {
         const dim3 gd((unsigned)nb, (unsigned)c->slots_R);
         if (c->KP == 32)
@@ -3901,30 +3929,38 @@ int launch_linesearch_fused(Ctx *c, const aa_spg_params *sp, double *cost_out, i
     const int nb = (int)((c->p_pad + cpb - 1) / cpb);
     double *part = c->redPartial.as<double>();
     double *ckct = c->gramState.as<double>() + (size_t)c->KP * c->KP;
-    if (g_pq_mfma && c->KP == 32)
+    // (every branch records the kernel it launches: aa_spg_path)
+    if (g_pq_mfma && c->KP == 32) {
+        SPG_NAME("k_gram_wide_pq_mfma<32>:nb=%d:cpb=%d", nb, cpb);
         hipLaunchKernelGGL(k_gram_wide_pq_mfma<32>, dim3(nb), dim3(256), 0, c->stream,
                            (const double *)c->P.as<double>(), (const double *)c->Q.as<double>(),
                            (int)c->p_pad, part, cpb);
-    else if (g_pq_mfma)
+    } else if (g_pq_mfma) {
+        SPG_NAME("k_gram_wide_pq_mfma<64>:nb=%d:cpb=%d", nb, cpb);
         hipLaunchKernelGGL(k_gram_wide_pq_mfma<64>, dim3(nb), dim3(256), 0, c->stream,
                            (const double *)c->P.as<double>(), (const double *)c->Q.as<double>(),
                            (int)c->p_pad, part, cpb);
-    else if (c->KP == 32)
+    } else if (c->KP == 32) {
+        SPG_NAME("k_gram_wide_pq<32>:nb=%d:cpb=%d", nb, cpb);
         hipLaunchKernelGGL(k_gram_wide_pq<32>, dim3(nb), dim3(256), 0, c->stream,
                            (const double *)c->P.as<double>(), (const double *)c->Q.as<double>(),
                            (int)c->p_pad, part, cpb, c->k);
-    else
+    } else {
+        SPG_NAME("k_gram_wide_pq<64>:nb=%d:cpb=%d", nb, cpb);
         hipLaunchKernelGGL(k_gram_wide_pq<64>, dim3(nb), dim3(256), 0, c->stream,
                            (const double *)c->P.as<double>(), (const double *)c->Q.as<double>(),
                            (int)c->p_pad, part, cpb, c->k);
+    }
     if (c->slots_aa) {
         hipLaunchKernelGGL(k_linesearch_fin_slots, dim3(1), dim3(1024), 0, c->stream, (const double *)part, nb, c->KP,
                            c->gramOut.as<double>(), (const double *)c->Mdev.as<double>(), c->scalars.as<double>(),
                            *sp, c->slots_k, c->slots_R, ckct, (double)c->n_global, slots_of(c));
-    } else
-    hipLaunchKernelGGL(k_linesearch_fin, dim3(1), dim3(1024), 0, c->stream, (const double *)part, nb, c->KP,
-                       c->gramOut.as<double>(), (const double *)c->Mdev.as<double>(),
-                       c->scalars.as<double>(), *sp, c->k, ckct, (double)c->n_global, cost_out, cost_slot);
+    } else {
+        SPG_NAME("k_linesearch_fin");
+        hipLaunchKernelGGL(k_linesearch_fin, dim3(1), dim3(1024), 0, c->stream, (const double *)part, nb, c->KP,
+                           c->gramOut.as<double>(), (const double *)c->Mdev.as<double>(),
+                           c->scalars.as<double>(), *sp, c->k, ckct, (double)c->n_global, cost_out, cost_slot);
+    }
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }

@@ -373,6 +373,12 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
     const bool fast = fused && warm && c->grams_valid && c->ckz_valid && !c->dict_inputs_overridden;
     // (single fit: the set-up block rides in the gradient launch below, beside its row blocks)
     const bool setup_in_grad = fast && g_setup_in_grad && !c->slots_aa;
+    c->spg_path[0] = 0;
+    c->spg_path_full = false;
+    if (setup_in_grad) SPG_NAME("fast:in_grad");
+    else if (fast) SPG_NAME("fast:k_dict_setup");
+    else if (warm) SPG_NAME("warm");
+    else SPG_NAME("cold");
     if (fast) {
         if (!setup_in_grad) AA_CHECK(launch_dict_setup(c, sp, (double)k));      // spg.py:153-157
     } else {
@@ -435,6 +441,7 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
                 AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->Q.as<double>(), gram + GS));
                 AA_CHECK(launch_gram_wide(c, c->Q.as<double>(), c->Q.as<double>(), gram + 2 * GS));
                 AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 1));
+                SPG_NAME("k_gram_wide<%d>x2;k_scalar_stage", KP);
             }
         } else {
             if (c->implicit_kernel) {
@@ -448,6 +455,7 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
             AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), c->Dt.as<double>(), gram + 2 * GS));
             AA_CHECK(launch_gram_tall(c, c->Gr.as<double>(), c->Dt.as<double>(), gram + 3 * GS));
             AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 0));
+            SPG_NAME("k_gram_tall<%d>x3;k_scalar_stage", KP);
         }
         if (data) {
             // x = x_old + lam d happens inside the gradient kernel (it reads d for <d, g_new>),
@@ -2451,6 +2459,43 @@ int aa_get_spg_scalars(aa_ctx *h, double *out)
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     AA_CHECK_HIP(ctx_memcpy(c, out, c->scalars.p, AA_SPG_SCALARS * sizeof(double), hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+int aa_get_spg_array(aa_ctx *h, int which, double *out)
+{
+    AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_state && c->scalars.p, AA_ERR_STATE, "no solver state");
+    const DevBuf *tall[] = {&c->gk, &c->gn, &c->Dt, &c->Gr, &c->Gn, &c->H};
+    AA_REQUIRE(which >= 0 && which <= AA_SPG_ARRAY_FMEM, AA_ERR_ARG, "aa_get_spg_array: which = %d out of range", which);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    if (which == AA_SPG_ARRAY_FMEM) {
+        AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+        AA_CHECK_HIP(ctx_memcpy(c, out, c->scalars.as<double>() + SC_FMEM0, 16 * sizeof(double), hipMemcpyDeviceToHost));
+        return AA_OK;
+    }
+    if (which <= AA_SPG_ARRAY_H) {                 // tall [n_pad][KP] -> n x k (download_tall joins the side stream)
+        AA_REQUIRE(tall[which]->p, AA_ERR_STATE, "aa_get_spg_array: array %d not allocated", which);
+        return download_tall(c, *tall[which], out, c->k, 1, c->n, c->k);
+    }
+    const bool wide = which == AA_SPG_ARRAY_Q;
+    const DevBuf &src = wide ? c->Q : c->Mdev;
+    const size_t ld = wide ? (size_t)c->p_pad : (size_t)c->KP, cols = wide ? (size_t)c->p : (size_t)c->k;
+    AA_REQUIRE(src.p && (!wide || c->form == AA_FORM_DATA), AA_ERR_STATE,
+               "aa_get_spg_array: array %d does not exist in this form", which);
+    AA_CHECK_HIP(ctx_memcpy2d(c, out, cols * sizeof(double), src.p, ld * sizeof(double), cols * sizeof(double),
+                             (size_t)c->k, hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+int aa_spg_path(aa_ctx *h, char *buf, int len)
+{
+    AA_REQUIRE(h && buf && len > 0, AA_ERR_ARG, "null argument");
+    const char *path = h->c.spg_path;
+    AA_REQUIRE((size_t)len > strlen(path), AA_ERR_ARG, "aa_spg_path: buffer of %d bytes, %zu needed", len,
+               strlen(path) + 1);
+    strcpy(buf, path);
     return AA_OK;
 }
 
