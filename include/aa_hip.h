@@ -228,8 +228,8 @@ int aa_ctx_p2p_init(aa_ctx *ctx, const void *handles, int rank, int world);
  * bench.py for the barrier + max-over-ranks timing); op: 0 = sum, 1 = max. */
 int aa_ctx_allreduce_host(aa_ctx *ctx, double *buf, int count, int op);
 
-/* Installing data.  Ten entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
- * aa_set_data_rows_affine, aa_set_data_take, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
+/* Installing data.  Eleven entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
+ * aa_set_data_rows_affine, aa_set_data_rows_model, aa_set_data_take, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
  * the _resident forms of the last two.  Every one of them ("an install") first checks its arguments -- a call it
  * refuses has not touched ctx, which keeps the data it had -- and then replaces everything that belonged to the
  * previous matrix: the form and the kind of implicit kernel (none for a stored matrix), aa_set_linear_kernel, the
@@ -323,6 +323,36 @@ int aa_set_data_rows(aa_ctx *ctx, const aa_ctx *owner, long row0, long n);
 int aa_data_column_moments(aa_ctx *ctx, double *mean, double *var);
 int aa_set_data_rows_affine(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, const double *shift,
                             const double *scale);
+
+/* Seasonal anomalies and per-group standardisation of resident data (the reference notebook
+ * hadisst_sst_anom.ipynb: calculate_monthly_anomalies and the per-month (x - mean_month) / std_month behind it).
+ * Every quantity of the anomaly model -- the values of the seasonal cycle, the trend's slope and intercept -- is
+ * a fixed linear functional of a column, so the model is ONE pass over the matrix with a small coefficient
+ * matrix built on the host, and the anomalies one read-and-write pass.
+ *
+ * aa_data_weighted_column_sums: out[g][j] = sum_t A[g][t] X[t][j] for g < G <= 16, j < p.  A: G x n host doubles
+ *   (row-major, n the resident rows), out: G x p host doubles.  float64 arithmetic in both context dtypes
+ *   (elements widened on load), the contraction over rows on v_mfma_f64_16x16x4_f64 (csrc/kernels_tall.hip:
+ *   k_col_weighted_sums), row-slab partials added in a fixed order, no atomics: two calls return the same bits.
+ *   Data form with a stored matrix (AA_ERR_STATE otherwise), single rank.
+ * aa_data_grouped_sqdev: out[g][j] = sum_t A[g][t] (X[t][j] - centre[group[t]][j])^2, the second sweep of
+ *   per-group variances.  group: n host ints in [-1, Gc), -1: the row is not counted (it contributes 0 whatever
+ *   A holds); centre: Gc x p host doubles, Gc <= 16.  Otherwise as above.
+ * aa_set_data_rows_model: aa_set_data_rows with
+ *     Y[r][j] = ((X[row0 + r][j] - shift[group[r]][j]) - (icpt[j] + slope[j] t[r])) / scale[group[r]][j],
+ *   exactly the float64 roundings of that expression as written (a subtraction, a product, a sum, a subtraction,
+ *   a true division; nothing fused), rounded once to the context's element type.  shift / scale: G x p host
+ *   doubles or NULL (part left out), G <= 16; group: n host ints in [0, G), one per row of the block (NULL with
+ *   G == 1: row 0 for every row); icpt / slope: p host doubles, t: n host doubles, all three or none.  G > 16, a
+ *   label outside [0, G), a zero or non-finite scale and a non-finite shift, slope, intercept or t are refused
+ *   with AA_ERR_ARG like any other bad argument of an install.  Otherwise the preconditions and refusals of
+ *   aa_set_data_rows. */
+int aa_data_weighted_column_sums(aa_ctx *ctx, int G, const double *A, double *out);
+int aa_data_grouped_sqdev(aa_ctx *ctx, int G, const double *A, const int *group, const double *centre, int Gc,
+                          double *out);
+int aa_set_data_rows_model(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, int G, const int *group,
+                           const double *shift, const double *icpt, const double *slope, const double *t,
+                           const double *scale);
 
 /* Row gather on the device (seasonal subsets, k-fold splits, bootstrap resamples of a resident block, and the
  * support rows KernelAA.transform keeps, `X[support]`): rows idx[0..n) of owner's resident DATA matrix, in any
@@ -653,7 +683,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * dense kernel on the same operand),
  * 13 = the row gather of aa_set_data_take on the context's own matrix (a seeded permutation of all its rows, into a
  * scratch copy), 14 = the feature build of aa_set_poly_features_resident from it (into a scratch buffer); both
- * need only a stored data matrix.
+ * need only a stored data matrix.  15 = the weighted column sums of aa_data_weighted_column_sums with 16 coefficient
+ * rows, 16 = the squared-deviation form of aa_data_grouped_sqdev (rows labelled r mod 12), both with their finish
+ * kernel and without the copies; 17 = the model copy of aa_set_data_rows_model in its anomalies form (a 12-row shift
+ * table and the trend) from the context's own matrix into a scratch copy; a stored data matrix is all they need.
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

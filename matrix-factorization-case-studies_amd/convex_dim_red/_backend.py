@@ -124,6 +124,10 @@ _SIGNATURES = {
     "aa_set_data_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long]),
     "aa_set_data_rows_affine": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, _dp, _dp]),
     "aa_data_column_moments": (ctypes.c_int, [_vp, _dp, _dp]),
+    "aa_data_weighted_column_sums": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp]),
+    "aa_data_grouped_sqdev": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _ip, _dp, ctypes.c_int, _dp]),
+    "aa_set_data_rows_model": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _ip, _dp, _dp, _dp,
+                                              _dp, _dp]),
     "aa_set_data_weighted": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                             _dp, ctypes.c_long, ctypes.c_long,
                                             ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_long)]),
@@ -533,6 +537,36 @@ class Context(object):
                                                 None if scale is None else _ptr(scale)))
         self._adopt(n, owner.p)
 
+    def set_data_rows_model(self, owner, row0, n, groups=None, shift=None, intercept=None, slope=None, t=None,
+                            scale=None):
+        """``((owner[row0:row0 + n] - shift[groups]) - (intercept + slope * t[:, None])) / scale[groups]`` becomes
+        this context's data matrix (aa_set_data_rows_model): the float64 roundings of that NumPy expression, one
+        rounding to the context's dtype.  ``shift`` / ``scale``: None (part left out) or ``(G, p)`` tables, row
+        ``groups[r]`` for row ``r`` of the block (``groups``: n integers in ``[0, G)``; None with ``G == 1``);
+        ``intercept`` / ``slope``: one value per column, ``t``: one per row, all three or none."""
+        n = int(n)
+        tables = [None if a is None else np.atleast_2d(_c64(a)) for a in (shift, scale)]
+        G = max([1] + [a.shape[0] for a in tables if a is not None])
+        for a, name in zip(tables, ("shift", "scale")):
+            if a is not None and a.shape != (G, owner.p):
+                raise ValueError("%s: a (%d, %d) table expected, one row per group; got shape %r"
+                                 % (name, G, owner.p, a.shape))
+        trend = [None if a is None else _c64(a) for a in (intercept, slope, t)]
+        if any(a is None for a in trend) != all(a is None for a in trend):
+            raise ValueError("intercept, slope and t come together or not at all")
+        for a, name, size in zip(trend, ("intercept", "slope", "t"), (owner.p, owner.p, n)):
+            if a is not None and a.shape != (size,):
+                raise ValueError("%s: %d values expected; got shape %r" % (name, size, a.shape))
+        if groups is not None:
+            groups = np.ascontiguousarray(groups, dtype=np.intc)
+            if groups.shape != (n,):
+                raise ValueError("groups: %d labels expected, one per row; got shape %r" % (n, groups.shape))
+        ptr = [None if a is None else _ptr(a) for a in tables + trend]
+        _check(self.lib.aa_set_data_rows_model(self.h, owner.h, int(row0), n, G,
+                                               None if groups is None else groups.ctypes.data_as(_ip),
+                                               ptr[0], ptr[2], ptr[3], ptr[4], ptr[1]))
+        self._adopt(n, owner.p)
+
     def set_data_take(self, owner, indices=None):
         """Rows ``indices`` (any order, duplicates allowed; None: all rows in order) of ``owner``'s resident data
         matrix become this context's data matrix (aa_set_data_take): a device gather that owns its memory.  A
@@ -574,6 +608,31 @@ class Context(object):
         v = np.empty(self.p) if var else None
         _check(self.lib.aa_data_column_moments(self.h, None if m is None else _ptr(m), None if v is None else _ptr(v)))
         return m, v
+
+    def data_weighted_column_sums(self, A, groups=None, centre=None):
+        """``A @ X`` for the resident data matrix ``X`` and a ``(G, n)`` coefficient matrix, ``G <= 16``
+        (aa_data_weighted_column_sums), or with ``groups`` (n integers, -1: row not counted) and a ``(Gc, p)``
+        table ``centre``: ``out[g] = sum_t A[g, t] * (X[t] - centre[groups[t]]) ** 2`` (aa_data_grouped_sqdev).
+        float64 arithmetic and a fixed summation order in both context dtypes.  Returns ``(G, p)`` float64."""
+        A = _c64(A)
+        if A.ndim != 2 or A.shape[1] != self.n:
+            raise ValueError("a (G, %d) coefficient matrix expected, one column per resident row; got shape %r"
+                             % (self.n, A.shape))
+        out = np.empty((A.shape[0], self.p))
+        if centre is None and groups is None:
+            _check(self.lib.aa_data_weighted_column_sums(self.h, A.shape[0], _ptr(A), _ptr(out)))
+            return out
+        if centre is None or groups is None:
+            raise ValueError("groups and centre come together")
+        centre = _c64(centre)
+        groups = np.ascontiguousarray(groups, dtype=np.intc)
+        if centre.ndim != 2 or centre.shape[1] != self.p:
+            raise ValueError("centre: a (Gc, %d) table expected; got shape %r" % (self.p, centre.shape))
+        if groups.shape != (self.n,):
+            raise ValueError("groups: %d labels expected, one per row; got shape %r" % (self.n, groups.shape))
+        _check(self.lib.aa_data_grouped_sqdev(self.h, A.shape[0], _ptr(A), groups.ctypes.data_as(_ip), _ptr(centre),
+                                              centre.shape[0], _ptr(out)))
+        return out
 
     def set_rbf_features(self, X, gamma):
         """The implicit RBF kernel exp(-gamma ||x_i - x_j||^2) of the rows of X as this context's kernel

@@ -22,6 +22,150 @@ ColumnStats = namedtuple("ColumnStats", ("mean", "std", "n_samples"))
 # What ``DeviceData.standardized`` applied: the ``ColumnStats`` it divided by (and subtracted, if ``center``).
 ColumnScaling = namedtuple("ColumnScaling", ("stats", "center"))
 
+# The anomaly model a block made by ``DeviceData.seasonal_anomalies`` was built with, as float64 host arrays:
+# ``seasonal_cycle`` (period, n_features), ``slope`` / ``intercept`` (n_features,; None with trend_order 0).
+SeasonalAnomalies = namedtuple("SeasonalAnomalies", ("period", "base_rows", "seasonal_cycle", "slope", "intercept"))
+# Per-group column statistics: ``mean`` / ``std`` (n_groups, n_features) (``std`` with ddof 0, as xarray's
+# ``.std``) and ``counts``, the rows each group's statistics were taken over.
+GroupedColumnStats = namedtuple("GroupedColumnStats", ("mean", "std", "counts"))
+# What ``DeviceData.standardized_by_group`` applied: the statistics, whether it centred, and the row labels.
+GroupScaling = namedtuple("GroupScaling", ("stats", "center", "groups"))
+
+MAX_GROUPS = 16          # coefficient rows / groups one device pass takes (AA_MAX_COEF_ROWS)
+MAX_PERIOD = MAX_GROUPS - 2
+
+
+def _is_int(v):
+    return isinstance(v, (int, np.integer)) and not isinstance(v, (bool, np.bool_))
+
+
+def _checked_row_range(rows, n, who):
+    """(lo, hi) of ``rows`` (None: all n rows), or ValueError."""
+    if rows is None:
+        return 0, n
+    try:
+        lo, hi = rows
+    except (TypeError, ValueError):
+        raise ValueError("%s: (lo, hi) expected; got %r" % (who, rows))
+    if not (_is_int(lo) and _is_int(hi)):
+        raise ValueError("%s: integer bounds expected; got %r, %r" % (who, lo, hi))
+    lo, hi = int(lo), int(hi)
+    if lo < 0 or hi > n or hi <= lo:
+        raise ValueError("%s: [%d, %d) is empty or outside the %d rows held" % (who, lo, hi, n))
+    return lo, hi
+
+
+def seasonal_coefficients(n, period, base_rows=None, trend_order=1):
+    """Host only: the monthly-anomaly model of the reference notebook ``hadisst_sst_anom.ipynb``
+    (``calculate_monthly_anomalies``) as a coefficient matrix.  Every quantity of that model is a fixed linear
+    functional of a column ``x`` of ``n`` rows, so ``A @ X`` gives, for every column at once,
+
+    * rows ``0 .. period - 1``: the seasonal cycle -- the centred moving average ``m`` (window ``[1/2, 1, ..., 1,
+      1/2] / period`` for an even period, ``ones(period) / period`` for an odd one), the means of ``x - m`` over
+      the rows ``t = g (mod period)`` inside ``base_rows = (lo, hi)`` (None: all rows) that have a full window
+      (``h <= t < n - h``, ``h`` half the window width), minus the mean of these ``period`` phase means;
+    * row ``period``: the slope, and row ``period + 1``: the intercept, of the least-squares line through
+      ``x[t] - cycle[t mod period]`` over ALL rows against ``t = 0 .. n - 1`` (``trend_order=1``;
+      ``trend_order=0`` leaves both rows out; higher orders, which the notebook fits with ``curve_fit``, are
+      refused).
+
+    Returns ``(A, A_parts)``, both ``(period + 2 * trend_order, n)`` float64.  ``A_parts >= |A|`` adds the
+    absolute values of the parts of ``A`` BEFORE they cancel -- indicator / count, indicator * |window| / count,
+    the mean over the phases, and for the trend rows ``|s|' (I + |cycle rows|)`` with ``s`` the regression's own
+    weights (intercept: ``1/n + mean(t) |s|``) -- so ``n u (A_parts @ |X|)`` bounds the rounding error of
+    ``A @ X`` AND of the notebook's step-by-step evaluation.  ``period``: 1 .. 14.  A phase without a usable base
+    row, where the notebook would produce NaN, is a ``ValueError``."""
+    if not _is_int(n) or n < 1:
+        raise ValueError("seasonal_coefficients: n must be a positive integer; got %r" % (n,))
+    if not _is_int(period) or not 1 <= period <= MAX_PERIOD:
+        raise ValueError("seasonal_coefficients: period must be an integer from 1 to %d; got %r" % (MAX_PERIOD, period))
+    if trend_order not in (0, 1) or not _is_int(trend_order):
+        raise ValueError("seasonal_coefficients: trend_order must be 0 (no trend) or 1 (linear); got %r"
+                         % (trend_order,))
+    n, P = int(n), int(period)
+    if P % 2 == 0:
+        window = np.ones(P + 1)
+        window[0] = window[-1] = 0.5
+        window = window / P
+    else:
+        window = np.ones(P) / P
+    h = (window.size - 1) // 2
+    if n < 2 * h + 1:
+        raise ValueError("seasonal_coefficients: %d rows are fewer than one moving-average window (%d)"
+                         % (n, 2 * h + 1))
+    if trend_order == 1 and n < 2:
+        raise ValueError("seasonal_coefficients: a linear trend needs at least 2 rows")
+    lo, hi = _checked_row_range(base_rows, n, "seasonal_coefficients: base_rows")
+    first, stop = max(lo, h), min(hi, n - h)
+    M, M_parts = np.zeros((P, n)), np.zeros((P, n))
+    for g in range(P):
+        rows = np.arange(first + (g - first) % P, stop, P)
+        if rows.size == 0:
+            raise ValueError("seasonal_coefficients: phase %d has no row with a full window inside the base rows "
+                             "[%d, %d); the notebook's cycle would be NaN there" % (g, lo, hi))
+        picked = np.zeros(n)
+        picked[rows] = 1.0
+        # the windows of the picked rows laid over each other (the window is symmetric and of odd length)
+        spread = np.convolve(picked, window, mode="same")
+        M[g] = (picked - spread) / rows.size
+        M_parts[g] = (picked + spread) / rows.size
+    cycle = M - M.mean(axis=0)
+    cycle_parts = M_parts + M_parts.mean(axis=0)
+    if trend_order == 0:
+        return cycle, cycle_parts
+    t = np.arange(n, dtype=np.float64)
+    t_mean = 0.5 * (n - 1)
+    s = (t - t_mean) / np.dot(t - t_mean, t - t_mean)           # slope = s' y
+    phase = np.arange(n) % P
+
+    def through_cycle(w, w_abs):
+        # w' y with y = x - cycle[t mod P]: w' (I - E cycle), E the n x P indicator of the phases
+        return (w - np.bincount(phase, weights=w, minlength=P).dot(cycle),
+                w_abs + np.bincount(phase, weights=w_abs, minlength=P).dot(cycle_parts))
+    slope, slope_parts = through_cycle(s, np.abs(s))
+    icpt, icpt_parts = through_cycle(1.0 / n - t_mean * s, 1.0 / n + t_mean * np.abs(s))   # mean(y) - slope mean(t)
+    return np.vstack([cycle, slope, icpt]), np.vstack([cycle_parts, slope_parts, icpt_parts])
+
+
+def _checked_groups(groups, n, who):
+    """(labels as intc, number of groups) of one label per row, or ValueError."""
+    raw = np.asarray(groups)
+    if raw.ndim != 1 or raw.shape[0] != n:
+        raise ValueError("%s: one group label per row (%d) expected; got shape %r" % (who, n, raw.shape))
+    if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer):
+        raise ValueError("%s: integer group labels expected; got dtype %s" % (who, raw.dtype))
+    if raw.min() < 0:
+        raise ValueError("%s: group labels start at 0; got %d" % (who, raw.min()))
+    if raw.max() >= MAX_GROUPS:
+        raise ValueError("%s: more than %d groups (label %d)" % (who, MAX_GROUPS, raw.max()))
+    return raw.astype(np.intc), int(raw.max()) + 1
+
+
+def _checked_group_stats(stats, n_groups, n_features, center):
+    """(shift or None, scale) tables of a per-group standardisation, or ValueError: from ``stats`` alone."""
+    who = "DeviceData.standardized_by_group"
+    std = None if stats.std is None else np.asarray(stats.std, dtype=np.float64)
+    if std is None or std.ndim != 2 or std.shape[1] != n_features:
+        raise ValueError("%s: stats.std must be (n_groups, %d); got %s"
+                         % (who, n_features, "None" if std is None else "shape %r" % (std.shape,)))
+    if std.shape[0] < n_groups or std.shape[0] > MAX_GROUPS:
+        raise ValueError("%s: the labels name %d groups, stats.std holds %d (at most %d)"
+                         % (who, n_groups, std.shape[0], MAX_GROUPS))
+    bad = np.argwhere(~np.isfinite(std) | (std == 0))
+    if bad.size:
+        raise ValueError("%s: %d entries of stats.std are zero or non-finite (the first is group %d, column %d); the "
+                         "notebook's division would fill them with inf / NaN" % (who, bad.shape[0], bad[0][0], bad[0][1]))
+    if not center:
+        return None, std
+    if stats.mean is None:
+        raise ValueError("%s: center=True needs stats with a mean" % who)
+    mean = np.asarray(stats.mean, dtype=np.float64)
+    if mean.shape != std.shape:
+        raise ValueError("%s: stats.mean must have the shape of stats.std %r; got %r" % (who, std.shape, mean.shape))
+    if not np.all(np.isfinite(mean)):
+        raise ValueError("%s: stats.mean has non-finite entries" % who)
+    return mean, std
+
 
 def _checked_stats(stats, n_features, center):
     """(shift or None, scale) of a standardisation, or ValueError: decided on the host, from ``stats`` alone."""
@@ -53,17 +197,21 @@ class DeviceData(object):
     ``valid``  -- boolean mask over the flattened features (True: kept), what the drivers use to
                   put archetypes back on the grid;
     ``to_host()`` -- the matrix as float64 NumPy (downloaded once, then cached);
-    ``scaling``  -- None, or the ``ColumnScaling`` a block made by ``standardized()`` was scaled with.
+    ``scaling``  -- None, or the ``ColumnScaling`` a block made by ``standardized()`` was scaled with;
+    ``anomaly``  -- None, or the ``SeasonalAnomalies`` model a block made by ``seasonal_anomalies()`` had removed;
+    ``group_scaling`` -- None, or the ``GroupScaling`` a block made by ``standardized_by_group()`` was scaled with.
 
     Pass it as ``data`` to ``ArchetypalAnalysis.fit_transform / transform`` or
     ``GPNHConvexCoding.fit_transform``; ``close()`` (or ``with``) frees the device copy."""
 
-    def __init__(self, ctx, shape, valid, original_shape, scaling=None):
+    def __init__(self, ctx, shape, valid, original_shape, scaling=None, anomaly=None, group_scaling=None):
         self._ctx = ctx
         self.shape = shape
         self.valid = valid
         self.original_shape = original_shape
         self.scaling = scaling
+        self.anomaly = anomaly
+        self.group_scaling = group_scaling
         self.ndim = 2
         self._host = None
         self._stats = None
@@ -185,6 +333,85 @@ class DeviceData(object):
             ctx.close()
             raise
         return DeviceData(ctx, self.shape, self.valid, self.original_shape, ColumnScaling(stats, bool(center)))
+
+    def seasonal_anomalies(self, period=12, base_rows=None, trend_order=1):
+        """A new ``DeviceData`` (same device and dtype, a lifetime of its own) holding the monthly anomalies of the
+        reference notebook ``hadisst_sst_anom.ipynb`` (``calculate_monthly_anomalies``): ``x - cycle[t mod period]
+        - (intercept + slope t)``, the rows being equally spaced times ``t = 0 .. n - 1`` -- see
+        ``seasonal_coefficients`` for the model, ``base_rows = (lo, hi)`` for the notebook's base period and
+        ``trend_order=0`` for no detrending.  One weighted-sums pass over the resident matrix gives the model
+        (aa_data_weighted_column_sums, float64), one read-and-write pass the anomalies (aa_set_data_rows_model, the
+        notebook's order ``(x - cycle) - fitted``, one rounding to the block's dtype).  Every refusal is a
+        ``ValueError`` raised before any device call.  ``valid``, ``original_shape`` and ``scaling`` are inherited;
+        ``anomaly`` holds the ``SeasonalAnomalies`` record.  The model is tied to the row index (row ``r`` has
+        phase ``r mod period`` and time ``r``), so ``rows()`` and ``take()`` of the new block carry no record."""
+        n = self.shape[0]
+        A, _ = seasonal_coefficients(n, period, base_rows, trend_order)
+        lo, hi = _checked_row_range(base_rows, n, "base_rows")
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        P = int(period)
+        model = self._ctx.data_weighted_column_sums(A)
+        cycle = model[:P].copy()
+        slope, icpt = (model[P].copy(), model[P + 1].copy()) if trend_order else (None, None)
+        ctx = _backend.Context(dtype=self.dtype, device=self._ctx.device)
+        try:
+            ctx.set_data_rows_model(self._ctx, 0, n, groups=np.arange(n) % P, shift=cycle, intercept=icpt,
+                                    slope=slope, t=None if slope is None else np.arange(n, dtype=np.float64))
+        except Exception:
+            ctx.close()
+            raise
+        return DeviceData(ctx, self.shape, self.valid, self.original_shape, self.scaling,
+                          anomaly=SeasonalAnomalies(P, (lo, hi), cycle, slope, icpt))
+
+    def grouped_column_stats(self, groups, rows=None):
+        """``GroupedColumnStats(mean, std, counts)``: the column statistics of each group of rows, ``groups`` holding
+        one integer label ``0 .. G - 1`` per row, ``G <= 16`` -- the notebook's ``groupby(time.month).mean() /
+        .std()`` (ddof 0).  ``rows = (lo, hi)`` counts only those rows, the notebook's base period; every group
+        needs at least one counted row.  Two float64 sweeps over the resident matrix, the second over the
+        deviations from the first's means (aa_data_weighted_column_sums, aa_data_grouped_sqdev).  Refusals are
+        ``ValueError``s raised before any device call."""
+        n = self.shape[0]
+        labels, G = _checked_groups(groups, n, "DeviceData.grouped_column_stats")
+        lo, hi = _checked_row_range(rows, n, "DeviceData.grouped_column_stats: rows")
+        counted = np.full(n, -1, dtype=np.intc)
+        counted[lo:hi] = labels[lo:hi]
+        counts = np.bincount(counted[lo:hi], minlength=G)
+        if np.any(counts == 0):
+            raise ValueError("DeviceData.grouped_column_stats: group %d has no counted row"
+                             % np.flatnonzero(counts == 0)[0])
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        A = (counted[None, :] == np.arange(G)[:, None]) / counts[:, None].astype(np.float64)
+        mean = self._ctx.data_weighted_column_sums(A)
+        var = self._ctx.data_weighted_column_sums(A, groups=counted, centre=mean)
+        return GroupedColumnStats(mean, np.sqrt(var), counts)
+
+    def standardized_by_group(self, groups, stats=None, center=True):
+        """A new ``DeviceData`` (same device and dtype, a lifetime of its own) holding ``(x - mean[g]) / std[g]``
+        with ``g = groups[row]``, or ``x / std[g]`` without ``center``: the notebook's per-month standardisation
+        ``(x - mean_month) / std_month``.  ``stats``: None (this block's own ``grouped_column_stats(groups)``) or
+        the ``GroupedColumnStats`` of a base period (``grouped_column_stats(groups, rows=...)``) or of another
+        block.  A zero or non-finite std is a ``ValueError`` raised before anything is copied.  ``valid``,
+        ``original_shape`` and ``scaling`` are inherited; ``group_scaling`` records ``(stats, center, groups)``
+        (tied to the row index: ``rows()`` and ``take()`` of the new block carry none)."""
+        n = self.shape[0]
+        labels, G = _checked_groups(groups, n, "DeviceData.standardized_by_group")
+        if stats is not None:
+            shift, scale = _checked_group_stats(stats, G, self.shape[1], center)
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        if stats is None:
+            stats = self.grouped_column_stats(labels)
+            shift, scale = _checked_group_stats(stats, G, self.shape[1], center)
+        ctx = _backend.Context(dtype=self.dtype, device=self._ctx.device)
+        try:
+            ctx.set_data_rows_model(self._ctx, 0, n, groups=labels, shift=shift, scale=scale)
+        except Exception:
+            ctx.close()
+            raise
+        return DeviceData(ctx, self.shape, self.valid, self.original_shape, self.scaling,
+                          group_scaling=GroupScaling(stats, bool(center), labels))
 
     def unscale(self, array):
         """Host only: a ``(..., n_features)`` array in this block's units (archetypes, a dictionary's transpose,

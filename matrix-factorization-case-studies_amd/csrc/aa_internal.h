@@ -439,6 +439,15 @@ int launch_col_moments(Ctx *c, double *partial_dev /* nslab x p_pad */, double *
                        double *var_dev /* p_pad, nullable */);
 int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shift_dev /*nullable*/,
                        const double *scale_dev /*nullable*/);
+// weighted column sums (at most AA_MAX_COEF_ROWS coefficient rows, on the f64 matrix cores) and the per-row model
+// copy behind aa_data_weighted_column_sums / aa_data_grouped_sqdev / aa_set_data_rows_model
+#define AA_MAX_COEF_ROWS 16
+int launch_col_weighted_sums(Ctx *c, int G, const double *At_dev /* n x 16 */, const int *grp_dev /* n, nullable */,
+                             const double *centre_dev /* Gc x p_pad, nullable: plain sums */,
+                             double *partial_dev /* nslab x G x p_pad */, double *out_dev /* G x p_pad */);
+int launch_model_rows(Ctx *c, const void *owner_X, long row0, const int *grp_dev, const double *shift_dev,
+                      const double *icpt_dev, const double *slope_dev, const double *t_dev, const double *scale_dev,
+                      void *dst = nullptr /* null: c->X; else a buffer of its layout (aa_time_kernel) */);
 // row gather behind aa_set_data_take (idx_dev null: the rows in order) and the float64 feature buffer of an
 // implicit kernel from a resident matrix; owner_dtype / owner_ld: element type and leading dimension of owner_X
 int launch_gather_rows(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, const long *idx_dev,

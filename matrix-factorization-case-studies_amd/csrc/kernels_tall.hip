@@ -3071,6 +3071,210 @@ int launch_affine_rows(Ctx *c, const void *owner_X, long row0, const double *shi
     return AA_OK;
 }
 
+// ---- weighted column sums and the per-row model copy (the reference notebook's monthly anomalies and its
+// per-month standardisation, on the resident matrix: aa_data_weighted_column_sums, aa_data_grouped_sqdev,
+// aa_set_data_rows_model)
+//
+// partial[slab][g][j] = sum over the slab's rows t of A[g][t] f(x[t][j]), g < 16, all in float64, with f(x) = x
+// (SQ = false) or f(x) = (x - centre[grp[t]][j])^2, 0 where grp[t] < 0 (SQ = true).  The contraction over rows
+// runs on v_mfma_f64_16x16x4_f64: the 16 coefficient rows are M, 16 columns of X are N, four rows of X are K --
+//   A lane l = At[t0 + (l>>4)][l&15]  (At: the coefficients transposed, n x 16, rows g >= G zero: a K step
+//                                      reads 512 contiguous bytes),
+//   B lane l = f(x[t0 + (l>>4)][column of l&15]),
+//   D lane l, reg q = out[g = (l>>4) + 4 q][column of l&15].
+// A WAVE owns 128 adjacent columns (eight 16-column tiles) and one row slab; there is no LDS and no barrier, the
+// four waves of a block take four adjacent column groups of the same slab, so they share their At loads in
+// L1.  A lane loads 8 elements of a row in 16-byte vectors: vector i covers the columns cw + 16 V i + V (l&15) + e,
+// so one load instruction reads 256-byte runs of four rows, and tile i V + e takes column e of vector i.  Whole
+// groups of U K steps are loaded before they are used (U x 8 elements per lane in flight); the slab's last rows
+// go one K step at a time, rows beyond the slab contributing a = 0 and f = 0 (selected, not multiplied: nothing
+// is read there).  Each tile is one MFMA accumulation chain in ascending row order: the same bits on every call.
+// Padding columns: x = 0 and centre = 0 there (zero-filled allocations), so their sums are zero.
+template <typename T, bool SQ>
+__global__ __launch_bounds__(256) void k_col_weighted_sums(const T *__restrict__ X, long ld, long n, long rps,
+                                                           const double *__restrict__ At, const int *__restrict__ grp,
+                                                           const double *__restrict__ centre, int G,
+                                                           double *__restrict__ partial)
+{
+    typedef ColVec<T> CV;
+    typedef typename CV::vec vec;
+    constexpr int V = CV::V, NV = 8 / V, U = SQ ? 2 : 4;
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, lc = lane & 15, lr = lane >> 4;
+    const long cw = ((long)blockIdx.x * 4 + wave) * 128;
+    if (cw >= ld) return;                               // wave-uniform, and the kernel has no barrier
+    const long r0 = (long)blockIdx.y * rps;
+    const long r1 = r0 + rps < n ? r0 + rps : n;
+    const T *src = X + cw + V * lc;
+    const double *cen = SQ ? centre + cw + V * lc : nullptr;
+    f64x4 acc[8];
+#pragma unroll
+    for (int i = 0; i < 8; ++i) acc[i] = (f64x4){0.0, 0.0, 0.0, 0.0};
+
+    // one K step: x[] holds the lane's 8 elements of row `row` (widened), a its coefficient
+    auto step = [&](long row, bool ok, double *x, double a) {
+        if (SQ) {
+            const int g = ok ? grp[row] : -1;
+            if (g >= 0) {
+                const double *ce = cen + (long)g * ld;
+#pragma unroll
+                for (int i = 0; i < NV; ++i)
+#pragma unroll
+                    for (int e = 0; e < V; ++e) {
+                        const double d = x[i * V + e] - ce[16 * V * i + e];
+                        x[i * V + e] = d * d;
+                    }
+            } else {
+#pragma unroll
+                for (int i = 0; i < 8; ++i) x[i] = 0.0;
+            }
+        }
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = __builtin_amdgcn_mfma_f64_16x16x4f64(a, x[i], acc[i], 0, 0, 0);
+    };
+
+    long t = r0;
+    for (; t + 4 * U <= r1; t += 4 * U) {
+        vec q[U][NV];
+        double a[U];
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            const long row = t + 4 * u + lr;
+#pragma unroll
+            for (int i = 0; i < NV; ++i) q[u][i] = *reinterpret_cast<const vec *>(src + row * ld + 16 * V * i);
+            a[u] = At[row * 16 + lc];
+        }
+#pragma unroll
+        for (int u = 0; u < U; ++u) {
+            double x[8];
+#pragma unroll
+            for (int i = 0; i < NV; ++i) colvec_get(q[u][i], x + V * i);
+            step(t + 4 * u + lr, true, x, a[u]);
+        }
+    }
+    for (; t < r1; t += 4) {
+        const long row = t + lr;
+        const bool ok = row < r1;
+        double x[8], a = 0.0;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) x[i] = 0.0;
+        if (ok) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+                colvec_get(*reinterpret_cast<const vec *>(src + row * ld + 16 * V * i), x + V * i);
+            a = At[row * 16 + lc];
+        }
+        step(row, ok, x, a);
+    }
+
+    double *dst = partial + (long)blockIdx.y * G * ld + cw + V * lc;
+#pragma unroll
+    for (int qq = 0; qq < 4; ++qq) {
+        const int g = lr + 4 * qq;
+        if (g < G) {
+#pragma unroll
+            for (int i = 0; i < NV; ++i)
+#pragma unroll
+                for (int e = 0; e < V; ++e) dst[(long)g * ld + 16 * V * i + e] = acc[i * V + e][qq];
+        }
+    }
+}
+
+// out_dev (G x p_pad) = the slab partials (nslab x G x p_pad) added per entry in the fixed order of
+// k_col_moment_finish, which sees G p_pad "columns" and divides by 1 (exact).  At_dev: n x 16 coefficients;
+// grp_dev / centre_dev (Gc x p_pad, padding columns zero): null for the plain sums.
+int launch_col_weighted_sums(Ctx *c, int G, const double *At_dev, const int *grp_dev, const double *centre_dev,
+                             double *partial_dev, double *out_dev)
+{
+    long nslab = 0;
+    const long rps = moment_slab_rows(c->n, c->p_pad, &nslab);
+    const long xb = c->p_pad / 128;
+    const dim3 grid((unsigned)((xb + 3) / 4), (unsigned)nslab);
+#define WSUMS(T, SQ)                                                                                              \
+    hipLaunchKernelGGL((k_col_weighted_sums<T, SQ>), grid, dim3(256), 0, c->stream, (const T *)c->X.as<T>(),      \
+                       c->p_pad, c->n, rps, At_dev, grp_dev, centre_dev, G, partial_dev)
+    if (c->dtype == AA_F32) {
+        if (centre_dev) WSUMS(float, true); else WSUMS(float, false);
+    } else {
+        if (centre_dev) WSUMS(double, true); else WSUMS(double, false);
+    }
+#undef WSUMS
+    AA_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k_col_moment_finish, dim3((unsigned)(G * c->p_pad / 8)), dim3(256), 0, c->stream,
+                       (const double *)partial_dev, (long)G * c->p_pad, nslab, 1.0, out_dev);
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+// Y[r][j] = (T)(((x - shift[grp[r]][j]) - (icpt[j] + slope[j] t[r])) / scale[grp[r]][j]) with x = X[row0 + r][j]:
+// exactly the float64 roundings of the NumPy expression ((X - shift[grp]) - (icpt + slope * t[:, None])) / scale[grp]
+// -- a subtraction, a product, a sum (kept apart from the product: the build contracts by default), a subtraction,
+// a true division -- and one rounding to T.  Each of the three parts is left out when its table is null (grp null:
+// every row uses row 0 of the tables).  Column mapping and padding as in k_affine_rows; the tables are G x ld.
+template <typename T>
+__global__ __launch_bounds__(256) void k_model_rows(const T *__restrict__ X, long ld, long row0, long n, long p,
+                                                    const int *__restrict__ grp, const double *__restrict__ shift,
+                                                    const double *__restrict__ icpt, const double *__restrict__ slope,
+                                                    const double *__restrict__ tt, const double *__restrict__ scale,
+                                                    T *__restrict__ Y)
+{
+    typedef ColVec<T> CV;
+    typedef typename CV::vec vec;
+    constexpr int V = CV::V, CL = CV::CL, RL = CV::RL;
+    const int cl = threadIdx.x % CL, rl = threadIdx.x / CL;
+    const long col = (long)blockIdx.x * 128 + cl * V;
+    if (col >= p) return;
+    double ic[V], sl[V];
+#pragma unroll
+    for (int v = 0; v < V; ++v) {
+        ic[v] = (slope && col + v < p) ? icpt[col + v] : 0.0;
+        sl[v] = (slope && col + v < p) ? slope[col + v] : 0.0;
+    }
+    for (long r = (long)blockIdx.y * RL + rl; r < n; r += (long)gridDim.y * RL) {
+        double x[V];
+        colvec_get(*reinterpret_cast<const vec *>(X + (row0 + r) * ld + col), x);
+        const long g = grp ? grp[r] : 0;
+        const double tr = slope ? tt[r] : 0.0;
+#pragma unroll
+        for (int v = 0; v < V; ++v) {
+            double y = 0.0;
+            if (col + v < p) {
+                y = x[v];
+                if (shift) y = y - shift[g * ld + col + v];
+                if (slope) y = y - __dadd_rn(ic[v], __dmul_rn(sl[v], tr));
+                if (scale) y = y / scale[g * ld + col + v];
+            }
+            x[v] = y;
+        }
+        *reinterpret_cast<vec *>(Y + r * ld + col) = colvec_put(x, T());
+    }
+}
+
+// c->X (zero filled, c->n x c->p_pad) from rows [row0, row0 + c->n) of the owner's matrix of the same p_pad;
+// grp_dev / t_dev: c->n entries, shift_dev / scale_dev: G x p_pad, icpt_dev / slope_dev: p_pad (all nullable;
+// icpt, slope and t together); dst: null for c->X, or a buffer of its layout (aa_time_kernel)
+int launch_model_rows(Ctx *c, const void *owner_X, long row0, const int *grp_dev, const double *shift_dev,
+                      const double *icpt_dev, const double *slope_dev, const double *t_dev, const double *scale_dev,
+                      void *dst)
+{
+    if (!dst) dst = c->X.p;
+    const long xb = c->p_pad / 128;
+    const long RL = c->dtype == AA_F32 ? ColVec<float>::RL : ColVec<double>::RL;
+    long yb = (4096 + xb - 1) / xb;
+    if (yb > (c->n + RL - 1) / RL) yb = (c->n + RL - 1) / RL;
+    if (yb > 65535) yb = 65535;
+    const dim3 grid((unsigned)xb, (unsigned)yb);
+    if (c->dtype == AA_F32)
+        hipLaunchKernelGGL(k_model_rows<float>, grid, dim3(256), 0, c->stream, reinterpret_cast<const float *>(owner_X),
+                           c->p_pad, row0, c->n, c->p, grp_dev, shift_dev, icpt_dev, slope_dev, t_dev, scale_dev,
+                           reinterpret_cast<float *>(dst));
+    else
+        hipLaunchKernelGGL(k_model_rows<double>, grid, dim3(256), 0, c->stream, reinterpret_cast<const double *>(owner_X),
+                           c->p_pad, row0, c->n, c->p, grp_dev, shift_dev, icpt_dev, slope_dev, t_dev, scale_dev,
+                           reinterpret_cast<double *>(dst));
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
 // ---- row gather and the feature buffer of an implicit kernel, both from a resident matrix (aa_set_data_take,
 // aa_set_*_features_resident).  Y[r][j] = (TO)X[src(r)][j] for r < n, j < p, src(r) = idx ? idx[r] : r; the
 // conversion is the identity or the exact widening float -> double.  A block covers 128 adjacent columns (32

@@ -1048,6 +1048,133 @@ int aa_data_column_moments(aa_ctx *h, double *mean, double *var)
     return AA_OK;
 }
 
+// out (G x p, host) = the weighted column sums of c's matrix; group / centre null: plain sums
+static int weighted_column_sums(aa_ctx *h, const char *who, int G, const double *A, const int *group,
+                                const double *centre, int Gc, double *out)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "%s: no stored data matrix (data form)", who);
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "%s is single-rank", who);
+    AA_REQUIRE(A && out, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(G >= 1 && G <= AA_MAX_COEF_ROWS, AA_ERR_ARG, "%s: %d coefficient rows (1 to %d are supported)", who, G,
+               AA_MAX_COEF_ROWS);
+    if (centre) {
+        AA_REQUIRE(group && Gc >= 1 && Gc <= AA_MAX_COEF_ROWS, AA_ERR_ARG,
+                   "%s: a centre table needs row labels and 1 to %d rows; got %d", who, AA_MAX_COEF_ROWS, Gc);
+        for (long r = 0; r < c->n; ++r)
+            AA_REQUIRE(group[r] >= -1 && group[r] < Gc, AA_ERR_ARG, "%s: group[%ld] = %d is outside [-1, %d)", who, r,
+                       group[r], Gc);
+    }
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(join_side(c));
+    long nslab = 0;
+    (void)moment_slab_rows(c->n, c->p_pad, &nslab);
+    std::vector<double> At((size_t)c->n * AA_MAX_COEF_ROWS, 0.0);            // transposed, rows g >= G zero
+    for (int g = 0; g < G; ++g)
+        for (long t = 0; t < c->n; ++t) At[(size_t)t * AA_MAX_COEF_ROWS + g] = A[(size_t)g * c->n + t];
+    ScopedDevBuf dAt, dgrp, dcen, partial, sums;
+    AA_CHECK(dAt.alloc(At.size() * sizeof(double)));
+    AA_CHECK(partial.alloc((size_t)nslab * G * c->p_pad * sizeof(double)));
+    AA_CHECK(sums.alloc((size_t)G * c->p_pad * sizeof(double)));
+    AA_CHECK_HIP(ctx_memcpy(c, dAt.p, At.data(), At.size() * sizeof(double), hipMemcpyHostToDevice));
+    if (centre) {
+        AA_CHECK(dgrp.alloc((size_t)c->n * sizeof(int)));
+        AA_CHECK(dcen.alloc((size_t)Gc * c->p_pad * sizeof(double)));     // zero filled: the padding columns stay zero
+        AA_CHECK_HIP(ctx_memcpy(c, dgrp.p, group, (size_t)c->n * sizeof(int), hipMemcpyHostToDevice));
+        AA_CHECK_HIP(ctx_memcpy2d(c, dcen.p, (size_t)c->p_pad * sizeof(double), centre, (size_t)c->p * sizeof(double),
+                                  (size_t)c->p * sizeof(double), (size_t)Gc, hipMemcpyHostToDevice));
+    }
+    AA_CHECK(launch_col_weighted_sums(c, G, dAt.as<double>(), centre ? dgrp.as<int>() : (const int *)nullptr,
+                                      centre ? dcen.as<double>() : (const double *)nullptr, partial.as<double>(),
+                                      sums.as<double>()));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy2d(c, out, (size_t)c->p * sizeof(double), sums.p, (size_t)c->p_pad * sizeof(double),
+                              (size_t)c->p * sizeof(double), (size_t)G, hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+int aa_data_weighted_column_sums(aa_ctx *h, int G, const double *A, double *out)
+{
+    return weighted_column_sums(h, "aa_data_weighted_column_sums", G, A, nullptr, nullptr, 0, out);
+}
+
+int aa_data_grouped_sqdev(aa_ctx *h, int G, const double *A, const int *group, const double *centre, int Gc, double *out)
+{
+    AA_REQUIRE(group && centre, AA_ERR_ARG, "null argument");
+    return weighted_column_sums(h, "aa_data_grouped_sqdev", G, A, group, centre, Gc, out);
+}
+
+int aa_set_data_rows_model(aa_ctx *h, const aa_ctx *owner, long row0, long n, int G, const int *group,
+                           const double *shift, const double *icpt, const double *slope, const double *t,
+                           const double *scale)
+{
+    AA_CHECK(check_owner(h, owner, "aa_set_data_rows_model", AA_ERR_ARG, DTYPE_SAME));
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
+               row0 + n, o->n);
+    const bool tables = shift || scale, trend = icpt || slope || t;
+    AA_REQUIRE(!trend || (icpt && slope && t), AA_ERR_ARG,
+               "aa_set_data_rows_model: intercept, slope and row times come together or not at all");
+    // refused before anything of ctx is released: too many groups, a label without a table row, a zero or
+    // non-finite divisor, a non-finite shift, slope, intercept or row time
+    AA_REQUIRE(G >= 1 && G <= AA_MAX_COEF_ROWS, AA_ERR_ARG, "aa_set_data_rows_model: %d groups (1 to %d are supported)",
+               G, AA_MAX_COEF_ROWS);
+    AA_REQUIRE(!tables || group || G == 1, AA_ERR_ARG, "aa_set_data_rows_model: tables of %d groups need row labels", G);
+    for (long r = 0; tables && group && r < n; ++r)
+        AA_REQUIRE(group[r] >= 0 && group[r] < G, AA_ERR_ARG, "aa_set_data_rows_model: group[%ld] = %d is outside [0, %d)",
+                   r, group[r], G);
+    for (long j = 0; tables && j < (long)G * o->p; ++j) {
+        AA_REQUIRE(!scale || (scale[j] != 0.0 && scale[j] - scale[j] == 0.0), AA_ERR_ARG,
+                   "aa_set_data_rows_model: scale[%ld][%ld] = %g is zero or not finite", j / o->p, j % o->p, scale[j]);
+        AA_REQUIRE(!shift || shift[j] - shift[j] == 0.0, AA_ERR_ARG,
+                   "aa_set_data_rows_model: shift[%ld][%ld] = %g is not finite", j / o->p, j % o->p, shift[j]);
+    }
+    for (long j = 0; trend && j < o->p; ++j)
+        AA_REQUIRE(icpt[j] - icpt[j] == 0.0 && slope[j] - slope[j] == 0.0, AA_ERR_ARG,
+                   "aa_set_data_rows_model: intercept %g / slope %g of column %ld is not finite", icpt[j], slope[j], j);
+    for (long r = 0; trend && r < n; ++r)
+        AA_REQUIRE(t[r] - t[r] == 0.0, AA_ERR_ARG, "aa_set_data_rows_model: t[%ld] = %g is not finite", r, t[r]);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    const size_t row = (size_t)o->p_pad * sizeof(double), used = (size_t)o->p * sizeof(double);
+    ScopedDevBuf dgrp, dtab, dtrend, dt;                  // dtab: shift | scale, G x p_pad each; dtrend: icpt | slope
+    const int *g_dev = nullptr;
+    const double *shift_dev = nullptr, *scale_dev = nullptr, *icpt_dev = nullptr, *slope_dev = nullptr, *t_dev = nullptr;
+    if (tables && group) {
+        AA_CHECK(dgrp.alloc((size_t)n * sizeof(int)));
+        AA_CHECK_HIP(ctx_memcpy(c, dgrp.p, group, (size_t)n * sizeof(int), hipMemcpyHostToDevice));
+        g_dev = dgrp.as<int>();
+    }
+    if (tables) {
+        AA_CHECK(dtab.alloc((size_t)2 * G * row));
+        if (shift) {
+            shift_dev = dtab.as<double>();
+            AA_CHECK_HIP(ctx_memcpy2d(c, dtab.p, row, shift, used, used, (size_t)G, hipMemcpyHostToDevice));
+        }
+        if (scale) {
+            scale_dev = dtab.as<double>() + (size_t)G * o->p_pad;
+            AA_CHECK_HIP(ctx_memcpy2d(c, dtab.as<double>() + (size_t)G * o->p_pad, row, scale, used, used, (size_t)G,
+                                      hipMemcpyHostToDevice));
+        }
+    }
+    if (trend) {
+        AA_CHECK(dtrend.alloc(2 * row));
+        AA_CHECK(dt.alloc((size_t)n * sizeof(double)));
+        icpt_dev = dtrend.as<double>();
+        slope_dev = dtrend.as<double>() + o->p_pad;
+        t_dev = dt.as<double>();
+        AA_CHECK_HIP(ctx_memcpy(c, dtrend.p, icpt, used, hipMemcpyHostToDevice));
+        AA_CHECK_HIP(ctx_memcpy(c, dtrend.as<double>() + o->p_pad, slope, used, hipMemcpyHostToDevice));
+        AA_CHECK_HIP(ctx_memcpy(c, dt.p, t, (size_t)n * sizeof(double), hipMemcpyHostToDevice));
+    }
+    AA_CHECK(install_begin(c, install_rows(n, o->p, o->p_pad)));
+    AA_CHECK(launch_model_rows(c, o->X.p, row0, g_dev, shift_dev, icpt_dev, slope_dev, t_dev, scale_dev));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    install_commit(c);
+    return AA_OK;
+}
+
 int aa_set_data_weighted(aa_ctx *h, const void *raw, int host_dtype, long n_total, long p_full, long ld,
                          const double *col_weight, long row0, long n, unsigned char *valid, long *p_valid)
 {
@@ -2651,9 +2778,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     else if (which == 12)                        // either stored form (not has_stored_data), like aa_pass_reduce_rows
         AA_REQUIRE(c->have_data && !c->implicit_kernel && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
-    else if (which == 13 || which == 14)
+    else if (which >= 13 && which <= 17)
         AA_REQUIRE(has_stored_data(c) && c->world == 1 && !c->force_comm, AA_ERR_STATE,
-                   "aa_time_kernel 13 / 14: a stored data matrix (data form), single rank");
+                   "aa_time_kernel 13 .. 17: a stored data matrix (data form), single rank");
     else
         AA_REQUIRE(has_stored_data(c) && c->have_state, AA_ERR_STATE, "aa_time_kernel: needs data-form state on a stored matrix");
     AA_CHECK_HIP(hipSetDevice(c->device));
@@ -2677,6 +2804,25 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         rc = perm.alloc(idx.size() * sizeof(long));
         if (rc == AA_OK && ctx_memcpy(c, perm.p, idx.data(), idx.size() * sizeof(long), hipMemcpyHostToDevice) != hipSuccess) {
             set_error("aa_time_kernel 13: upload of the permutation failed");
+            rc = AA_ERR_HIP;
+        }
+    }
+    // 15 / 16: 16 coefficient rows (the values do not matter to the time), 16: rows labelled r mod 12 and a zero
+    // centre table; 17: the anomalies form of the model copy (12 x p_pad shift table, trend) into a scratch copy
+    ScopedDevBuf coef, labels, tables, partial;
+    long nslab = 0;
+    (void)moment_slab_rows(c->n, c->p_pad, &nslab);
+    if (which >= 15 && which <= 17 && rc == AA_OK) {
+        std::vector<int> grp((size_t)c->n);
+        for (long r = 0; r < c->n; ++r) grp[(size_t)r] = (int)(r % 12);
+        rc = labels.alloc(grp.size() * sizeof(int));
+        if (rc == AA_OK) rc = coef.alloc((size_t)c->n * AA_MAX_COEF_ROWS * sizeof(double));      // At, or t in its first n
+        if (rc == AA_OK) rc = tables.alloc((size_t)(2 * AA_MAX_COEF_ROWS + 2) * c->p_pad * sizeof(double));
+        if (rc == AA_OK && which != 17)
+            rc = partial.alloc((size_t)(nslab + 1) * AA_MAX_COEF_ROWS * c->p_pad * sizeof(double));
+        if (rc == AA_OK && which == 17) rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));
+        if (rc == AA_OK && ctx_memcpy(c, labels.p, grp.data(), grp.size() * sizeof(int), hipMemcpyHostToDevice) != hipSuccess) {
+            set_error("aa_time_kernel 15 .. 17: upload of the row labels failed");
             rc = AA_ERR_HIP;
         }
     }
@@ -2705,6 +2851,15 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                 rc = launch_gather_rows(c, c->X.p, c->dtype, c->p_pad, perm.as<long>(), scratch.p);
             else if (which == 14)
                 rc = launch_features_from_data(c, c->X.p, c->dtype, c->p_pad, c->n, c->p, scratch.as<double>(), scratch_ld);
+            else if (which == 15 || which == 16)
+                rc = launch_col_weighted_sums(c, AA_MAX_COEF_ROWS, coef.as<double>(), which == 16 ? labels.as<int>() : nullptr,
+                                              which == 16 ? tables.as<double>() : nullptr, partial.as<double>(),
+                                              partial.as<double>() + (size_t)nslab * AA_MAX_COEF_ROWS * c->p_pad);
+            else if (which == 17)
+                rc = launch_model_rows(c, c->X.p, 0, labels.as<int>(), tables.as<double>(),
+                                       tables.as<double>() + (size_t)2 * AA_MAX_COEF_ROWS * c->p_pad,
+                                       tables.as<double>() + (size_t)(2 * AA_MAX_COEF_ROWS + 1) * c->p_pad, coef.as<double>(),
+                                       nullptr, scratch.p);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
@@ -2724,7 +2879,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (which == 13 || which == 14) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
+    if (which >= 13 && which <= 17) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
     return rc;
 }
 
