@@ -377,7 +377,8 @@ int aa_set_linear_kernel(aa_ctx *ctx, int on);
  * matrix K_ij = exp(-gamma ||x_i - x_j||^2) NEVER formed): uploads the n x p feature matrix (float64) and
  * switches the context to the kernel form of the algorithm; every product C K / K Z is one fused
  * distance + exp + multiply pass over the features (csrc/kernels_gemm.hip: k_rbf_kv), tr K = n, and
- * aa_distance_column returns sqrt(2 - 2 K_ij).  Single rank, float64 context.  An install
+ * aa_distance_column returns sqrt(2 - 2 K_ij).  AA_ERR_ARG unless gamma > 0 and finite; single rank and a
+ * float64 context, AA_ERR_STATE otherwise (a float32 context is refused here, not only by the binding).  An install
  * ("installing data" above); everything downstream (aa_set_state, aa_prepare, aa_iterate, aa_get_state ...) is the explicit kernel form's. */
 int aa_set_rbf_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma);
 /* The same for the polynomial kernel K_ij = (gamma x_i.x_j + coef0)^degree (scikit-learn's polynomial_kernel),
@@ -386,7 +387,9 @@ int aa_set_rbf_features(aa_ctx *ctx, const double *X, long n, long p, long ld, d
  * (csrc/kernels_gemm.hip: k_poly_kv_mfma), tr K = sum_i (gamma |x_i|^2 + coef0)^degree is summed in a fixed
  * order, and aa_distance_column returns sqrt(max(K_ii - 2 K_ij + K_jj, 0)) with exactly 0 at i = j.
  * AA_ERR_ARG unless gamma > 0, coef0 >= 0 (so that K is positive semi-definite), degree >= 1, all finite.
- * Single rank, float64 context. */
+ * Single rank, float64 context (AA_ERR_STATE).  Both kinds share one body (csrc/solver.hip: set_kernel_features)
+ * and one launcher of their products (csrc/kernels_gemm.hip: launch_kernel_product); a refused call has not
+ * touched ctx, and ctx names its kernel only once the features are in place. */
 int aa_set_poly_features(aa_ctx *ctx, const double *X, long n, long p, long ld, double gamma, double coef0,
                          int degree);
 /* aa_set_rbf_features / aa_set_poly_features with the features taken from owner's resident DATA matrix instead of

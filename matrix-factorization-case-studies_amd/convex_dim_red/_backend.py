@@ -420,6 +420,7 @@ class Context(object):
         self.row_lo = 0
         self.n_global = 0
         self._data_owner = None    # the context whose matrix this one aliases (share_data): kept alive
+        self._reference_kind = "rbf"   # the kind of the latest reference set (kernel_cross; the library refuses without one)
 
     def _adopt(self, n, p, row_lo=0, n_global=None, implicit=False, owner=None):
         """What an install left in the library (include/aa_hip.h, "installing data"); every setter of
@@ -582,24 +583,54 @@ class Context(object):
         _check(self.lib.aa_set_data_take(self.h, owner.h, ptr, int(n)))
         self._adopt(n, owner.p)
 
-    def _set_features_resident(self, owner, call, what):
+    # -- implicit kernels: 'rbf' exp(-gamma ||x - y||^2) and 'poly' (gamma x.y + coef0)^degree, never formed.  The
+    # library has one entry point per kind and operation (aa_set_<kind>_features, ..._features_resident,
+    # aa_set_<kind>_reference, aa_<kind>_cross); _kernel_call picks it and appends the kind's parameters
+    _KERNEL_NAMES = {"rbf": "RBF", "poly": "polynomial"}
+
+    def _kernel_call(self, entry, kind, gamma, coef0, degree, *args):
+        params = (float(gamma),) if kind == "rbf" else (float(gamma), float(coef0), int(degree))
+        _check(getattr(self.lib, entry % kind)(self.h, *(args + params)))
+
+    def _set_kernel_features(self, kind, gamma, coef0, degree, X=None, owner=None):
+        """The implicit kernel of the rows of ``X`` (host), or of ``owner``'s resident data matrix (nothing
+        crosses the bus; ``owner`` is only read), as this context's kernel matrix: kernel form, float64."""
+        if owner is None:
+            X = _c64(X)
+            if X.ndim != 2:
+                raise ValueError("feature matrix must be 2-D")
         if self.dtype_code != AA_F64:
-            raise ValueError("the implicit %s kernel needs a float64 context" % what)
-        _check(call())
-        self._adopt(owner.n, owner.n, implicit=True)
+            raise ValueError("the implicit %s kernel needs a float64 context" % self._KERNEL_NAMES[kind])
+        if owner is None:
+            n, p = X.shape
+            self._kernel_call("aa_set_%s_features", kind, gamma, coef0, degree, _ptr(X), n, p, p)
+        else:
+            n = owner.n
+            self._kernel_call("aa_set_%s_features_resident", kind, gamma, coef0, degree, owner.h)
+        self._adopt(n, n, implicit=True)
+
+    def set_rbf_features(self, X, gamma):
+        self._set_kernel_features("rbf", gamma, 0.0, 1, X=X)
+
+    def set_poly_features(self, X, gamma, coef0, degree):
+        self._set_kernel_features("poly", gamma, coef0, degree, X=X)
 
     def set_rbf_features_resident(self, owner, gamma):
-        """set_rbf_features with the rows of ``owner``'s resident data matrix as the features
-        (aa_set_rbf_features_resident): nothing crosses the bus; ``owner`` is only read."""
-        self._set_features_resident(
-            owner, lambda: self.lib.aa_set_rbf_features_resident(self.h, owner.h, float(gamma)), "RBF")
+        self._set_kernel_features("rbf", gamma, 0.0, 1, owner=owner)
 
     def set_poly_features_resident(self, owner, gamma, coef0, degree):
-        """set_poly_features with the rows of ``owner``'s resident data matrix as the features
-        (aa_set_poly_features_resident)."""
-        self._set_features_resident(
-            owner, lambda: self.lib.aa_set_poly_features_resident(self.h, owner.h, float(gamma), float(coef0),
-                                                                  int(degree)), "polynomial")
+        self._set_kernel_features("poly", gamma, coef0, degree, owner=owner)
+
+    @staticmethod
+    def _spec_args(spec):
+        """``(kind, gamma, coef0, degree)`` of a kernel dict ``dict(form=, gamma=[, coef0=, degree=])``."""
+        return spec["form"], spec["gamma"], spec.get("coef0", 0.0), spec.get("degree", 1)
+
+    def set_kernel_features(self, spec, X_or_owner):
+        """set_<form>_features[_resident] for the kernel ``spec`` names (KernelAA's ``_kernel_spec``); a
+        ``Context`` as the second argument is an owner."""
+        key = "owner" if isinstance(X_or_owner, type(self)) else "X"
+        self._set_kernel_features(*self._spec_args(spec), **{key: X_or_owner})
 
     def data_column_moments(self, mean=True, var=True):
         """``(mean[p], var[p])`` of the columns of the resident data matrix (aa_data_column_moments): two
@@ -633,30 +664,6 @@ class Context(object):
         _check(self.lib.aa_data_grouped_sqdev(self.h, A.shape[0], _ptr(A), groups.ctypes.data_as(_ip), _ptr(centre),
                                               centre.shape[0], _ptr(out)))
         return out
-
-    def set_rbf_features(self, X, gamma):
-        """The implicit RBF kernel exp(-gamma ||x_i - x_j||^2) of the rows of X as this context's kernel
-        matrix (never formed): kernel form of the algorithm, float64."""
-        X = _c64(X)
-        if X.ndim != 2:
-            raise ValueError("feature matrix must be 2-D")
-        if self.dtype_code != AA_F64:
-            raise ValueError("the implicit RBF kernel needs a float64 context")
-        n, p = X.shape
-        _check(self.lib.aa_set_rbf_features(self.h, _ptr(X), n, p, p, float(gamma)))
-        self._adopt(n, n, implicit=True)
-
-    def set_poly_features(self, X, gamma, coef0, degree):
-        """The implicit polynomial kernel (gamma x_i.x_j + coef0)^degree of the rows of X as this context's
-        kernel matrix (never formed): kernel form of the algorithm, float64, products on the f64 matrix cores."""
-        X = _c64(X)
-        if X.ndim != 2:
-            raise ValueError("feature matrix must be 2-D")
-        if self.dtype_code != AA_F64:
-            raise ValueError("the implicit polynomial kernel needs a float64 context")
-        n, p = X.shape
-        _check(self.lib.aa_set_poly_features(self.h, _ptr(X), n, p, p, float(gamma), float(coef0), int(degree)))
-        self._adopt(n, n, implicit=True)
 
     def set_linear_kernel(self, on):
         """The resident data matrix X stands in for the kernel K = X X' of KernelAA
@@ -959,40 +966,43 @@ class Context(object):
 
     # -- KernelAA.transform (aa_set_rbf_reference / aa_rbf_cross, aa_set_poly_reference / aa_poly_cross,
     # aa_kernel_transform_cost)
-    def set_rbf_reference(self, XS, V, gamma):
-        """Reference set of the cross RBF product for the resident rows Y (set_data): the training rows
+    def _set_kernel_reference(self, kind, gamma, coef0, degree, XS, V):
+        """Reference set of the cross kernel product for the resident rows Y (set_data): the training rows
         ``XS`` (s x p) and ``V`` (s x k, = D' on them).  Sizes the factor buffers for k components."""
         XS, V = _c64(XS), _c64(V)
         if XS.ndim != 2 or V.ndim != 2 or V.shape[0] != XS.shape[0]:
             raise ValueError("reference rows (s x p) and V (s x k) expected")
         s, p = XS.shape
         k = V.shape[1]
-        _check(self.lib.aa_set_rbf_reference(self.h, int(k), _ptr(XS), s, p, p, _ptr(V), k, float(gamma)))
+        self._kernel_call("aa_set_%s_reference", kind, gamma, coef0, degree, int(k), _ptr(XS), s, p, p, _ptr(V), k)
         self.k = k
+        self._reference_kind = kind
 
-    def rbf_cross(self, fetch=False):
-        """XW = rbf(Y, XS) V into the QP's linear-term buffer (what gpnh_weights_update reads); with
+    def _kernel_cross(self, kind, fetch):
+        """XW = kappa(Y, XS) V into the QP's linear-term buffer (what gpnh_weights_update reads); with
         ``fetch`` also returned (m x k)."""
         out = np.empty((self.n, self.k)) if fetch else None
-        _check(self.lib.aa_rbf_cross(self.h, None if out is None else _ptr(out)))
+        _check(getattr(self.lib, "aa_%s_cross" % kind)(self.h, None if out is None else _ptr(out)))
         return out
+
+    def set_rbf_reference(self, XS, V, gamma):
+        self._set_kernel_reference("rbf", gamma, 0.0, 1, XS, V)
 
     def set_poly_reference(self, XS, V, gamma, coef0, degree):
-        """set_rbf_reference for the polynomial kernel (gamma y.x + coef0)^degree."""
-        XS, V = _c64(XS), _c64(V)
-        if XS.ndim != 2 or V.ndim != 2 or V.shape[0] != XS.shape[0]:
-            raise ValueError("reference rows (s x p) and V (s x k) expected")
-        s, p = XS.shape
-        k = V.shape[1]
-        _check(self.lib.aa_set_poly_reference(self.h, int(k), _ptr(XS), s, p, p, _ptr(V), k, float(gamma),
-                                              float(coef0), int(degree)))
-        self.k = k
+        self._set_kernel_reference("poly", gamma, coef0, degree, XS, V)
+
+    def rbf_cross(self, fetch=False):
+        return self._kernel_cross("rbf", fetch)
 
     def poly_cross(self, fetch=False):
-        """XW = poly(Y, XS) V into the QP's linear-term buffer, as rbf_cross."""
-        out = np.empty((self.n, self.k)) if fetch else None
-        _check(self.lib.aa_poly_cross(self.h, None if out is None else _ptr(out)))
-        return out
+        return self._kernel_cross("poly", fetch)
+
+    def set_kernel_reference(self, spec, XS, V):
+        self._set_kernel_reference(*(self._spec_args(spec) + (XS, V)))
+
+    def kernel_cross(self, fetch=False):
+        """The cross product of the kernel the latest set_kernel_reference named."""
+        return self._kernel_cross(self._reference_kind, fetch)
 
     def kernel_transform_cost(self, A, diag=None):
         """0.5 sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) / m from the resident weights and linear terms;

@@ -616,7 +616,7 @@ def _float64_rows(data):
                 yield ctx
 
 
-def _implicit_kernel_spec(which, features, gamma, kwargs):
+def _kernel_spec(which, features, gamma, kwargs):
     """The feature-space kernel a ``KernelAA.fit_transform`` call names, checked: None for the linear kernel
     (explicit matrix or ``features=True``), else ``dict(form=, gamma=[, coef0=, degree=])`` with ``gamma``
     None for the default.  Pops ``degree`` / ``coef0`` from ``kwargs``; every refusal is a ValueError."""
@@ -663,9 +663,9 @@ class KernelAA(_BaseAA):
                    update_scale_factors=True, **kwargs):
         self.__dict__.pop('_transform_state', None)      # a failed fit leaves nothing to transform with
         features = kwargs.pop('features', False)
-        which = kwargs.pop('implicit_kernel', 'linear')
+        which = kwargs.pop('feature_kernel', 'linear')
         gamma = kwargs.pop('gamma', None)
-        spec = _implicit_kernel_spec(which, features, gamma, kwargs)     # ValueErrors before any device call
+        spec = _kernel_spec(which, features, gamma, kwargs)     # ValueErrors before any device call
         if spec is not None:
             return self._kernel_aa_implicit(kernel, spec, dictionary, weights, alpha, update_dictionary,
                                             update_weights, update_scale_factors, **kwargs)
@@ -724,7 +724,7 @@ class KernelAA(_BaseAA):
                             update_scale_factors, **kwargs):
         """SURVEY 8(f4), the alternative it names: a feature-space kernel of the rows of ``X``, never formed --
         the RBF kernel ``exp(-gamma ||x_i - x_j||^2)`` or the polynomial kernel ``(gamma x_i.x_j + coef0)^degree``
-        (``spec``: _implicit_kernel_spec).  The kernel form of the algorithm (reference :399-531, :673-910)
+        (``spec``: _kernel_spec).  The kernel form of the algorithm (reference :399-531, :673-910)
         with every product ``C K`` / ``K Z`` computed as one fused pass over the features
         (aa_set_rbf_features, aa_set_poly_features).  Same conventions, initialisers and RNG order as the
         explicit-kernel path: ``KernelAA(...).fit_transform(rbf_kernel(X, gamma=g))`` is what it reproduces
@@ -750,16 +750,10 @@ class KernelAA(_BaseAA):
             if on_device:
                 owner = stack.enter_context(X.borrow())
                 ctx = stack.enter_context(_backend.Context(dtype=np.float64, device=owner.device))
-                if spec['form'] == 'rbf':
-                    ctx.set_rbf_features_resident(owner, gamma)
-                else:
-                    ctx.set_poly_features_resident(owner, gamma, spec['coef0'], spec['degree'])
+                ctx.set_kernel_features(spec, owner)
             else:
                 ctx = stack.enter_context(_backend.Context(dtype=np.float64))
-                if spec['form'] == 'rbf':
-                    ctx.set_rbf_features(X, gamma)
-                else:
-                    ctx.set_poly_features(X, gamma, spec['coef0'], spec['degree'])
+                ctx.set_kernel_features(spec, X)
 
             def init_dictionary():
                 init = 'furthest_sum' if self.init is None else self.init
@@ -815,7 +809,7 @@ class KernelAA(_BaseAA):
         n_features``), of the polynomial kernel ``(gamma x_i.x_j + coef0)^degree`` -- which is then never
         formed."""
         if 'kernel' in kwargs:                 # (`kernel` is also the name of _kernel_aa's first argument)
-            kwargs['implicit_kernel'] = kwargs.pop('kernel')
+            kwargs['feature_kernel'] = kwargs.pop('kernel')
         self.cost, self.n_iter, self.avg_time_per_iter, self.cost_deltas = self._kernel_aa(
             data, dictionary=dictionary, weights=weights, alpha=alpha, **kwargs)
         return self.weights
@@ -911,14 +905,9 @@ class KernelAA(_BaseAA):
             ctx.gpnh_set_factors(k, W=D.T, Z=weights)                       # kappa(Y, X) D'
         elif form == 'linear':
             ctx.gpnh_set_factors(k, W=state['archetypes'].T, Z=weights)     # Y (D X)'
-        elif form == 'rbf':
-            ctx.set_rbf_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'])
-            ctx.rbf_cross()                                                 # kappa(Y, X_S) D_S'
-            ctx.gpnh_set_factors(k, Z=weights)
-        else:
-            ctx.set_poly_reference(state['support_rows'], state['support_dictionary'].T, state['gamma'],
-                                   state['coef0'], state['degree'])
-            ctx.poly_cross()
+        else:                                                               # 'rbf', 'poly': the state names the kernel
+            ctx.set_kernel_reference(state, state['support_rows'], state['support_dictionary'].T)
+            ctx.kernel_cross()                                              # kappa(Y, X_S) D_S'
             ctx.gpnh_set_factors(k, Z=weights)
 
     def kernel_scores(self, data, weights=None, diagonal=None):

@@ -71,6 +71,34 @@ __device__ __forceinline__ double poly_kappa(double s, const PolyKernel pk)
     return v;
 }
 
+// A feature-space kernel that is never formed: its kind and parameters, host side.  A context holds two
+// (Ctx::kernel, Ctx::cross).  Code that only asks whether a matrix is stored tests `kind` for non-zero; what
+// depends on the formula switches on it.  The device takes gamma (RBF) or poly() (POLY) by value.
+enum { IMPLICIT_RBF = 1, IMPLICIT_POLY = 2 };   // KernelSpec::kind
+struct KernelSpec {
+    int kind = 0;              // 0: none; RBF: exp(-gamma ||x - y||^2); POLY: poly_kappa(x.y, poly())
+    double gamma = 0.0, coef0 = 0.0;
+    int degree = 1;
+    PolyKernel poly() const { return PolyKernel{gamma, coef0, degree}; }
+    const char *name() const { return kind == IMPLICIT_POLY ? "polynomial" : "RBF"; }
+    const char *stem() const { return kind == IMPLICIT_POLY ? "poly" : "rbf"; }   // aa_set_<stem>_reference, ...
+    // what the kind's product kernels ask of the feature buffer: k_rbf_kv reads the features in pairs, the tile
+    // body of k_poly_kv_mfma in chunks of 32 that must stay inside the zero-padded row
+    long feat_ld(long p) const { return round_up(p, kind == IMPLICIT_POLY ? 32 : 2); }
+    bool cross_reads_norms() const { return kind == IMPLICIT_RBF; }   // |y_r|^2 and |x_c|^2 beside the dot product
+};
+// gamma > 0 (both kinds), coef0 >= 0 (K positive semi-definite) and degree >= 1 (POLY), all finite (a NaN fails
+// every comparison)
+inline int kernel_spec_check(const KernelSpec &s)
+{
+    if (s.kind == IMPLICIT_RBF) AA_REQUIRE(s.gamma > 0.0 && s.gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
+    if (s.kind == IMPLICIT_POLY)
+        AA_REQUIRE(s.gamma > 0.0 && s.gamma < 1e300 && s.coef0 >= 0.0 && s.coef0 < 1e300 && s.degree >= 1, AA_ERR_ARG,
+                   "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", s.gamma,
+                   s.coef0, s.degree);
+    return AA_OK;
+}
+
 // zero rows allocated past n_pad in X and in every tall array, so software-pipelined
 // kernels may prefetch past the end of their row range without a guard
 #define AA_SLACK_ROWS 64
@@ -200,7 +228,6 @@ inline LoopJudge loop_judge(const aa_iter_params *ip, int it, double cost0, Iter
 }
 
 // ------------------------------------------------------------------ context
-enum { IMPLICIT_RBF = 1, IMPLICIT_POLY = 2 };   // Ctx::implicit_kernel, Ctx::cross_kind
 struct Comm;   // RCCL wrapper (comm.hip)
 struct P2P;    // one-shot peer-to-peer all-reduce over IPC-mapped buffers (comm.hip)
 
@@ -318,21 +345,14 @@ struct Ctx {
     DevBuf qpPerm;                             // n ints: sample order of the lane kernel
     DevBuf feat, featNorm;                     // implicit kernels: features [n_pad][feat_ld] (float64) and their squared norms
     long feat_p = 0, feat_ld = 0;
-    // 0: none; IMPLICIT_RBF: K_ij = exp(-rbf_gamma ||x_i - x_j||^2) (aa_set_rbf_features); IMPLICIT_POLY:
-    // K_ij = poly_kappa(x_i.x_j, poly) (aa_set_poly_features).  Never formed.  Code that only asks whether a
-    // matrix is stored tests it for non-zero; what depends on the formula dispatches on the kind.
-    int implicit_kernel = 0;
-    double rbf_gamma = 0.0;
-    PolyKernel poly = {0.0, 0.0, 1};
+    KernelSpec kernel;                         // K_ij = kappa(x_i, x_j) of the features (aa_set_*_features); kind 0: none
     // KernelAA.transform on an implicit kernel (aa_set_rbf_reference, aa_set_poly_reference): the reference rows
     // X_S [cross_s_pad][p_pad], their squared norms (RBF), V = D' on them [cross_s_pad][KP], the squared norms of the
     // resident rows (also the linear kernel's diagonal), and the kernel-form cost's operands
     DevBuf crossX, crossNorm, crossV, rowNorm, xformCost;
     long cross_s = 0, cross_s_pad = 0;
     int cross_k = 0;
-    int cross_kind = 0;                        // IMPLICIT_RBF (cross_gamma) or IMPLICIT_POLY (cross_poly)
-    double cross_gamma = 0.0;
-    PolyKernel cross_poly = {0.0, 0.0, 1};
+    KernelSpec cross;                          // the reference set's kernel, valid while cross_s > 0
     DevBuf scoreScratch;                       // aa_gpnh_residual_scores: [slab][p_pad] | [split][n_pad] partials, the sums, the total
     DevBuf fsScratch;                          // FurthestSum on the device: running sums, one distance column, state, alive flags
     bool qp_iters_valid = false;               // qpIters belongs to the current rows / state
@@ -360,7 +380,7 @@ void spg_name(Ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3))
 
 // a stored matrix in data form: X holds the n x p rows themselves -- not a kernel matrix, and not nothing
 // behind an implicit kernel.  (An implicit kernel always comes with form == AA_FORM_KERNEL: install_begin.)
-inline bool has_stored_data(const Ctx *c) { return c->have_data && !c->implicit_kernel && c->form == AA_FORM_DATA; }
+inline bool has_stored_data(const Ctx *c) { return c->have_data && !c->kernel.kind && c->form == AA_FORM_DATA; }
 
 // ------------------------------------------------------------------ kernels_gemm.hip
 // out[KP][p_pad] (double) = sum_r A[r][i] * X[r][c];  A tall double, X T.
@@ -470,10 +490,8 @@ int launch_gpnh_cost(Ctx *c, double lambda, double *out_dev, int *slot_counter, 
 enum { ST_INIT_F = 0, ST_ALPHA = 1, ST_LINESEARCH = 2, ST_BB = 3, ST_CONV = 4 };
 int launch_row_sqnorm_sum(Ctx *c, double *trace_out_host);
 int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double *xj_host, double *d_host);
-int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall);   // out = K V for the implicit kernel (tall in, tall out)
-int launch_rbf_norms(Ctx *c);
-int launch_rbf_cross(Ctx *c);      // Gr (XW) = rbf(Y, X_S) V for the reference set of aa_set_rbf_reference
-int launch_poly_cross(Ctx *c);     // Gr (XW) = poly(Y, X_S) V for the reference set of aa_set_poly_reference
+int kernel_kv(Ctx *c, const double *V_tall, double *out_tall);   // out = K V for c->kernel (tall in, tall out)
+int kernel_cross(Ctx *c);          // Gr (XW) = kappa(Y, X_S) V for c->cross and the reference set of aa_set_*_reference
 int launch_poly_trace(Ctx *c, double *trace_out_host);   // sum_i poly_kappa(|x_i|^2) from featNorm, fixed order
 int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double *nrm);   // nrm[r] = |F_r|^2
 // sum_t (d_t - 2 z_t.XW_t + z_t' A z_t) over the resident rows (A: KP x KP device, d: device or null = 1;
@@ -481,7 +499,7 @@ int launch_row_norms(Ctx *c, const double *F, long ld, long p, long rows, double
 int launch_kernel_transform_cost(Ctx *c, const double *A_dev, const double *d_dev, double *part, double *out_host);
 // the same terms per sample (aa_kernel_sample_residuals): r_dev / dout_dev n doubles each, part 2 nb + 2 doubles
 // (nb = (n + 255) / 256) whose last two receive sum r and sum d; kind: AA_DIAG_*, d_dev (GIVEN) / nrm_dev (POLY
-// with c->cross_poly, LINEAR: squared row norms) n doubles.  Launches only
+// with c->cross.poly(), LINEAR: squared row norms) n doubles.  Launches only
 int launch_kernel_sample_residuals(Ctx *c, const double *A_dev, int kind, const double *d_dev, const double *nrm_dev,
                                    double *r_dev, double *dout_dev, double *part);
 int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n_ex, int extra_steps,

@@ -1716,58 +1716,6 @@ __global__ __launch_bounds__(256) void k_rbf_norms(const double *__restrict__ F,
     nrm[r] = s;
 }
 
-int launch_rbf_norms(Ctx *c)
-{
-    hipLaunchKernelGGL(k_rbf_norms, dim3((unsigned)((c->n_pad + 255) / 256)), dim3(256), 0, c->stream,
-                       (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n_pad, c->featNorm.as<double>());
-    AA_CHECK_HIP(hipGetLastError());
-    return AA_OK;
-}
-
-static int launch_poly_kv(Ctx *c, const double *V_tall, double *out_tall);
-
-int launch_implicit_kv(Ctx *c, const double *V_tall, double *out_tall)
-{
-    AA_REQUIRE(c->implicit_kernel && c->feat.p, AA_ERR_STATE, "no implicit kernel set");
-    if (c->implicit_kernel == IMPLICIT_POLY) return launch_poly_kv(c, V_tall, out_tall);
-    const long rtiles = c->n_pad / 64, ntile = c->n_pad / 64;
-    long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU
-    if (nsplit > ntile) nsplit = ntile;
-    if (nsplit < 1) nsplit = 1;
-    const long tps = (ntile + nsplit - 1) / nsplit;
-    nsplit = (ntile + tps - 1) / tps;
-    double *dst = out_tall;
-    if (nsplit > 1) {
-        AA_CHECK(c->rlPartial.alloc((size_t)nsplit * c->n_pad * c->KP * sizeof(double)));
-        dst = c->rlPartial.as<double>();
-    }
-    const dim3 grid((unsigned)rtiles, (unsigned)nsplit);
-    const size_t lds = (size_t)(64 * 65 + 64 * c->KP + 2 * 64 * 17) * sizeof(double);
-    static bool attr_rbf[64] = {false};
-    if (!attr_rbf[c->device & 63]) {
-        AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_kv<32>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_kv<64>),
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
-        attr_rbf[c->device & 63] = true;
-    }
-    if (c->KP == 32)
-        hipLaunchKernelGGL(k_rbf_kv<32>, grid, dim3(256), lds, c->stream, (const double *)c->feat.as<double>(), c->feat_ld,
-                           (int)c->feat_p, (const double *)c->featNorm.as<double>(), c->rbf_gamma, V_tall, c->n, c->n_pad,
-                           tps, dst);
-    else
-        hipLaunchKernelGGL(k_rbf_kv<64>, grid, dim3(256), lds, c->stream, (const double *)c->feat.as<double>(), c->feat_ld,
-                           (int)c->feat_p, (const double *)c->featNorm.as<double>(), c->rbf_gamma, V_tall, c->n, c->n_pad,
-                           tps, dst);
-    if (nsplit > 1) {
-        const long elems = c->n_pad * c->KP;
-        hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
-                           (const double *)dst, elems, (int)nsplit, out_tall);
-    }
-    AA_CHECK_HIP(hipGetLastError());
-    return AA_OK;
-}
-
 // ---------------------------------------------------------------------------
 // Cross RBF product of KernelAA.transform (archetypal_analysis.py:1151-1199 in kernel form):
 //   out[r][i] = sum_c exp(-gamma max(|y_r|^2 + |x_c|^2 - 2 y_r.x_c, 0)) V[c][i]
@@ -1893,10 +1841,10 @@ __global__ __launch_bounds__(256) void k_rbf_cross_mfma(const double *__restrict
 // formed:   out[r][i] = sum_c kappa(y_r, x_c) V[c][i]
 // on the tile body above, both contractions on v_mfma_f64_16x16x4_f64 and kappa(S) formed in the registers S
 // was computed in.  One kernel serves both products:
-//   * the fit (launch_implicit_kv): Y = X_S = the features of aa_set_poly_features ([n_pad][feat_ld], feat_ld =
+//   * the fit (kernel_kv): Y = X_S = the features of aa_set_poly_features ([n_pad][feat_ld], feat_ld =
 //     p rounded up to 32, so that the last 32-feature chunk of a row stays inside the row; zero padded),
 //     V = C' or Z.  Rows and columns are the same set and the diagonal is simply what the tile computes;
-//   * KernelAA.transform (launch_poly_cross): Y = the resident rows, X_S = the reference rows, ld = p_pad.
+//   * KernelAA.transform (kernel_cross): Y = the resident rows, X_S = the reference rows, ld = p_pad.
 // No norms are read.  Padding columns have zero rows of V (a padding column's kappa is coef0^degree, times
 // zero); padding rows are written as zeros.  n^2 (2 p + 2 KP) flop (p rounded up to 4, n to 64).
 // Per block: 64 x 34 doubles of Y and of X_S and 64 x (KP + 16) of V in LDS (58 KB at KP = 32, 74 KB at 64);
@@ -1912,13 +1860,19 @@ __global__ __launch_bounds__(256) void k_poly_kv_mfma(const double *__restrict__
                             out);
 }
 
-// out_tall = kappa(Y, X_S) V: rows [0, m) of Y (m_pad a multiple of 64), s_pad / 64 column tiles split over
-// grid.y as in launch_implicit_kv, the splits summed in a fixed order
-static int launch_poly_product(Ctx *c, const double *Y, const double *XS, const double *V, long ld, long p, long m,
-                               long m_pad, long s_pad, const PolyKernel &poly, double *out_tall)
+// out_tall = kappa(Y, X_S) V for the kernel `spec`, the one launcher of the three product kernels: rows [0, m) of
+// Y ([m_pad][ld], m_pad / 64 row tiles = grid.x) against s_pad / 64 column tiles of X_S ([s_pad][ld]) and V
+// ([s_pad][KP]); ny / ns: the squared row norms of Y / X_S (RBF; POLY reads none); p: the features of a row.  The
+// column tiles are split over grid.y so that about 1024 blocks run (~4 per CU); with more than one split the
+// kernel writes [nsplit][m_pad][KP] partials that k_sum_chunks adds in a fixed order.  RBF with Y == X_S (the
+// fit: rows and columns are the same set, the diagonal is exactly 1) is k_rbf_kv, RBF otherwise
+// k_rbf_cross_mfma, POLY k_poly_kv_mfma for both.
+static int launch_kernel_product(Ctx *c, const KernelSpec &spec, const double *Y, const double *ny, const double *XS,
+                                 const double *ns, const double *V, long ld, long p, long m, long m_pad, long s_pad,
+                                 double *out_tall)
 {
     const long rtiles = m_pad / 64, stiles = s_pad / 64;
-    long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU
+    long nsplit = (1024 + rtiles - 1) / rtiles;
     if (nsplit > stiles) nsplit = stiles;
     if (nsplit < 1) nsplit = 1;
     const long tps = (stiles + nsplit - 1) / nsplit;
@@ -1929,12 +1883,31 @@ static int launch_poly_product(Ctx *c, const double *Y, const double *XS, const 
         dst = c->rlPartial.as<double>();
     }
     const dim3 grid((unsigned)rtiles, (unsigned)nsplit);
-    if (c->KP == 32)
-        hipLaunchKernelGGL(k_poly_kv_mfma<32>, grid, dim3(256), 0, c->stream, Y, XS, V, ld, (int)round_up(p, 4), m,
-                           m_pad, stiles, tps, poly, dst);
-    else
-        hipLaunchKernelGGL(k_poly_kv_mfma<64>, grid, dim3(256), 0, c->stream, Y, XS, V, ld, (int)round_up(p, 4), m,
-                           m_pad, stiles, tps, poly, dst);
+    const bool rbf_fit = spec.kind == IMPLICIT_RBF && Y == XS;
+    const size_t lds_fit = (size_t)(64 * 65 + 64 * c->KP + 2 * 64 * 17) * sizeof(double);   // k_rbf_kv's dynamic LDS
+    static bool attr_rbf[64] = {false};
+    if (rbf_fit && !attr_rbf[c->device & 63]) {
+        AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_kv<32>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_rbf_kv<64>),
+                                         hipFuncAttributeMaxDynamicSharedMemorySize, 96 * 1024));
+        attr_rbf[c->device & 63] = true;
+    }
+    const int pk = (int)round_up(p, 4);                  // the MFMAs of the tile body stop here
+#define PRODUCT(KPV)                                                                                              \
+    do {                                                                                                          \
+        if (rbf_fit)                                                                                              \
+            hipLaunchKernelGGL(k_rbf_kv<KPV>, grid, dim3(256), lds_fit, c->stream, Y, ld, (int)p, ny, spec.gamma, V, m, \
+                               m_pad, tps, dst);                                                                  \
+        else if (spec.kind == IMPLICIT_RBF)                                                                       \
+            hipLaunchKernelGGL(k_rbf_cross_mfma<KPV>, grid, dim3(256), 0, c->stream, Y, ny, XS, ns, V, ld, pk, m, \
+                               m_pad, stiles, tps, spec.gamma, dst);                                              \
+        else                                                                                                      \
+            hipLaunchKernelGGL(k_poly_kv_mfma<KPV>, grid, dim3(256), 0, c->stream, Y, XS, V, ld, pk, m, m_pad,    \
+                               stiles, tps, spec.poly(), dst);                                                    \
+    } while (0)
+    if (c->KP == 32) PRODUCT(32); else PRODUCT(64);
+#undef PRODUCT
     if (nsplit > 1) {
         const long elems = m_pad * c->KP;
         hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
@@ -1944,18 +1917,23 @@ static int launch_poly_product(Ctx *c, const double *Y, const double *XS, const 
     return AA_OK;
 }
 
-static int launch_poly_kv(Ctx *c, const double *V_tall, double *out_tall)
+// the fit: K V on the features (rows = columns = the n samples padded to 128)
+int kernel_kv(Ctx *c, const double *V_tall, double *out_tall)
 {
-    return launch_poly_product(c, c->feat.as<double>(), c->feat.as<double>(), V_tall, c->feat_ld, c->feat_p, c->n,
-                               c->n_pad, c->n_pad, c->poly, out_tall);
+    AA_REQUIRE(c->kernel.kind && c->feat.p, AA_ERR_STATE, "no implicit kernel set");
+    const double *F = c->feat.as<double>(), *nrm = c->featNorm.as<double>();
+    return launch_kernel_product(c, c->kernel, F, nrm, F, nrm, V_tall, c->feat_ld, c->feat_p, c->n, c->n_pad, c->n_pad,
+                                 out_tall);
 }
 
-int launch_poly_cross(Ctx *c)
+// KernelAA.transform: Gr (XW) = kappa(Y, X_S) V, the resident rows against the reference set
+int kernel_cross(Ctx *c)
 {
-    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_POLY && c->dtype == AA_F64,
-               AA_ERR_STATE, "no polynomial reference set");
-    return launch_poly_product(c, c->X.as<double>(), c->crossX.as<double>(), c->crossV.as<double>(), c->p_pad, c->p,
-                               c->n, c->n_pad, c->cross_s_pad, c->cross_poly, c->Gr.as<double>());
+    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->dtype == AA_F64, AA_ERR_STATE, "no %s reference set",
+               c->cross.name());
+    return launch_kernel_product(c, c->cross, c->X.as<double>(), c->rowNorm.as<double>(), c->crossX.as<double>(),
+                                 c->crossNorm.as<double>(), c->crossV.as<double>(), c->p_pad, c->p, c->n, c->n_pad,
+                                 c->cross_s_pad, c->Gr.as<double>());
 }
 
 // tr K = sum_i kappa(x_i, x_i) from the squared row norms: one block, each thread a strided sum, then a tree
@@ -1977,45 +1955,12 @@ __global__ __launch_bounds__(256) void k_poly_trace(const double *__restrict__ n
 
 int launch_poly_trace(Ctx *c, double *trace_out_host)
 {
-    AA_REQUIRE(c->implicit_kernel == IMPLICIT_POLY && c->featNorm.p, AA_ERR_STATE, "no implicit polynomial kernel set");
+    AA_REQUIRE(c->kernel.kind == IMPLICIT_POLY && c->featNorm.p, AA_ERR_STATE, "no implicit polynomial kernel set");
     double *out = c->featNorm.as<double>() + c->n_pad;   // the first slack entry behind the norms (never read as one)
     hipLaunchKernelGGL(k_poly_trace, dim3(1), dim3(256), 0, c->stream, (const double *)c->featNorm.as<double>(), c->n,
-                       c->poly, out);
+                       c->kernel.poly(), out);
     AA_CHECK_HIP(hipGetLastError());
     AA_CHECK_HIP(ctx_memcpy(c, trace_out_host, out, sizeof(double), hipMemcpyDeviceToHost));
-    return AA_OK;
-}
-
-int launch_rbf_cross(Ctx *c)
-{
-    AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_RBF && c->dtype == AA_F64, AA_ERR_STATE,
-               "no RBF reference set");
-    const long rtiles = c->n_pad / 64, stiles = c->cross_s_pad / 64;
-    long nsplit = (1024 + rtiles - 1) / rtiles;          // ~4 blocks per CU, as launch_implicit_kv
-    if (nsplit > stiles) nsplit = stiles;
-    if (nsplit < 1) nsplit = 1;
-    const long tps = (stiles + nsplit - 1) / nsplit;
-    nsplit = (stiles + tps - 1) / tps;
-    double *out_tall = c->Gr.as<double>();
-    double *dst = out_tall;
-    if (nsplit > 1) {
-        AA_CHECK(c->rlPartial.alloc((size_t)nsplit * c->n_pad * c->KP * sizeof(double)));
-        dst = c->rlPartial.as<double>();
-    }
-    const dim3 grid((unsigned)rtiles, (unsigned)nsplit);
-#define CROSS(KPV)                                                                                             \
-    hipLaunchKernelGGL(k_rbf_cross_mfma<KPV>, grid, dim3(256), 0, c->stream, (const double *)c->X.as<double>(),  \
-                       (const double *)c->rowNorm.as<double>(), (const double *)c->crossX.as<double>(),         \
-                       (const double *)c->crossNorm.as<double>(), (const double *)c->crossV.as<double>(),       \
-                       c->p_pad, (int)round_up(c->p, 4), c->n, c->n_pad, stiles, tps, c->cross_gamma, dst)
-    if (c->KP == 32) CROSS(32); else CROSS(64);
-#undef CROSS
-    if (nsplit > 1) {
-        const long elems = c->n_pad * c->KP;
-        hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
-                           (const double *)dst, elems, (int)nsplit, out_tall);
-    }
-    AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
 

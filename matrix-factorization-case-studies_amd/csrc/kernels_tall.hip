@@ -4334,12 +4334,12 @@ int launch_distance_column(Ctx *c, long j_local, int owner_has_row, const double
     (void)owner_has_row;
     (void)xj_host;
     double *dd = c->tmpTall.as<double>();
-    if (c->implicit_kernel == IMPLICIT_POLY) {
+    if (c->kernel.kind == IMPLICIT_POLY) {
         hipLaunchKernelGGL(k_distance_poly, dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
-                           (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->poly, dd);
-    } else if (c->implicit_kernel) {
+                           (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->kernel.poly(), dd);
+    } else if (c->kernel.kind) {
         hipLaunchKernelGGL(k_distance_rbf, dim3((unsigned)((c->n + 3) / 4)), dim3(256), 0, c->stream,
-                           (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->rbf_gamma, dd);
+                           (const double *)c->feat.as<double>(), c->feat_ld, (int)c->feat_p, c->n, j_local, c->kernel.gamma, dd);
     } else if (c->form == AA_FORM_DATA) {
         dim3 grid((unsigned)((c->n + 3) / 4));
         if (c->dtype == AA_F32)
@@ -4736,7 +4736,7 @@ int launch_kernel_sample_residuals(Ctx *c, const double *A_dev, int kind, const 
 #define KSR(KPV)                                                                                                   \
     hipLaunchKernelGGL(k_kernel_sample_residuals<KPV>, dim3((unsigned)nb), dim3(256), 0, c->stream,                \
                        (const double *)c->Zt.as<double>(), (const double *)c->Gr.as<double>(), A_dev, kind, d_dev, \
-                       nrm_dev, c->cross_poly, c->n, nb, r_dev, dout_dev, part)
+                       nrm_dev, c->cross.poly(), c->n, nb, r_dev, dout_dev, part)
     if (c->KP == 32) KSR(32); else KSR(64);
 #undef KSR
     AA_CHECK_HIP(hipGetLastError());

@@ -189,12 +189,12 @@ static int device_cost(Ctx *c, double *cost)
 static int ensure_trace(Ctx *c)
 {
     if (c->have_trace) return AA_OK;
-    if (c->implicit_kernel == IMPLICIT_RBF) {    // every diagonal entry is exp(0) = 1
+    if (c->kernel.kind == IMPLICIT_RBF) {    // every diagonal entry is exp(0) = 1
         c->trace = (double)c->n_global;
         c->have_trace = true;
         return AA_OK;
     }
-    if (c->implicit_kernel == IMPLICIT_POLY) {   // sum_i (gamma |x_i|^2 + coef0)^degree
+    if (c->kernel.kind == IMPLICIT_POLY) {   // sum_i (gamma |x_i|^2 + coef0)^degree
         AA_CHECK(launch_poly_trace(c, &c->trace));
         c->have_trace = true;
         return AA_OK;
@@ -223,8 +223,8 @@ static int refresh_after_dictionary(Ctx *c, bool recompute_products, bool ckct_d
         }
         AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), gpp));
     } else {
-        if (recompute_products && c->implicit_kernel) {
-            AA_CHECK(launch_implicit_kv(c, c->Ct.as<double>(), c->Gr.as<double>()));      // (C K)' = K C'
+        if (recompute_products && c->kernel.kind) {
+            AA_CHECK(kernel_kv(c, c->Ct.as<double>(), c->Gr.as<double>()));      // (C K)' = K C'
         } else if (recompute_products) {
             AA_CHECK(launch_reduce_rows(c, c->Ct.as<double>(), c->wideScratch.as<double>(), nullptr));
             AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gr.as<double>()));
@@ -276,8 +276,8 @@ static int refresh_after_weights(Ctx *c)
     } else {
         if (c->qp_tail_pending) AA_CHECK(launch_qp_tail_fixup(c, c->Zt.as<double>()));   // not used
         AA_CHECK(launch_gram_tall(c, c->Zt.as<double>(), c->Zt.as<double>(), dev_ZtZ(c)));
-        if (c->implicit_kernel) {
-            AA_CHECK(launch_implicit_kv(c, c->Zt.as<double>(), c->H.as<double>()));       // K Z
+        if (c->kernel.kind) {
+            AA_CHECK(kernel_kv(c, c->Zt.as<double>(), c->H.as<double>()));       // K Z
         } else {
             AA_CHECK(launch_transpose_tall_to_wide(c, c->Zt.as<double>(), c->ZtX.as<double>(),
                                                    operandT(c, c->ZtX, c->Qw)));
@@ -394,8 +394,8 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
                 if (mixed) AA_CHECK(slots_restore_P_warm(c));
                 AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), gram));
             } else {
-                if (c->implicit_kernel) {
-                    AA_CHECK(launch_implicit_kv(c, x, c->Gr.as<double>()));
+                if (c->kernel.kind) {
+                    AA_CHECK(kernel_kv(c, x, c->Gr.as<double>()));
                 } else {
                     AA_CHECK(launch_reduce_rows(c, x, c->wideScratch.as<double>(), nullptr));
                     AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gr.as<double>()));
@@ -444,8 +444,8 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
                 SPG_NAME("k_gram_wide<%d>x2;k_scalar_stage", KP);
             }
         } else {
-            if (c->implicit_kernel) {
-                AA_CHECK(launch_implicit_kv(c, c->Dt.as<double>(), c->Gn.as<double>()));  // (D K)' = K D'
+            if (c->kernel.kind) {
+                AA_CHECK(kernel_kv(c, c->Dt.as<double>(), c->Gn.as<double>()));  // (D K)' = K D'
             } else {
                 AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->wideScratch.as<double>(), nullptr, false,
                                             &c->groupFlags));
@@ -696,8 +696,7 @@ struct Install {
     int form = AA_FORM_DATA;
     long n = 0, p = 0, p_pad = 0;              // n_pad is roundup(n, 128) everywhere
     long n_global = 0, row_offset = 0;
-    int implicit = 0;                          // IMPLICIT_*: feat [n_pad + slack][feat_ld] and featNorm instead of X
-    long feat_p = 0, feat_ld = 0;
+    long feat_p = 0, feat_ld = 0;              // feat_ld > 0: feat [n_pad + slack][feat_ld] and featNorm instead of X
     const DevBuf *borrow = nullptr;            // aa_share_data: X aliases this buffer instead of being allocated
 };
 
@@ -718,7 +717,7 @@ static int install_begin(Ctx *c, const Install &in)
     c->have_data = false;
     c->form = in.form;
     c->linear_kernel = false;
-    c->implicit_kernel = in.implicit;
+    c->kernel = KernelSpec{};                  // an implicit kernel's installer names it once its fill has succeeded
     c->cross_s = 0;                            // a reference set belongs to the rows it was set for
     c->n = in.n;
     c->p = in.p;
@@ -741,7 +740,7 @@ static int install_begin(Ctx *c, const Install &in)
         c->X.borrowed = true;
         return AA_OK;
     }
-    if (!in.implicit)
+    if (!in.feat_ld)
         return c->X.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));
     c->feat_p = in.feat_p;
     c->feat_ld = in.feat_ld;
@@ -763,7 +762,7 @@ static int check_owner(const aa_ctx *h, const aa_ctx *owner, const char *who, in
 {
     AA_REQUIRE(h && owner && h != owner, AA_ERR_ARG, "%s: two different contexts needed", who);
     const Ctx *c = &h->c, *o = &owner->c;
-    AA_REQUIRE(kernel_form_too ? o->have_data && !o->implicit_kernel : has_stored_data(o), AA_ERR_STATE,
+    AA_REQUIRE(kernel_form_too ? o->have_data && !o->kernel.kind : has_stored_data(o), AA_ERR_STATE,
                "%s: the owner holds no stored %s", who, kernel_form_too ? "matrix" : "data matrix (data form)");
     AA_REQUIRE(c->world == 1 && !c->force_comm && o->world == 1 && !o->force_comm, code, "%s is single-rank", who);
     static const char *const needed[] = {"same data type needed",
@@ -776,85 +775,64 @@ static int check_owner(const aa_ctx *h, const aa_ctx *owner, const char *who, in
     return AA_OK;
 }
 
-// the features of an implicit kernel: the kernel form of the algorithm (/k conventions, tr K) on a virtual n x n
-// matrix; feat_ld: the leading dimension of the zero-padded feature buffer, chosen by the kernels that read it.
-// `owner` (X == nullptr): the features are the rows of its resident data matrix, converted on the device
-static int set_implicit_features(Ctx *c, const double *X, long n, long p, long ld, long feat_ld, int kind,
-                                 const Ctx *owner = nullptr)
+// The features of the implicit kernel `spec`: the kernel form of the algorithm (/k conventions, tr K) on a
+// virtual n x n matrix.  From the host (X, n, p, ld), or -- `who` names the entry point -- the rows of `owner`'s
+// resident data matrix, converted on the device.  The context is float64 and single rank for both; check_owner
+// says so first for an owner, with its own words.
+static int set_kernel_features(aa_ctx *h, const KernelSpec &spec, const double *X, long n, long p, long ld,
+                               const aa_ctx *owner = nullptr, const char *who = nullptr)
 {
+    if (who) {
+        AA_CHECK(check_owner(h, owner, who, AA_ERR_STATE, DTYPE_INTO_F64));
+        n = owner->c.n;
+        p = owner->c.p;
+        AA_REQUIRE(p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", n, p);
+    } else {
+        AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
+        AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
+    }
+    AA_CHECK(kernel_spec_check(spec));
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit %s kernel is single-rank", spec.name());
+    AA_REQUIRE(c->dtype == AA_F64, AA_ERR_STATE, "the implicit %s kernel needs a float64 context", spec.name());
     AA_CHECK_HIP(hipSetDevice(c->device));
     Install in = install_rows(n, n, round_up(n, 128));
     in.form = AA_FORM_KERNEL;
-    in.implicit = kind;
     in.feat_p = p;
-    in.feat_ld = feat_ld;
+    in.feat_ld = spec.feat_ld(p);
     AA_CHECK(install_begin(c, in));
-    if (owner)
-        AA_CHECK(launch_features_from_data(c, owner->X.p, owner->dtype, owner->p_pad, n, p, c->feat.as<double>(),
+    if (who)
+        AA_CHECK(launch_features_from_data(c, owner->c.X.p, owner->c.dtype, owner->c.p_pad, n, p, c->feat.as<double>(),
                                            c->feat_ld));
     else
         AA_CHECK_HIP(ctx_memcpy2d(c, c->feat.p, (size_t)c->feat_ld * sizeof(double), X, (size_t)ld * sizeof(double),
                                   (size_t)p * sizeof(double), (size_t)n, hipMemcpyHostToDevice));
-    AA_CHECK(launch_rbf_norms(c));
+    AA_CHECK(launch_row_norms(c, c->feat.as<double>(), c->feat_ld, c->feat_p, c->n_pad, c->featNorm.as<double>()));
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // the owner has been read: it may go
+    c->kernel = spec;
     install_commit(c);
     return AA_OK;
 }
 
 int aa_set_rbf_features(aa_ctx *h, const double *X, long n, long p, long ld, double gamma)
 {
-    AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
-    AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
-    c->rbf_gamma = gamma;
-    return set_implicit_features(c, X, n, p, ld, round_up(p, 2), IMPLICIT_RBF);
-}
-
-// gamma > 0, coef0 >= 0 (K positive semi-definite), degree >= 1, all finite (a NaN fails every comparison)
-static bool poly_params_ok(double gamma, double coef0, int degree)
-{
-    return gamma > 0.0 && gamma < 1e300 && coef0 >= 0.0 && coef0 < 1e300 && degree >= 1;
+    return set_kernel_features(h, KernelSpec{IMPLICIT_RBF, gamma}, X, n, p, ld);
 }
 
 int aa_set_poly_features(aa_ctx *h, const double *X, long n, long p, long ld, double gamma, double coef0, int degree)
 {
-    AA_REQUIRE(h && X, AA_ERR_ARG, "null argument");
-    AA_REQUIRE(n >= 1 && p >= 1 && ld >= p && p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld ld=%ld", n, p, ld);
-    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
-               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
-               degree);
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit polynomial kernel is single-rank");
-    AA_REQUIRE(c->dtype == AA_F64, AA_ERR_STATE, "the implicit polynomial kernel needs a float64 context");
-    c->poly = PolyKernel{gamma, coef0, degree};
-    // k_poly_kv_mfma reads rows in chunks of 32 features
-    return set_implicit_features(c, X, n, p, ld, round_up(p, 32), IMPLICIT_POLY);
+    return set_kernel_features(h, KernelSpec{IMPLICIT_POLY, gamma, coef0, degree}, X, n, p, ld);
 }
 
 int aa_set_rbf_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma)
 {
-    AA_CHECK(check_owner(h, owner, "aa_set_rbf_features_resident", AA_ERR_STATE, DTYPE_INTO_F64));
-    Ctx *c = &h->c;
-    const Ctx *o = &owner->c;
-    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
-    c->rbf_gamma = gamma;
-    return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 2), IMPLICIT_RBF, o);
+    return set_kernel_features(h, KernelSpec{IMPLICIT_RBF, gamma}, nullptr, 0, 0, 0, owner, "aa_set_rbf_features_resident");
 }
 
 int aa_set_poly_features_resident(aa_ctx *h, const aa_ctx *owner, double gamma, double coef0, int degree)
 {
-    AA_CHECK(check_owner(h, owner, "aa_set_poly_features_resident", AA_ERR_STATE, DTYPE_INTO_F64));
-    Ctx *c = &h->c;
-    const Ctx *o = &owner->c;
-    AA_REQUIRE(o->p < (1L << 30), AA_ERR_ARG, "bad shape n=%ld p=%ld", o->n, o->p);
-    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
-               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
-               degree);
-    c->poly = PolyKernel{gamma, coef0, degree};
-    return set_implicit_features(c, nullptr, o->n, o->p, 0, round_up(o->p, 32), IMPLICIT_POLY, o);
+    return set_kernel_features(h, KernelSpec{IMPLICIT_POLY, gamma, coef0, degree}, nullptr, 0, 0, 0, owner,
+                               "aa_set_poly_features_resident");
 }
 
 int aa_comm_get_unique_id(void *id128) { return comm_unique_id(id128); }
@@ -1224,7 +1202,7 @@ int aa_get_data(aa_ctx *h, double *out, long ld)
     AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     // any stored matrix, the kernel form's too (not has_stored_data)
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_get_data: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(!c->kernel.kind, AA_ERR_STATE, "aa_get_data: no stored matrix behind an implicit kernel");
     AA_REQUIRE(c->have_data, AA_ERR_STATE, "no data");
     AA_REQUIRE(ld >= c->p, AA_ERR_ARG, "ld < p");
     AA_CHECK_HIP(hipSetDevice(c->device));
@@ -1651,7 +1629,7 @@ int aa_furthest_sum(aa_ctx *h, int k, long start_index, const int *exclude, int 
     AA_REQUIRE(c->have_data, AA_ERR_STATE, "no data");
     AA_REQUIRE(c->world <= 1 && !c->force_comm, AA_ERR_STATE,
                "aa_furthest_sum is single-rank (row-sharded runs pull distance columns: aa_distance_column)");
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_furthest_sum: implicit kernels pull distance columns (aa_distance_column)");
+    AA_REQUIRE(!c->kernel.kind, AA_ERR_STATE, "aa_furthest_sum: implicit kernels pull distance columns (aa_distance_column)");
     AA_REQUIRE(k >= 1 && k <= AA_MAX_K, AA_ERR_ARG, "k = %d out of range", k);
     AA_REQUIRE(start_index >= 0 && start_index < c->n, AA_ERR_ARG, "start index %ld out of range", start_index);
     AA_REQUIRE(n_exclude >= 0 && (n_exclude == 0 || exclude), AA_ERR_ARG, "bad exclude list");
@@ -2365,9 +2343,21 @@ int aa_gpnh_residual_scores(aa_ctx *h, double *col_sse, double *row_sse, double 
 }
 
 // ------------------------------------------------------------------ KernelAA.transform
-// the reference rows X_S and V = D' on them for the cross product against the resident rows (both kinds)
-static int set_cross_reference(Ctx *c, int k, const double *XS, long s, long p, long ld, const double *V, long ldv)
+// the reference rows X_S and V = D' on them for the cross product of kernel `spec` against the resident rows, and
+// the squared norms where the kind's product reads them.  The context names the reference set (cross, cross_s)
+// once everything of it is in place; until then it has none
+static int set_kernel_reference(aa_ctx *h, const KernelSpec &spec, int k, const double *XS, long s, long p, long ld,
+                                const double *V, long ldv)
 {
+    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit %s kernel is single-rank", spec.name());
+    AA_REQUIRE(has_stored_data(c) && c->dtype == AA_F64, AA_ERR_STATE,
+               "aa_set_%s_reference needs the new samples as a float64 data matrix (aa_set_data)", spec.stem());
+    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
+               s, p, c->p, ld, ldv);
+    AA_CHECK(kernel_spec_check(spec));
+    c->cross_s = 0;
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
     const long s_pad = round_up(s, 64);
@@ -2380,80 +2370,49 @@ static int set_cross_reference(Ctx *c, int k, const double *XS, long s, long p, 
         for (int i = 0; i < k; ++i) v[(size_t)j * c->KP + i] = V[j * ldv + i];
     AA_CHECK(c->crossV.alloc(v.size() * sizeof(double)));
     AA_CHECK_HIP(ctx_memcpy(c, c->crossV.p, v.data(), v.size() * sizeof(double), hipMemcpyHostToDevice));
+    c->gpnh_valid = false;
+    if (spec.cross_reads_norms()) {
+        AA_CHECK(c->crossNorm.alloc((size_t)s_pad * sizeof(double)));
+        AA_CHECK(launch_row_norms(c, c->crossX.as<double>(), c->p_pad, p, s_pad, c->crossNorm.as<double>()));
+        AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
+        AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, p, c->n_pad, c->rowNorm.as<double>()));
+    }
+    c->cross = spec;
     c->cross_s = s;
     c->cross_s_pad = s_pad;
     c->cross_k = k;
-    c->gpnh_valid = false;
+    return AA_OK;
+}
+
+// XW = kappa(Y, X_S) V into Gr (and to the host), for the entry point of kernel `kind`
+static int kernel_cross_product(aa_ctx *h, int kind, double *XW)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
+    Ctx *c = &h->c;
+    AA_REQUIRE(has_stored_data(c) && c->cross_s > 0 && c->cross_k == c->k && c->cross.kind == kind, AA_ERR_STATE,
+               "aa_set_%s_reference first", KernelSpec{kind}.stem());
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(kernel_cross(c));
+    c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
+    if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
     return AA_OK;
 }
 
 int aa_set_rbf_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
                          double gamma)
 {
-    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit RBF kernel is single-rank");
-    AA_REQUIRE(has_stored_data(c) && c->dtype == AA_F64, AA_ERR_STATE,
-               "aa_set_rbf_reference needs the new samples as a float64 data matrix (aa_set_data)");
-    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
-               s, p, c->p, ld, ldv);
-    AA_REQUIRE(gamma > 0.0 && gamma < 1e300, AA_ERR_ARG, "gamma must be positive");
-    c->cross_s = 0;
-    AA_CHECK(set_cross_reference(c, k, XS, s, p, ld, V, ldv));
-    AA_CHECK(c->crossNorm.alloc((size_t)c->cross_s_pad * sizeof(double)));
-    AA_CHECK(launch_row_norms(c, c->crossX.as<double>(), c->p_pad, p, c->cross_s_pad, c->crossNorm.as<double>()));
-    AA_CHECK(c->rowNorm.alloc((size_t)c->n_pad * sizeof(double)));
-    AA_CHECK(launch_row_norms(c, c->X.as<double>(), c->p_pad, p, c->n_pad, c->rowNorm.as<double>()));
-    c->cross_kind = IMPLICIT_RBF;
-    c->cross_gamma = gamma;
-    return AA_OK;
-}
-
-int aa_rbf_cross(aa_ctx *h, double *XW)
-{
-    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
-    Ctx *c = &h->c;
-    AA_REQUIRE(has_stored_data(c) && c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_RBF, AA_ERR_STATE,
-               "aa_set_rbf_reference first");
-    AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_CHECK(launch_rbf_cross(c));
-    c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
-    if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
-    return AA_OK;
+    return set_kernel_reference(h, KernelSpec{IMPLICIT_RBF, gamma}, k, XS, s, p, ld, V, ldv);
 }
 
 int aa_set_poly_reference(aa_ctx *h, int k, const double *XS, long s, long p, long ld, const double *V, long ldv,
                           double gamma, double coef0, int degree)
 {
-    AA_REQUIRE(h && XS && V, AA_ERR_ARG, "null argument");
-    Ctx *c = &h->c;
-    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_STATE, "the implicit polynomial kernel is single-rank");
-    AA_REQUIRE(has_stored_data(c) && c->dtype == AA_F64, AA_ERR_STATE,
-               "aa_set_poly_reference needs the new samples as a float64 data matrix (aa_set_data)");
-    AA_REQUIRE(s >= 1 && p == c->p && ld >= p && ldv >= k, AA_ERR_ARG, "bad shape s=%ld p=%ld (data p=%ld) ld=%ld ldv=%ld",
-               s, p, c->p, ld, ldv);
-    AA_REQUIRE(poly_params_ok(gamma, coef0, degree), AA_ERR_ARG,
-               "the polynomial kernel needs gamma > 0, coef0 >= 0 and degree >= 1 (finite); got %g, %g, %d", gamma, coef0,
-               degree);
-    c->cross_s = 0;
-    AA_CHECK(set_cross_reference(c, k, XS, s, p, ld, V, ldv));
-    c->cross_kind = IMPLICIT_POLY;
-    c->cross_poly = PolyKernel{gamma, coef0, degree};
-    return AA_OK;
+    return set_kernel_reference(h, KernelSpec{IMPLICIT_POLY, gamma, coef0, degree}, k, XS, s, p, ld, V, ldv);
 }
 
-int aa_poly_cross(aa_ctx *h, double *XW)
-{
-    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
-    Ctx *c = &h->c;
-    AA_REQUIRE(has_stored_data(c) && c->cross_s > 0 && c->cross_k == c->k && c->cross_kind == IMPLICIT_POLY, AA_ERR_STATE,
-               "aa_set_poly_reference first");
-    AA_CHECK_HIP(hipSetDevice(c->device));
-    AA_CHECK(launch_poly_cross(c));
-    c->gpnh_valid = true;                        // the QP's linear term, as after aa_gpnh_set_factors
-    if (XW) AA_CHECK(download_tall(c, c->Gr, XW, c->k, 1, c->n, c->k));
-    return AA_OK;
-}
+int aa_rbf_cross(aa_ctx *h, double *XW) { return kernel_cross_product(h, IMPLICIT_RBF, XW); }
+
+int aa_poly_cross(aa_ctx *h, double *XW) { return kernel_cross_product(h, IMPLICIT_POLY, XW); }
 
 int aa_kernel_transform_cost(aa_ctx *h, const double *A, const double *diag, double *cost)
 {
@@ -2490,7 +2449,7 @@ int aa_kernel_sample_residuals(aa_ctx *h, const double *A, int diag_kind, const 
     const bool from_norms = diag_kind == AA_DIAG_POLY || diag_kind == AA_DIAG_LINEAR;
     AA_REQUIRE(!from_norms || (has_stored_data(c) && c->dtype == AA_F64), AA_ERR_STATE,
                "this diagonal is computed from a stored float64 data matrix");
-    AA_REQUIRE(diag_kind != AA_DIAG_POLY || (c->cross_s > 0 && c->cross_kind == IMPLICIT_POLY), AA_ERR_STATE,
+    AA_REQUIRE(diag_kind != AA_DIAG_POLY || (c->cross_s > 0 && c->cross.kind == IMPLICIT_POLY), AA_ERR_STATE,
                "aa_set_poly_reference first");
     AA_CHECK_HIP(hipSetDevice(c->device));
     const size_t GS = (size_t)c->KP * c->KP;
@@ -2645,7 +2604,7 @@ static int pass_reduce_rows(aa_ctx *h, int k, const double *A, double *out, long
     AA_REQUIRE(h && A && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     // the stored kernel form is served too (not has_stored_data); ensure_problem asks for the data
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_pass_reduce_rows: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(!c->kernel.kind, AA_ERR_STATE, "aa_pass_reduce_rows: no stored matrix behind an implicit kernel");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
     AA_REQUIRE(ldo >= (c->form == AA_FORM_KERNEL ? c->n : c->p), AA_ERR_ARG, "ldo too small");
@@ -2689,7 +2648,7 @@ int aa_pass_row_local(aa_ctx *h, int k, const double *B, long ldb, double *out)
     AA_REQUIRE(h && B && out, AA_ERR_ARG, "null argument");
     Ctx *c = &h->c;
     // as aa_pass_reduce_rows: either stored form
-    AA_REQUIRE(!c->implicit_kernel, AA_ERR_STATE, "aa_pass_row_local: no stored matrix behind an implicit kernel");
+    AA_REQUIRE(!c->kernel.kind, AA_ERR_STATE, "aa_pass_row_local: no stored matrix behind an implicit kernel");
     AA_CHECK_HIP(hipSetDevice(c->device));
     AA_CHECK(ensure_problem(c, k));
     AA_REQUIRE(ldb >= c->p, AA_ERR_ARG, "ldb < p");
@@ -2768,7 +2727,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     AA_REQUIRE(h && ms_avg && reps >= 1, AA_ERR_ARG, "bad arguments");
     Ctx *c = &h->c;
     if (which == 8)
-        AA_REQUIRE(c->implicit_kernel && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit kernel with state");
+        AA_REQUIRE(c->kernel.kind && c->have_state, AA_ERR_STATE, "aa_time_kernel 8: an implicit kernel with state");
     else if (which == 9)
         AA_REQUIRE(c->cross_s > 0 && c->cross_k == c->k, AA_ERR_STATE,
                    "aa_time_kernel 9: aa_set_rbf_reference or aa_set_poly_reference first");
@@ -2776,7 +2735,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         AA_REQUIRE(has_stored_data(c) && c->have_state && c->gpnh_valid && c->world == 1 && !c->force_comm, AA_ERR_STATE,
                    "aa_time_kernel 10 / 11: aa_gpnh_set_factors (dictionary and weights) first, single rank");
     else if (which == 12)                        // either stored form (not has_stored_data), like aa_pass_reduce_rows
-        AA_REQUIRE(c->have_data && !c->implicit_kernel && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
+        AA_REQUIRE(c->have_data && !c->kernel.kind && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
     else if (which >= 13 && which <= 17)
         AA_REQUIRE(has_stored_data(c) && c->world == 1 && !c->force_comm, AA_ERR_STATE,
@@ -2838,9 +2797,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
             else if (which >= 2 && which <= 7)
                 rc = launch_stream_probe(c, which - 2);
             else if (which == 8)
-                rc = launch_implicit_kv(c, c->Zt.as<double>(), c->H.as<double>());
+                rc = kernel_kv(c, c->Zt.as<double>(), c->H.as<double>());
             else if (which == 9)
-                rc = c->cross_kind == IMPLICIT_POLY ? launch_poly_cross(c) : launch_rbf_cross(c);
+                rc = kernel_cross(c);
             else if (which == 10)
                 rc = launch_residual_scores(c, nullptr, nullptr, nullptr, false);
             else if (which == 11)

@@ -69,7 +69,7 @@ def round_up(a, b):
 
 # ---------------------------------------------------------------- the launchers' split arithmetic
 def split_arithmetic(row_tiles, col_tiles):
-    """(nsplit, tiles_per_split) of launch_implicit_kv and launch_rbf_cross: about 1024 blocks in all."""
+    """(nsplit, tiles_per_split) of launch_kernel_product (the fit and the cross product): about 1024 blocks in all."""
     nsplit = (1024 + row_tiles - 1) // row_tiles
     nsplit = max(1, min(nsplit, col_tiles))
     tps = (col_tiles + nsplit - 1) // nsplit
@@ -77,13 +77,13 @@ def split_arithmetic(row_tiles, col_tiles):
 
 
 def kv_splits(n):
-    """launch_implicit_kv: rows and columns are the n samples padded to 128 (n_pad), in tiles of 64."""
+    """kernel_kv: rows and columns are the n samples padded to 128 (n_pad), in tiles of 64."""
     tiles = round_up(n, 128) // 64
     return split_arithmetic(tiles, tiles)
 
 
 def cross_splits(m, s):
-    """launch_rbf_cross: m resident rows padded to 128, s reference rows padded to 64."""
+    """kernel_cross: m resident rows padded to 128, s reference rows padded to 64."""
     return split_arithmetic(round_up(m, 128) // 64, round_up(s, 64) // 64)
 
 

@@ -62,7 +62,7 @@ def _product_bound(p, degree, n, magnitude):
 
 
 # n = 130: one partial 64-row tile and padding columns; 4200 with the launcher's split arithmetic
-# (launch_implicit_kv's): 66 row tiles, 14 splits of 5 column tiles, the last one a single tile; p = 7 (no
+# (launch_kernel_product's): 66 row tiles, 14 splits of 5 column tiles, the last one a single tile; p = 7 (no
 # multiple of 4), 33 (crosses a 32-feature chunk), 64 (exact chunks); k = 3 (KP = 32), 40 (KP = 64)
 @pytest.mark.parametrize("n,p,k,degree", [(130, 7, 3, 2), (130, 33, 40, 3), (130, 64, 3, 3), (900, 64, 40, 2),
                                           (900, 33, 3, 3), (4200, 7, 3, 3), (4200, 33, 40, 2)])

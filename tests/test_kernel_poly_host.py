@@ -37,8 +37,9 @@ class _FakeContext(object):
     def __exit__(self, *exc):
         return False
 
-    def set_poly_features(self, X, gamma, coef0, degree):
-        type(self).calls.append((X.shape, gamma, coef0, degree))
+    def set_kernel_features(self, spec, X):
+        assert spec["form"] == "poly"
+        type(self).calls.append((X.shape, spec["gamma"], spec["coef0"], spec["degree"]))
 
     def grams(self):
         k = 2

@@ -126,7 +126,7 @@ def test_planted_faults_are_caught(fault):
 
 
 def test_split_arithmetic():
-    """launch_implicit_kv and launch_rbf_cross, restated: the splits the cases are named for.  k_rbf_kv's grid
+    """kernel_kv and kernel_cross (launch_kernel_product), restated: the splits the cases are named for.  k_rbf_kv's grid
     covers n_pad = n rounded up to 128, so n = 64 has two splits (the second leaves its loop at once) and n = 130
     four, three of one data tile each and an empty one."""
     def kv(n):
