@@ -491,8 +491,12 @@ int aa_get_archetypes(aa_ctx *ctx, double *CX, long ld);
 
 /* FurthestSum support (furthest_sum.py:23-127 needs column j of the n x n
  * dissimilarity matrix, archetypal_analysis.py:95-100): d[i] =
- * sqrt(K_ii - 2 K_ij + K_jj) for this rank's rows i, K = XX' never formed
- * (form DATA) or the stored K (form KERNEL).  j is a GLOBAL row index. */
+ * sqrt(max(K_ii - 2 K_ij + K_jj, 0)) for this rank's rows i, K = XX' never formed
+ * (form DATA) or the stored K (form KERNEL).  j is a GLOBAL row index.  Every form clamps
+ * at 0 (the reference does not: where rounding puts K_ii - 2 K_ij + K_jj below zero -- two
+ * nearly equal samples of a kernel matrix stored in float32 -- it has NaN and its selection
+ * fails; here the entry is 0); where the reference's value is finite the bits are the same.
+ * d[j] is exactly 0. */
 int aa_distance_column(aa_ctx *ctx, long j, double *d);
 /* The whole FurthestSum selection (furthest_sum.py:23-127) on the device, single rank: running
  * distance sums and the candidate flags stay in device memory, every pick is one distance-column
@@ -500,10 +504,24 @@ int aa_distance_column(aa_ctx *ctx, long j, double *d);
  * round trip per pick.  selected[k] out.  *tie != 0: at some pick the largest running sum was
  * shared by several candidates; the reference then takes the one its stable sorts left last, a rule
  * that depends on the history of the list -- the caller repeats the selection through
- * aa_distance_column and the host's list logic (convex_dim_red/furthest_sum.py).  Distances in the
+ * aa_distance_column and the host's list logic (convex_dim_red/furthest_sum.py).  The flag is also raised
+ * when a live running sum is NaN (inf - inf behind a non-finite entry of the matrix: no comparison sees
+ * it), and the host's logic refuses that selection by name.  Distances in the
  * arithmetic of aa_distance_column, sums updated in the same order: the same picks. */
 int aa_furthest_sum(aa_ctx *ctx, int k, long start_index, const int *exclude, int n_exclude, int extra_steps,
                     int *selected, int *tie);
+/* What the latest aa_furthest_sum of this context left in its device scratch, copied out: the running sums
+ * (n doubles; the entry of a candidate that is not alive keeps the sum it was picked with, that of a point
+ * that never was a candidate is unspecified), the alive flags (n bytes, 1: a candidate), the last distance
+ * column the chain computed (n doubles: that of the last point picked), cur (the index that column belongs
+ * to), tie and selected[0 .. k).  *n and *k: the sizes of that selection; every pointer may be NULL, so a
+ * first call can ask for the sizes alone.  Waits for the context's stream, launches nothing and steers
+ * nothing.  A test of the chain has to see every pick, not only the last (tests/test_gpu_furthest_sum.py
+ * calls aa_furthest_sum with extra_steps = 0, 1, 2, ... and reads the state after each).  The reference has
+ * no counterpart (its list is a local of furthest_sum).  AA_ERR_STATE when no selection has run since the
+ * last install. */
+int aa_get_furthest_sum_state(aa_ctx *ctx, long *n, int *k, double *sums, unsigned char *alive, double *column,
+                              int *cur, int *tie, int *selected);
 
 /* GPNH restarts side by side (the drivers' n_init loop, bin/run_jra55_pca_gpnh.py:112-138):
  * R independent fits of k components each share one set of device arrays (R k <= 64) and every launch

@@ -151,6 +151,9 @@ _SIGNATURES = {
     "aa_distance_column": (ctypes.c_int, [_vp, ctypes.c_long, _dp]),
     "aa_furthest_sum": (ctypes.c_int, [_vp, ctypes.c_int, ctypes.c_long, ctypes.POINTER(ctypes.c_int), ctypes.c_int,
                                        ctypes.c_int, ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
+    "aa_get_furthest_sum_state": (ctypes.c_int, [_vp, ctypes.POINTER(ctypes.c_long), ctypes.POINTER(ctypes.c_int), _dp,
+                                                 ctypes.POINTER(ctypes.c_ubyte), _dp, ctypes.POINTER(ctypes.c_int),
+                                                 ctypes.POINTER(ctypes.c_int), ctypes.POINTER(ctypes.c_int)]),
     "aa_gpnh_set_factors": (ctypes.c_int, [_vp, ctypes.c_int, _dp, ctypes.c_long, _dp]),
     "aa_gpnh_get_weights": (ctypes.c_int, [_vp, _dp]),
     "aa_gpnh_reduce": (ctypes.c_int, [_vp, _dp, ctypes.c_long, _dp, _dp]),
@@ -815,6 +818,24 @@ class Context(object):
                                         int(max(extra_steps, 0)),
                                         sel.ctypes.data_as(ctypes.POINTER(ctypes.c_int)), ctypes.byref(tie)))
         return None if tie.value else sel.astype(np.int64)
+
+    def furthest_sum_state(self):
+        """What the latest ``furthest_sum`` left on the device (aa_get_furthest_sum_state): a dict with ``sums``
+        (n), ``alive`` (n, bool), ``column`` (n: the last distance column of the chain), ``cur``, ``tie`` and
+        ``selected`` (k).  Raises when no selection has run since the data was installed."""
+        n, k = ctypes.c_long(0), ctypes.c_int(0)
+        _check(self.lib.aa_get_furthest_sum_state(self.h, ctypes.byref(n), ctypes.byref(k), None, None, None,
+                                                  None, None, None))
+        sums, column = np.empty(n.value), np.empty(n.value)
+        alive = np.empty(n.value, dtype=np.uint8)
+        selected = np.zeros(k.value, dtype=np.int32)
+        cur, tie = ctypes.c_int(0), ctypes.c_int(0)
+        _check(self.lib.aa_get_furthest_sum_state(self.h, None, None, _ptr(sums),
+                                                  alive.ctypes.data_as(ctypes.POINTER(ctypes.c_ubyte)), _ptr(column),
+                                                  ctypes.byref(cur), ctypes.byref(tie),
+                                                  selected.ctypes.data_as(ctypes.POINTER(ctypes.c_int))))
+        return dict(sums=sums, alive=alive.astype(bool), column=column, cur=cur.value, tie=tie.value,
+                    selected=selected.astype(np.int64))
 
     # -- GPNH
     def gpnh_set_factors(self, k, W=None, Z=None):

@@ -64,6 +64,11 @@ class _Pool(object):
 
     def take_furthest(self):
         cur = np.where(self.alive, self.sums, -np.inf)
+        if np.isnan(cur).any():
+            # inf - inf behind a non-finite entry of the kernel or data matrix: a sort with NaN keys has no
+            # defined order (the reference returns whatever its list.sort leaves)
+            raise ValueError("Non-finite dissimilarity: the running distance sum of candidate %d is NaN"
+                             % int(np.flatnonzero(np.isnan(cur))[0]))
         tied = np.flatnonzero(cur == cur.max())
         depth = len(self.history)
         while tied.size > 1 and depth > 0:                        # order the previous sorts left
@@ -80,7 +85,8 @@ class _Pool(object):
     def shift(self, column, sign):
         column = np.asarray(column)
         self._grow(column.shape[0])
-        self.sums[self.alive] += sign * column[:self.n][self.alive]
+        with np.errstate(invalid="ignore"):                       # inf - inf: take_furthest refuses the NaN by name
+            self.sums[self.alive] += sign * column[:self.n][self.alive]
 
     def push(self, member, value):
         member = int(member)

@@ -355,6 +355,10 @@ struct Ctx {
     KernelSpec cross;                          // the reference set's kernel, valid while cross_s > 0
     DevBuf scoreScratch;                       // aa_gpnh_residual_scores: [slab][p_pad] | [split][n_pad] partials, the sums, the total
     DevBuf fsScratch;                          // FurthestSum on the device: running sums, one distance column, state, alive flags
+    // the layout of fsScratch as the latest selection on the current rows left it (aa_get_furthest_sum_state);
+    // fs_k == 0: no selection since the last install
+    int fs_k = 0;
+    size_t fs_off_col = 0, fs_off_st = 0, fs_off_alive = 0;
     bool qp_iters_valid = false;               // qpIters belongs to the current rows / state
     bool linear_kernel = false;                // data form, KernelAA conventions: K = X X' implicit (aa_set_linear_kernel)
     DevBuf qpStats;                            // 2 long long
@@ -504,6 +508,9 @@ int launch_kernel_sample_residuals(Ctx *c, const double *A_dev, int kind, const 
                                    double *r_dev, double *dout_dev, double *part);
 int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n_ex, int extra_steps,
                         int *selected_host, int *tie_host);
+// copies out of fsScratch (any pointer may be null); launches nothing
+int fetch_furthest_sum_state(Ctx *c, double *sums, unsigned char *alive, double *column, int *cur, int *tie,
+                             int *selected);
 int launch_row_broadcast(Ctx *c, long j_local, bool own);
 int launch_proj_side(Ctx *c, const double *x, const double *g, double a_const, int a_slot, int mode,
                      const aa_spg_params *sp, int stage_after);   // launch_proj on the side stream / scratch set

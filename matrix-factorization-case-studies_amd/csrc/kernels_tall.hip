@@ -2089,6 +2089,8 @@ __global__ __launch_bounds__(256) void k_distance_poly(const double *__restrict_
     }
 }
 
+// the stored kernel matrix: d[i] = sqrt(max(K_ii - 2 K_ij + K_jj, 0)), clamped like the three forms above -- a
+// matrix stored in float32 puts the squared distance of two nearly equal samples a rounding below zero
 template <typename T>
 __global__ __launch_bounds__(256) void k_distance_kernel(const T *__restrict__ K, long ldx, long n,
                                                          long j, double *__restrict__ d)
@@ -2097,7 +2099,7 @@ __global__ __launch_bounds__(256) void k_distance_kernel(const T *__restrict__ K
     if (r >= n) return;
     const double kd = (double)K[r * ldx + r], kj = (double)K[r * ldx + j],
                  jj = (double)K[j * ldx + j];
-    d[r] = sqrt(kd - 2.0 * kj + jj);
+    d[r] = sqrt(fmax(kd - 2.0 * kj + jj, 0.0));
 }
 
 // sum_r || x_r - sum_i z[r][i] * alpha[i] * W[i][:] ||^2, one wave per row.
@@ -4407,7 +4409,7 @@ __global__ __launch_bounds__(256) void k_fs_distance(const T *__restrict__ X, lo
         const long r = (long)blockIdx.x * 256 + threadIdx.x;
         if (r >= n) return;
         const double kd = (double)X[r * ldx + r], kj = (double)X[r * ldx + j], jj = (double)X[j * ldx + j];
-        d[r] = sqrt(kd - 2.0 * kj + jj);
+        d[r] = sqrt(fmax(kd - 2.0 * kj + jj, 0.0));
     }
 }
 
@@ -4474,7 +4476,7 @@ __global__ __launch_bounds__(1024) void k_fs_step(double *__restrict__ sums, uns
                 } else {
                     const double kd = (double)X[(long)leaving * ldx + leaving], kj = (double)X[(long)leaving * ldx + other],
                                  jj = (double)X[other * ldx + other];
-                    dv = sqrt(kd - 2.0 * kj + jj);
+                    dv = sqrt(fmax(kd - 2.0 * kj + jj, 0.0));
                 }
             }
             if (lane == 0) dback[q] = dv;
@@ -4492,15 +4494,16 @@ __global__ __launch_bounds__(1024) void k_fs_step(double *__restrict__ sums, uns
     if (pick) {
         double best = -INFINITY;
         long arg = -1;
-        int cnt = 0;
+        int cnt = 0, nan = 0;
         for (long i = t; i < n; i += 1024)
             if (alive[i]) {
                 const double v = sums[i];
                 if (v > best) { best = v; arg = i; cnt = 1; }
                 else if (v == best) { cnt += 1; }
+                else if (v != v) { nan = 1; }             // inf - inf behind a non-finite entry: no comparison sees it
             }
         sv[t] = best; si[t] = arg; sc[t] = cnt;
-        __syncthreads();
+        const int any_nan = __syncthreads_or(nan);
         for (int o = 512; o > 0; o >>= 1) {
             if (t < o) {
                 const double a = sv[t], b = sv[t + o];
@@ -4510,7 +4513,8 @@ __global__ __launch_bounds__(1024) void k_fs_step(double *__restrict__ sums, uns
             __syncthreads();
         }
         if (t == 0) {
-            if (sc[0] != 1 || si[0] < 0) st->tie = 1;     // shared maximum (or nothing left): the host decides
+            // shared maximum, nothing left, or a live sum that is NaN: the host decides (or refuses)
+            if (sc[0] != 1 || si[0] < 0 || any_nan) st->tie = 1;
             const long a = si[0] < 0 ? 0 : si[0];
             st->selected[pick_slot] = (int)a;
             alive[a] = 0;
@@ -4530,6 +4534,7 @@ int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n
     const size_t off_st = 2 * off_col;
     const size_t off_ex = off_st + round_up((long)sizeof(FsState), 256);
     const size_t off_alive = off_ex + round_up((long)(n_ex > 0 ? n_ex : 1) * sizeof(int), 256);
+    c->fs_k = 0;
     AA_CHECK(c->fsScratch.alloc(off_alive + (size_t)n));
     unsigned char *base = reinterpret_cast<unsigned char *>(c->fsScratch.p);
     double *sums = reinterpret_cast<double *>(base), *col = reinterpret_cast<double *>(base + off_col);
@@ -4583,6 +4588,29 @@ int launch_furthest_sum(Ctx *c, int k, int start, const int *exclude_host, int n
     AA_CHECK_HIP(hipStreamSynchronize(c->stream));
     for (int q = 0; q < k; ++q) selected_host[q] = hst.selected[q];
     *tie_host = hst.tie;
+    c->fs_k = k;                                          // what aa_get_furthest_sum_state needs
+    c->fs_off_col = off_col;
+    c->fs_off_st = off_st;
+    c->fs_off_alive = off_alive;
+    return AA_OK;
+}
+
+int fetch_furthest_sum_state(Ctx *c, double *sums, unsigned char *alive, double *column, int *cur, int *tie,
+                             int *selected)
+{
+    const size_t n = (size_t)c->n;
+    const unsigned char *base = reinterpret_cast<const unsigned char *>(c->fsScratch.p);
+    FsState hst;
+    if (sums) AA_CHECK_HIP(hipMemcpyAsync(sums, base, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (column)
+        AA_CHECK_HIP(hipMemcpyAsync(column, base + c->fs_off_col, n * sizeof(double), hipMemcpyDeviceToHost, c->stream));
+    if (alive) AA_CHECK_HIP(hipMemcpyAsync(alive, base + c->fs_off_alive, n, hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipMemcpyAsync(&hst, base + c->fs_off_st, sizeof(hst), hipMemcpyDeviceToHost, c->stream));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    if (cur) *cur = hst.cur;
+    if (tie) *tie = hst.tie;
+    if (selected)
+        for (int q = 0; q < c->fs_k; ++q) selected[q] = hst.selected[q];
     return AA_OK;
 }
 

@@ -733,6 +733,7 @@ static int install_begin(Ctx *c, const Install &in)
     c->qp_iters_valid = false;                 // pass counts and sample order of the previous rows
     c->qp_perm_ready = false;
     c->qp_perm_n = 0;
+    c->fs_k = 0;                               // a selection belongs to the rows it ran on
     c->X.release();                            // (an implicit kernel: nothing stands in for K)
     if (in.borrow) {
         c->X.p = in.borrow->p;                 // read-only everywhere in the solver
@@ -1640,6 +1641,19 @@ int aa_furthest_sum(aa_ctx *h, int k, long start_index, const int *exclude, int 
     AA_CHECK_HIP(hipSetDevice(c->device));
     return launch_furthest_sum(c, k, (int)start_index, exclude, n_exclude, extra_steps < 0 ? 0 : extra_steps,
                                selected, tie);
+}
+
+int aa_get_furthest_sum_state(aa_ctx *h, long *n, int *k, double *sums, unsigned char *alive, double *column,
+                              int *cur, int *tie, int *selected)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null ctx");
+    Ctx *c = &h->c;
+    AA_REQUIRE(c->have_data && c->fs_k > 0 && c->fsScratch.p, AA_ERR_STATE,
+               "aa_get_furthest_sum_state: no selection has run on this data");
+    if (n) *n = c->n;
+    if (k) *k = c->fs_k;
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    return fetch_furthest_sum_state(c, sums, alive, column, cur, tie, selected);
 }
 
 // ------------------------------------------------------------------ GPNH
