@@ -555,7 +555,8 @@ int launch_residual_scores(Ctx *c, double *col_host, double *row_host, double *s
 // ------------------------------------------------------------------ kernels_qp.hip
 // A_host (k x k) and bscale_host (k or null) come from the host, or -- A_host == nullptr --
 // the Hessian is D G D with G = gram_dev (KP x KP, device) and D = bscale = alphaDev, set
-// up by a kernel (no host synchronisation).
+// up by a kernel (no host synchronisation).  What it launches -- mapping, caps, sample order,
+// continuation -- is decided by qp_plan (qp_plan.h) from the qp_* knobs and these arguments.
 int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, long stride_t,
               const double *bscale_host /*k or null*/, double *Ztall, int ldz, long n, int k,
               const aa_qp_params *p, int *iters_dev, aa_qp_stats *stats,
@@ -565,6 +566,8 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
 // the reduce-over-rows pass of Z'X with it, then calls launch_qp_tail_fixup: it waits for
 // the stragglers, adds sum_s (z_new - z_old)_s x_s' as QP_FIX_SLABS extra slabs of the
 // split-row partials (device-side count, no host synchronisation) and commits z_new to Z.
+// It is honoured only while the qp_overlap_tail knob is set: qp_plan asks the knob as well,
+// and the one caller that passes defer_tail passes it by that knob.
 #define QP_FIX_SLABS 32
 int launch_qp_tail_fixup(Ctx *c, double *Ztall);
 int launch_simplex_rows_generic(hipStream_t s, const double *in, double *out, long rows, long cols);

@@ -29,11 +29,10 @@
 //   * the projection is sort-free (Michelot from t = max - 1), same support and the
 //     same closed-form threshold as simplex_projection.py:13-27.
 #include "aa_internal.h"
+#include "qp_plan.h"
 
 namespace aa {
 
-#define QP_MAXMEM 8        // f_mem entries the lane / quad kernels keep in registers (spg.py:310)
-#define QW_MAXMEM 32       // ... and the wave-per-sample kernel, which takes over for memory > 8
 typedef double f64x4 __attribute__((ext_vector_type(4)));
 
 // Threshold t of the projection of w = x - a*g (components >= k excluded).
@@ -1114,12 +1113,6 @@ __global__ __launch_bounds__(256) void k_qp_wave(QW_ARGS) { qp_wave_body<KQ, MEM
 __global__ __launch_bounds__(1024) void k_qp_wave_live(QW_ARGS) { qp_wave_body<32, true>(QW_PASS); }
 #undef QW_ARGS
 #undef QW_PASS
-// continuation launches (memory == 1 by construction of the callers: the memory-1 instantiation)
-#define QW32_LAUNCH(...)                                                              \
-    do {                                                                              \
-        if (g_qp_wave_lazy) hipLaunchKernelGGL((k_qp_wave<32, true, true>), __VA_ARGS__);  \
-        else hipLaunchKernelGGL((k_qp_wave<32, true, false>), __VA_ARGS__);           \
-    } while (0)
 
 // max_iterations <= 0: the reference's loop body never runs and x = P(x0) is returned.
 template <int KQ>
@@ -1255,7 +1248,6 @@ __device__ __forceinline__ double qr_threshold(const double (&w)[CPL], unsigned 
     return (s - 1.0) / (double)c;
 }
 
-#define QR_MAXMEM 16
 template <int CPL>
 __global__ __launch_bounds__(64) void k_qp_row(const double *__restrict__ A /*[lda][lda], zero padded*/,
                                                int lda, const double *__restrict__ B, long stride_j,
@@ -1992,21 +1984,14 @@ int g_qp_quad_cap = 0;         // passes after which k_qp_quad parks a sample fo
                                // iteration), 24 below (12 500: 0.572 against 0.582)
 int g_qp_live = 0;             // k_qp_quad hands parked samples to a concurrent k_qp_wave launch (QpLive)
 #define QP_LIVE_LDS 163840     // a CU's LDS
-// Launch shapes; the measurements behind the values are in DESIGN.md sections 8.2 and 9.
-constexpr int QP_WAVES = 1024;        // most waves of the lane-per-sample kernel: one per SIMD
-constexpr int QP_QUAD_WAVES = 8192;   // most waves of k_qp_quad_w3: up to 131 072 samples every wave takes ONE batch of 16
-                                      // and the hardware hands the batches (longest first) to SIMDs as they free up
-constexpr int QP_ROW_WAVES = 2048;    // most waves of the row kernel (k_qp_row): 2 per SIMD, all resident
-constexpr int QP_WAVE_BLOCKS = 1024;  // blocks (4 waves each) of the wave-per-sample kernel when it finishes parked samples
+// Launch shapes (the others are in qp_plan.h); the measurements behind the values are in DESIGN.md sections 8.2 and 9.
 constexpr int QP_QUAD_OCC = 3;        // waves per SIMD of k_qp_quad_w3 (its LDS share beside the live consumers follows)
 constexpr int QP_LIVE_BLOCKS = 48;    // CUs given to the live consumers (one block of 16 waves each)
-constexpr int QP_TAIL_CAP = 96;       // qp_overlap_tail: only samples beyond this many passes go to the side stream
 int g_qp_quad_lazy = 0;        // four-lane QP, opt-in: the stopping test of a pass decided in the next trip (LAZYQ) -- same results; 497/497/494 it/s with, 503/498 without at the driver's flags, 524/523 against 522 at the default flags: a third of the trips skip the test for the whole wave (counted: 32 % in iterations 8-14, 31 % around 30), which saves less than the extra partial trip per batch and the 22 VGPR spills (7 without) cost
 int g_qp_fused_order = 1;   // four-lane QP: the sample order of the NEXT update is formed by extra blocks of this update's continuation launch (k_qp_wave_ord)
 int g_qp_wave_lazy = 1;        // wave-per-sample kernel: stopping test of a pass decided at the top of the next one, skipped when <d, d> proves it negative (0: after every pass)
 int g_qp_overlap_tail = 0;     // 1: stragglers on a side stream, overlapped with the Z'X pass
 int g_qp_sort = 1;             // order the samples by the previous update's pass counts
-static int qp_pass_cap() { return g_qp_pass_cap < 1 ? 1 : g_qp_pass_cap; }
 
 // Order of the samples for the lane kernel: by the pass count of the PREVIOUS weights update,
 // longest first (counting sort: block histograms, then block-wise scatter into per-bucket
@@ -2016,7 +2001,6 @@ static int qp_pass_cap() { return g_qp_pass_cap < 1 ? 1 : g_qp_pass_cap; }
 // trips at a 0.83 correlation between consecutive updates) -- and the long batches start
 // first, the short ones fill the second round.
 #define QP_SORT_BUCKETS 64
-#define QP_SORT_ROWS_PER_BLOCK 1024
 
 __device__ __forceinline__ int qp_sort_bucket(int it)
 {
@@ -2088,7 +2072,6 @@ struct QpOrder {
     int blocks;
 };
 #define QP_ORDER_AREA (2 * QP_SORT_BUCKETS + 4)
-#define QP_ORDER_MAX_BLOCKS 256
 
 __device__ __forceinline__ void qp_order_block(const QpOrder &od)
 {
@@ -2242,8 +2225,7 @@ __global__ __launch_bounds__(256) void k_qp_setup_slots(QpHeader *__restrict__ h
 
 int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_params *p)
 {
-    int KQ = 4;
-    while (KQ < k) KQ *= 2;
+    const int KQ = qp_pad_k(k);
     AA_REQUIRE(KQ <= 32 && R >= 1 && R * k <= c->KP, AA_ERR_ARG, "QP slots: k = %d, R = %d unsupported", k, R);
     AA_REQUIRE(p->memory <= QP_MAXMEM, AA_ERR_ARG, "QP slots: memory = %d > %d", p->memory, QP_MAXMEM);
     const long n = c->n;
@@ -2255,9 +2237,7 @@ int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_pa
     double *Ad = reinterpret_cast<double *>(base + off_A);
     static_assert(sizeof(QpHeader) == 64, "one header per 64 bytes");
     hipLaunchKernelGGL(k_qp_setup_slots, dim3((unsigned)R), dim3(256), 0, c->stream, hdr, Ad, gram_dev, k, KQ, c->KP);
-    long waves = (n + 63) / 64;
-    if (waves > QP_WAVES) waves = QP_WAVES;
-    const dim3 grid((unsigned)waves, (unsigned)R);
+    const dim3 grid((unsigned)qp_grid(n, 64, QP_WAVES), (unsigned)R);
     const int cap = p->max_iterations;
     double *Zt = c->Zt.as<double>();
     const double *Bt = c->Gr.as<double>();
@@ -2272,6 +2252,53 @@ int launch_qp_slots(Ctx *c, int R, int k, const double *gram_dev, const aa_qp_pa
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
+
+// What launch_qp launched, in launch order and separated by ';' (aa_qp_kernels): a host-side string,
+// written beside the launches and read by nothing that launches.
+static void __attribute__((format(printf, 2, 3))) qp_name(Ctx *c, const char *fmt, ...)
+{
+    const size_t at = strlen(c->qp_names);
+    if (at + 2 >= sizeof(c->qp_names)) return;
+    if (at) strcat(c->qp_names, ";");
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(c->qp_names + strlen(c->qp_names), sizeof(c->qp_names) - strlen(c->qp_names), fmt, ap);
+    va_end(ap);
+}
+#define QP_NAME(...) qp_name(c, __VA_ARGS__)
+
+// the arguments every QP kernel shares (A: the Hessian as padded for the kernel at hand, A2d for the wave kernels)
+struct QpProblem {
+    const double *A, *Btall;
+    long stride_j, stride_t;
+    const double *bsd;
+    double *Ztall;
+    int ldz, k;
+    const aa_qp_params *p;
+    int *iters_dev;
+    QpHeader *hdr;
+};
+
+// A continuation launch: one wave per sample of the list (rows, carry) that a first phase parked
+// (memory == 1 by construction of the callers: the memory-1 instantiation).
+struct WaveTail {
+    dim3 grid;
+    const int *rows;                           // the list: its samples' rows ...
+    const QpCarry *carry;                      // ... and continuation records
+    bool side = false;                         // deferred tail: see launch_wave_tail
+    const unsigned int *count = nullptr;       // the list's length when it is not QpHeader::n_overflow
+    int park_at = 1 << 30;                     // samples that reach this many passes go to a second list:
+    unsigned int *n_parked = nullptr;          // its length, rows, records and gradients
+    int *park_rows = nullptr;
+    QpCarry *park = nullptr;
+    double *park_g = nullptr;
+    QpLive lv{0, 0, 0u, 0u, nullptr, nullptr};
+    int rst_b = 0;                             // restart slots (grid.y): components and list stride of a slot
+    long rst_n = 0;
+    const QpOrder *order = nullptr;            // k_qp_wave_ord: order->blocks ordering blocks in front
+};
+// (defined behind launch_qp_slots_aa: the kernels it instantiates keep their place in the code object)
+static int launch_wave_tail(Ctx *c, const QpProblem &q, const WaveTail &t);
 
 // AA restarts side by side: the weights QPs of R slots in ONE launch of the four-lanes-per-sample kernel
 // and ONE of the wave-per-sample kernel (grid.y = slot), each slot with its own Hessian
@@ -2310,186 +2337,197 @@ int launch_qp_slots_aa(Ctx *c, const aa_qp_params *p)
     const double *gram = c->gramState.as<double>() + (size_t)c->KP * c->KP;          // C K C'
     hipLaunchKernelGGL(k_qp_setup_slots_aa, dim3((unsigned)R), dim3(256), 0, c->stream, hdr, A2d, bsd, gram,
                        (const double *)c->alphaDev.as<double>(), k, c->KP);
-    int cap = g_qp_quad_cap > 0 ? g_qp_quad_cap : 24;
-    if (p->max_iterations <= cap) cap = p->max_iterations;
+    // (the single fit's rule; under the requirements above -- memory <= 1, n < 65 536 -- it is the knob or 24,
+    // and max_iterations when that is no larger: loosen either requirement and this cap changes with it)
+    const int cap = qp_quad_cap(g_qp_quad_cap, n, p->memory, p->max_iterations);
     // (a single fit orders its samples by their previous pass counts from 4097 samples on: which wave
     // takes a sample does not enter its arithmetic, so the slots go without)
-    long waves = (n + 15) / 16;
-    if (waves > QP_QUAD_WAVES) waves = QP_QUAD_WAVES;
-    const long rounds = (n + 16 * waves - 1) / (16 * waves);
-    const long max_trips = 16 * rounds * ((long)cap + 2) + 16;
+    const QpQuadShape shape = qp_quad_shape(n, cap);
     const double *Bt = c->Gr.as<double>();
     double *Zt = c->Zt.as<double>();
-    const dim3 grid((unsigned)waves, (unsigned)R);
+    const dim3 grid((unsigned)shape.waves, (unsigned)R);
     hipLaunchKernelGGL((k_qp_quad_w3<1, true>), grid, dim3(64), 0, c->stream, (const double *)A2d, 32, Bt, (long)1,
                        (long)c->KP, (const double *)bsd, Zt, c->KP, n, k, *p, cap, (int *)nullptr, hdr, ovf_rows,
-                       ovf, (const int *)nullptr, max_trips, 0, (int *)nullptr, k, n_al);
-    // (a wave per parked sample: no more blocks per slot than a quarter of its samples -- which block
-    // continues a sample does not enter its arithmetic, and R x 1024 mostly idle blocks cost 49 us)
-    long wblocks = (n + 3) / 4;
-    if (wblocks < 64) wblocks = 64;
-    if (wblocks > QP_WAVE_BLOCKS) wblocks = QP_WAVE_BLOCKS;
-    if (cap < p->max_iterations)
-        QW32_LAUNCH(dim3((unsigned)wblocks, (unsigned)R), dim3(256), 0, c->stream,
-                           (const double *)A2d, Bt, (long)1, (long)c->KP, (const double *)bsd, Zt, c->KP, (long)-1, k,
-                           *p, (int *)nullptr, hdr, (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                           (const unsigned int *)nullptr, 1 << 30, (unsigned int *)nullptr,
-                           (int *)nullptr, (QpCarry *)nullptr, QpLive{0, 0, 0u, 0u, nullptr, nullptr}, k, n_al);
+                       ovf, (const int *)nullptr, shape.max_trips, 0, (int *)nullptr, k, n_al);
+    if (cap < p->max_iterations) {
+        // (a wave per parked sample: no more blocks per slot than a quarter of its samples -- which block
+        // continues a sample does not enter its arithmetic, and R x 1024 mostly idle blocks cost 49 us)
+        const long wblocks = qp_grid(n < 256 ? 256 : n, 4, QP_WAVE_BLOCKS);      // (64 at the least)
+        WaveTail t{dim3((unsigned)wblocks, (unsigned)R), ovf_rows, ovf};
+        t.rst_b = k;
+        t.rst_n = n_al;
+        AA_CHECK(launch_wave_tail(c, QpProblem{A2d, Bt, 1, c->KP, bsd, Zt, c->KP, k, p, nullptr, hdr}, t));
+    }
+    c->qp_names[0] = 0;                        // (the record is launch_qp's: nothing of the slots stays in it)
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }
 
-// What launch_qp launched, in launch order and separated by ';' (aa_qp_kernels): a host-side string,
-// written beside the launches and read by nothing that launches.
-static void qp_name(Ctx *c, const char *fmt, ...) __attribute__((format(printf, 2, 3)));
-static void qp_name(Ctx *c, const char *fmt, ...)
+// The only place that launches k_qp_wave<32, true, lazy> or k_qp_wave_ord<lazy>.  side (the deferred tail): on the
+// side stream behind everything enqueued so far, results to tmpTall by slot of the list, and what
+// launch_qp_tail_fixup needs to commit them -- the list and its length -- left in the context.
+static int launch_wave_tail(Ctx *c, const QpProblem &q, const WaveTail &t)
 {
-    const size_t at = strlen(c->qp_names);
-    if (at + 2 >= sizeof(c->qp_names)) return;
-    if (at) strcat(c->qp_names, ";");
-    va_list ap;
-    va_start(ap, fmt);
-    vsnprintf(c->qp_names + strlen(c->qp_names), sizeof(c->qp_names) - strlen(c->qp_names), fmt, ap);
-    va_end(ap);
+    const bool lazy = g_qp_wave_lazy != 0, parks = t.park_at < (1 << 30);
+    hipStream_t stream = t.side ? c->stream2 : c->stream;
+    double *zslot = t.side ? c->tmpTall.as<double>() : nullptr;
+    if (t.side) {
+        AA_CHECK_HIP(hipEventRecord(c->evFork, c->stream));
+        AA_CHECK_HIP(hipStreamWaitEvent(c->stream2, c->evFork, 0));
+    }
+    if (!t.order) {
+        const auto kernel = lazy ? k_qp_wave<32, true, true> : k_qp_wave<32, true, false>;
+        hipLaunchKernelGGL(kernel, t.grid, dim3(256), 0, stream, q.A, q.Btall, q.stride_j, q.stride_t, q.bsd, q.Ztall,
+                           q.ldz, (long)-1, q.k, *q.p, q.iters_dev, q.hdr, t.rows, t.carry, zslot, t.count, t.park_at,
+                           t.n_parked, t.park_rows, t.park, t.lv, t.rst_b, t.rst_n, t.park_g);
+        if (parks) QP_NAME("k_qp_wave<32,1,%d>:park=%d", lazy, t.park_at);
+        else QP_NAME("k_qp_wave<32,1,%d>", lazy);
+    } else {
+        const auto kernel = lazy ? k_qp_wave_ord<true> : k_qp_wave_ord<false>;
+        hipLaunchKernelGGL(kernel, dim3(t.grid.x + (unsigned)t.order->blocks), dim3(256), 0, stream, *t.order, q.A,
+                           q.Btall, q.stride_j, q.stride_t, q.bsd, q.Ztall, q.ldz, q.k, *q.p, q.iters_dev, q.hdr, t.rows,
+                           t.carry, t.park_at, t.n_parked, t.park_rows, t.park, t.park_g);
+        c->qp_perm_ready = true;               // the next update's order
+        c->qp_perm_n = t.order->n;
+        if (parks) QP_NAME("k_qp_wave_ord<%d>:park=%d", lazy, t.park_at);
+        else QP_NAME("k_qp_wave_ord<%d>", lazy);
+    }
+    if (t.side) {
+        AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
+        c->qp_tail_pending = true;
+        c->qp_tail_rows = t.rows;
+        c->qp_tail_count = t.count ? t.count : &q.hdr->n_overflow;
+    }
+    return AA_OK;
 }
-#define QP_NAME(...) qp_name(c, __VA_ARGS__)
 
+// launch_qp's scratch (qpStats), by member: QpHeader | A[KQ*KQ] | A2[KW*KW] | bscale[64] | ovf_rows[n] | ovf[n] |
+// ovf2_rows[n] | ovf2[n] (the second overflow list: QP_TAIL_CAP).  A null base gives the sizes alone;
+// prefix_only: base holds host_prefix_bytes() and no more (a host-side set-up), the lists stay null.
+struct QpScratch {
+    QpHeader *hdr;
+    double *A, *A2, *bscale;
+    int *ovf_rows = nullptr, *ovf2_rows = nullptr;
+    QpCarry *ovf = nullptr, *ovf2 = nullptr;
+    size_t at = 0, prefix = 0;
+    QpScratch(void *base, long n, int KQ, int KW, bool prefix_only = false)
+    {
+        unsigned char *b = static_cast<unsigned char *>(base);
+        auto take = [&](size_t bytes) { at += bytes; return b ? b + (at - bytes) : nullptr; };
+        hdr = (QpHeader *)take(192);
+        A = (double *)take((size_t)KQ * KQ * sizeof(double));
+        A2 = (double *)take((size_t)KW * KW * sizeof(double));
+        bscale = (double *)take(64 * sizeof(double));
+        prefix = at;
+        if (prefix_only) return;
+        ovf_rows = (int *)take(round_up((long)n * sizeof(int), 16));
+        ovf = (QpCarry *)take((size_t)n * sizeof(QpCarry));
+        ovf2_rows = (int *)take(round_up((long)n * sizeof(int), 16));
+        ovf2 = (QpCarry *)take((size_t)n * sizeof(QpCarry));
+    }
+    size_t bytes() const { return at; }
+    size_t host_prefix_bytes() const { return prefix; }       // what a host-side set-up fills: up to bscale
+};
+
+// The continuation a first phase's plan asks for, on its overflow list.  deferred: the caller's Z'X pass runs
+// beside it on the weights as the first phase left them and launch_qp_tail_fixup adds the rank-m correction
+// afterwards -- the dependent chain of the longest sample (100-450 passes at ~0.9 us) hides behind an HBM-bound
+// pass instead of idling the chip.  two_stage: everything up to park_at passes here, at full speed on the whole
+// chip; only the handful of samples beyond it deferred.  (Tried: a CU-masked stream pair,
+// hipExtStreamCreateWithCUMask -- 8 or 16 CUs for these chains alone, the rest of the chip for the caller's
+// pass, so that the two share no SIMD.  With masked queues alive EVERY launch of the process, on any stream,
+// took ~45 us longer (k_qp_setup 6 -> 50 us) and the iteration went from 2.0 to 3.0-3.2 ms:
+// profiles/round4_ab.txt.)
+static int finish_parked(Ctx *c, const QpProblem &q, const QpScratch &s, const QpPlan &pl, long n)
+{
+    if (pl.tail == QpTail::none || pl.tail == QpTail::live) return AA_OK;      // (live: the quad arm's own clean-up)
+    const QpOrder od{q.iters_dev, c->qpPerm.as<int>(), c->qpPerm.as<int>() + (pl.tail_ord ? n : 0), n, pl.order_blocks};
+    WaveTail t{dim3((unsigned)QP_WAVE_BLOCKS), s.ovf_rows, s.ovf, pl.tail == QpTail::deferred};
+    if (pl.tail_ord) t.order = &od;
+    if (pl.tail != QpTail::two_stage) return launch_wave_tail(c, q, t);
+    t.park_at = pl.park_at;
+    t.n_parked = &s.hdr->pad;
+    t.park_rows = s.ovf2_rows;
+    t.park = s.ovf2;
+    t.park_g = c->tmpTall.as<double>();
+    AA_CHECK(launch_wave_tail(c, q, t));
+    WaveTail t2{dim3(64), s.ovf2_rows, s.ovf2, /*side*/ true, &s.hdr->pad};
+    return launch_wave_tail(c, q, t2);
+}
+
+// Check, plan (qp_plan.h: what to launch, every mapping and schedule), allocate, set up, launch what
+// the plan says, read back the statistics.
 int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, long stride_t,
               const double *bscale_host, double *Ztall, int ldz, long n, int k,
               const aa_qp_params *p, int *iters_dev, aa_qp_stats *stats, const double *gram_dev,
               bool defer_tail)
 {
-    int KQ = 4;
-    while (KQ < k) KQ *= 2;
-    AA_REQUIRE(KQ <= 64, AA_ERR_ARG, "QP: k = %d > 64 unsupported", k);
+    AA_REQUIRE(qp_pad_k(k) <= 64, AA_ERR_ARG, "QP: k = %d > 64 unsupported", k);
     AA_REQUIRE(n < (1L << 31), AA_ERR_ARG, "QP: too many samples");
     c->qp_names[0] = 0;
-    // default (qp_mode 0), k <= 32: four lanes per sample in the matrix-core operand layout
-    // (k_qp_quad) followed by the wave-per-sample kernel for the samples that reach its pass cap --
-    // ahead of the other mappings at every size measured (1 600 .. 100 000 samples per GPU:
-    // 0.63 ms per outer iteration at 12 500 rows against 0.69 for the row kernel and 0.81 for
-    // lane + wave; 1.99 against 2.21 ms at 100 000) -- except when every sample gets the same
-    // one or two passes (GPNH's weights QP with max_iterations = 1): nothing diverges then and
-    // the lane-per-sample kernel, 64 samples per wave, is cheaper (0.175 against 0.188 ms on the
-    // C3 stand-in).  k > 32: one wave per sample.
-    // spg.py:310 allocates f_mem of any length; the kernels keep it in registers: 8 entries in the
-    // throughput kernels, 16 in the row kernel, 32 in the wave-per-sample kernel, which therefore
-    // takes the whole update when memory > 8 (a setting the reference's callers never use)
-    const bool big_mem = p->memory > QP_MAXMEM;
-    const bool row_mode = KQ <= 32 && g_qp_mode == 3 && p->memory <= QR_MAXMEM;
-    const bool quad_mode = !big_mem && KQ <= 32 && (g_qp_mode == 4 || (g_qp_mode == 0 && p->max_iterations > 4));
-    const bool wave_only = !row_mode && !quad_mode && (big_mem || KQ > 32 || g_qp_mode == 1 || g_qp_mode == 3);   // else: lane + wave
-    const int KW = KQ > 32 ? 64 : 32;              // A padding of the wave and row kernels
     AA_REQUIRE(p->memory <= QW_MAXMEM, AA_ERR_ARG,
                "QP: memory = %d exceeds the HIP backend limit of %d", p->memory, QW_MAXMEM);
-    // scratch layout: QpHeader | A[KQ*KQ] | A2[KW*KW] | bscale[64] | ovf_rows[n] | ovf[n]
-    const size_t off_A = 192;             // QpHeader at 0
-    const size_t off_A2 = off_A + (size_t)KQ * KQ * sizeof(double);
-    const size_t off_bs = off_A2 + (size_t)KW * KW * sizeof(double);
-    const size_t off_rows = off_bs + 64 * sizeof(double);
-    const size_t off_ovf = off_rows + round_up((long)n * sizeof(int), 16);
-    const size_t off_rows2 = off_ovf + (size_t)n * sizeof(QpCarry);          // second overflow list (QP_TAIL_CAP)
-    const size_t off_ovf2 = off_rows2 + round_up((long)n * sizeof(int), 16);
-    const size_t bytes = off_ovf2 + (size_t)n * sizeof(QpCarry);
-    AA_CHECK(c->qpStats.alloc(bytes));
-    // samples in the order of their pass counts in the previous update of this context (iters_dev
-    // still holds them; the kernels below overwrite them); pointless when everybody gets the same
-    // one or two passes, and for the kernel that takes a wave per sample anyway
-    // and for a few thousand samples (measured: 1610 and 3000 rows 2 % faster unordered, 12 500 rows
-    // 3 % slower)
-    const bool will_sort = g_qp_sort && p->max_iterations > 2 && n > 4096 && !wave_only && iters_dev &&
-                           iters_dev == c->qpIters.as<int>() && c->qp_iters_valid;
-    int *sort_hist = nullptr;
-    // four-lane kernel: the order is formed by extra blocks of the PREVIOUS update's continuation launch
-    // (k_qp_wave_ord) and this update's launch forms the next one; an update without a predecessor runs
-    // unordered
-    int quad_cap = g_qp_quad_cap > 0 ? g_qp_quad_cap : (n >= 65536 ? 32 : 24);
-    if (p->memory > 1 || p->max_iterations <= quad_cap) quad_cap = p->max_iterations;
-    // (deferred stragglers: only the two-stage form, whose first stage is an ordinary launch on the main stream)
-    const bool defer_ok = defer_tail && !stats && c->stream2 && ldz == c->KP && KW == 32 && c->dtype == AA_F32 &&
-                          c->tmpTall.bytes >= (size_t)n * 32 * sizeof(double);
-    const bool two_stage = defer_ok && QP_TAIL_CAP > quad_cap && QP_TAIL_CAP < p->max_iterations;
-    const bool fused_order = g_qp_fused_order && g_qp_sort && quad_mode && !A_host && KW == 32 && p->memory <= 1 &&
-                             !g_qp_live && (!defer_ok || two_stage) && quad_cap < p->max_iterations &&
-                             p->max_iterations > 2 && n > 4096 &&
-                             n <= (long)QP_ORDER_MAX_BLOCKS * QP_SORT_ROWS_PER_BLOCK && iters_dev &&
-                             iters_dev == c->qpIters.as<int>();
-    const int order_blocks = (int)((n + QP_SORT_ROWS_PER_BLOCK - 1) / QP_SORT_ROWS_PER_BLOCK);
-    const bool use_prefetched = fused_order && c->qp_perm_ready && c->qp_perm_n == n;
+    const QpKnobs knobs{g_qp_mode, g_qp_pass_cap, g_qp_quad_cap, g_qp_live, g_qp_quad_lazy, g_qp_fused_order,
+                        g_qp_wave_lazy, g_qp_overlap_tail, g_qp_sort};
+    const bool defer_possible = defer_tail && !stats && c->stream2 && ldz == c->KP && c->dtype == AA_F32 &&
+                                c->tmpTall.bytes >= (size_t)n * 32 * sizeof(double);
+    const QpPlanIn in{n, k, p->memory, p->max_iterations, /*host_hessian*/ A_host != nullptr,
+                      /*own_iters*/ iters_dev && iters_dev == c->qpIters.as<int>(), /*iters_valid*/ c->qp_iters_valid,
+                      /*perm_ready*/ c->qp_perm_ready && c->qp_perm_n == n, defer_possible,
+                      /*live_stream*/ c->stream3 && !defer_tail};
+    const QpPlan pl = qp_plan(knobs, in);
     c->qp_perm_ready = false;
+    const int KQ = pl.KQ, KW = pl.KW, cap = pl.cap;      // (the names the launch macros below are written in)
+
+    AA_CHECK(c->qpStats.alloc(QpScratch(nullptr, n, KQ, KW).bytes()));
+    const QpScratch s(c->qpStats.p, n, KQ, KW);
     if (A_host) {
-        std::vector<unsigned char> host(off_rows, 0);
-        double *Ah = reinterpret_cast<double *>(host.data() + off_A);
-        double *A2h = reinterpret_cast<double *>(host.data() + off_A2);
+        std::vector<unsigned char> host(s.host_prefix_bytes(), 0);
+        const QpScratch h(host.data(), n, KQ, KW, /*prefix_only*/ true);
         for (int i = 0; i < k; ++i)
-            for (int j = 0; j < k; ++j) {
-                Ah[i * KQ + j] = A_host[i * k + j];
-                A2h[i * KW + j] = A_host[i * k + j];
-            }
-        double *bs = reinterpret_cast<double *>(host.data() + off_bs);
-        for (int i = 0; i < 64; ++i) bs[i] = (bscale_host && i < k) ? bscale_host[i] : 1.0;
-        reinterpret_cast<QpHeader *>(host.data())->pad1 = 1u;      // an order, if any, is formed in stream order
-        AA_CHECK_HIP(hipMemcpyAsync(c->qpStats.p, host.data(), off_rows, hipMemcpyHostToDevice, c->stream));
+            for (int j = 0; j < k; ++j) h.A[i * KQ + j] = h.A2[i * KW + j] = A_host[i * k + j];
+        for (int i = 0; i < 64; ++i) h.bscale[i] = (bscale_host && i < k) ? bscale_host[i] : 1.0;
+        h.hdr->pad1 = 1u;      // an order, if any, is formed in stream order
+        AA_CHECK_HIP(hipMemcpyAsync(c->qpStats.p, host.data(), host.size(), hipMemcpyHostToDevice, c->stream));
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // host vector goes out of scope
     } else {
         AA_REQUIRE(gram_dev != nullptr, AA_ERR_ARG, "QP: no Hessian");
-        if (will_sort || fused_order) {                // its histograms are zeroed by the set-up kernel
-            AA_CHECK(c->qpPerm.alloc((size_t)n * sizeof(int) + QP_ORDER_AREA * sizeof(int)));
-            sort_hist = c->qpPerm.as<int>() + n;
-        }
-        unsigned char *b0 = reinterpret_cast<unsigned char *>(c->qpStats.p);
-        hipLaunchKernelGGL(k_qp_setup, dim3(1), dim3(256), 0, c->stream, reinterpret_cast<QpHeader *>(b0),
-                           reinterpret_cast<double *>(b0 + off_A), reinterpret_cast<double *>(b0 + off_A2),
-                           reinterpret_cast<double *>(b0 + off_bs), gram_dev,
-                           (const double *)c->alphaDev.as<double>(), k, KQ, KW, c->KP, sort_hist,
-                           fused_order ? (use_prefetched ? order_blocks : 0) : -1);
+        // (the histograms of an ordering are zeroed by the set-up kernel)
+        if (pl.sort_hist) AA_CHECK(c->qpPerm.alloc((size_t)n * sizeof(int) + QP_ORDER_AREA * sizeof(int)));
+        int *sort_hist = pl.sort_hist ? c->qpPerm.as<int>() + n : nullptr;
+        hipLaunchKernelGGL(k_qp_setup, dim3(1), dim3(256), 0, c->stream, s.hdr, s.A, s.A2, s.bscale, gram_dev,
+                           (const double *)c->alphaDev.as<double>(), k, KQ, KW, c->KP, sort_hist, pl.setup_order);
     }
-    unsigned char *base = reinterpret_cast<unsigned char *>(c->qpStats.p);
-    QpHeader *hdr = reinterpret_cast<QpHeader *>(base);
-    const double *Ad = reinterpret_cast<const double *>(base + off_A);
-    const double *A2d = reinterpret_cast<const double *>(base + off_A2);
-    const double *bsd = (bscale_host || !A_host) ? reinterpret_cast<const double *>(base + off_bs) : nullptr;
-    int *ovf_rows = reinterpret_cast<int *>(base + off_rows);
-    QpCarry *ovf = reinterpret_cast<QpCarry *>(base + off_ovf);
-    int *ovf2_rows = reinterpret_cast<int *>(base + off_rows2);
-    QpCarry *ovf2 = reinterpret_cast<QpCarry *>(base + off_ovf2);
+    const double *A2d = s.A2, *bsd = (bscale_host || !A_host) ? s.bscale : nullptr;
+    const QpProblem q{A2d, Btall, stride_j, stride_t, bsd, Ztall, ldz, k, p, iters_dev, s.hdr};
+    const dim3 grid((unsigned)pl.grid);
+    // the order of the samples a first phase runs in: none, one formed here and now (iters_dev still holds the
+    // pass counts of the previous update of this context; the kernels overwrite them), or the one the previous
+    // update's k_qp_wave_ord left (the kernel checks QpHeader::pad1)
+    const int *perm = pl.order == QpSampleOrder::prefetched ? c->qpPerm.as<int>() : nullptr;
 
-    if (p->max_iterations <= 0) {
-        dim3 grid((unsigned)((n + 255) / 256));
+    switch (pl.mapping) {
+    case QpMap::project_only:
 #define QPP(KQV) hipLaunchKernelGGL(k_qp_project_only<KQV>, grid, dim3(256), 0, c->stream, Ztall, Ztall, ldz, n, k)
         switch (KQ) { case 4: QPP(4); break; case 8: QPP(8); break; case 16: QPP(16); break;
                       case 32: QPP(32); break; default: QPP(64); break; }
 #undef QPP
         QP_NAME("k_qp_project_only<%d>", KQ);
-    } else if (row_mode) {
-        // samples ordered by their previous pass count, longest first (iters_dev still holds the
-        // counts of the previous update of this context); every sample runs to completion
-        const int *perm = nullptr;
-        if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
-        long waves = (n + 3) / 4;
-        if (waves > QP_ROW_WAVES) waves = QP_ROW_WAVES;
-        if (k <= 16)
-            hipLaunchKernelGGL(k_qp_row<1>, dim3((unsigned)waves), dim3(64), 0, c->stream, A2d, KW, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm);
-        else
-            hipLaunchKernelGGL(k_qp_row<2>, dim3((unsigned)waves), dim3(64), 0, c->stream, A2d, KW, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr, perm);
-        QP_NAME("k_qp_row<%d>", k <= 16 ? 1 : 2);
-    } else if (quad_mode) {
-        int cap = g_qp_quad_cap > 0 ? g_qp_quad_cap : (n >= 65536 ? 32 : 24);
-        if (p->memory > 1 || p->max_iterations <= cap) cap = p->max_iterations;
-        long waves = (n + 15) / 16;
-        if (waves > QP_QUAD_WAVES) waves = QP_QUAD_WAVES;
-        const int *perm = nullptr;
-        hipStream_t s_main = c->stream;
-        // watchdog only: a wave's slots take their samples one after the other, each at most
-        // cap passes and a start-up trip
-        const long rounds = (n + 16 * waves - 1) / (16 * waves);
-        const long max_trips = 16 * rounds * ((long)cap + 2) + 16;
+        break;
+    case QpMap::row:
+        // samples longest first; every sample runs to completion
+        if (pl.order == QpSampleOrder::sort_now) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, pl.sort_hist));
+#define QRW(CPLV) hipLaunchKernelGGL(k_qp_row<CPLV>, grid, dim3(64), 0, c->stream, A2d, KW, Btall, stride_j, stride_t, \
+                                     bsd, Ztall, ldz, n, k, *p, iters_dev, s.hdr, perm)
+        if (pl.sel == 1) QRW(1); else QRW(2);
+#undef QRW
+        QP_NAME("k_qp_row<%d>", pl.sel);
+        break;
+    case QpMap::quad: {
         // live hand-over (qp_live): the consumer launch of k_qp_wave goes out FIRST, on the side stream,
         // so that its waves (80 VGPRs) are resident when k_qp_quad fills the rest of every SIMD --
         // the quad kernel then runs at the four-waves-per-SIMD budget (128 VGPRs: 80 + 3 x 128 <= 512)
-        const bool live = g_qp_live && cap < p->max_iterations && c->stream3 && KW == 32 && !defer_tail;
+        const bool live = pl.tail == QpTail::live;
         QpLive lv{0, 0, 0u, 0u, nullptr, nullptr};
         if (live) {
             if ((long)c->qp_live_cap < n) {
@@ -2505,7 +2543,7 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
             }
             lv.mode = 1;
             lv.epoch = ++c->qp_live_epoch;
-            lv.producer_waves = (unsigned int)waves;
+            lv.producer_waves = (unsigned int)pl.grid;
             lv.n = (unsigned int)n;
             lv.ready = c->qpLive.as<int>();
             lv.done = lv.ready + c->qp_live_cap;
@@ -2518,8 +2556,8 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
                 lds_attr_set = true;
             }
             hipLaunchKernelGGL(k_qp_wave_live, dim3((unsigned)QP_LIVE_BLOCKS), dim3(1024), QP_LIVE_LDS, c->stream3, A2d, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                               (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
+                               stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, s.hdr,
+                               (const int *)s.ovf_rows, (const QpCarry *)s.ovf, (double *)nullptr,
                                (const unsigned int *)nullptr, 1 << 30,
                                (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
             QP_NAME("k_qp_wave_live");
@@ -2527,186 +2565,61 @@ int launch_qp(Ctx *c, const double *A_host, const double *Btall, long stride_j, 
         }
         // (the ordering kernels run while the cross-stream dependency of the consumers resolves: the
         // consumers are resident on their CUs before k_qp_quad fills the chip)
-        if (fused_order) perm = use_prefetched ? c->qpPerm.as<int>() : nullptr;   // (the kernel checks QpHeader::pad1)
-        else if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
+        if (pl.order == QpSampleOrder::sort_now) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, pl.sort_hist));
         // beside live consumers every wave of k_qp_quad asks for its share of a CU's LDS (see k_qp_wave_live)
         const unsigned quad_lds = live ? (unsigned)((QP_LIVE_LDS / (4 * QP_QUAD_OCC)) & ~511) : 0u;
-        const int live_epoch = lv.epoch;
-        int *ovf_ready = lv.ready;
 #define QQK(MTV, M1V, LZV)                                                                          \
-    hipLaunchKernelGGL((k_qp_quad_w3<MTV, M1V, LZV>), dim3((unsigned)waves), dim3(64), quad_lds, s_main, A2d, KW, Btall, \
-                       stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf,           \
-                       perm, max_trips, live_epoch, ovf_ready, 0, 0L)
-#define QQL(MTV, M1V) do { if (g_qp_quad_lazy && !live) QQK(MTV, M1V, true); else QQK(MTV, M1V, false); } while (0)
-        if (k <= 16) { if (p->memory <= 1) QQL(1, true); else QQL(1, false); }
-        else         { if (p->memory <= 1) QQL(2, true); else QQL(2, false); }
+    hipLaunchKernelGGL((k_qp_quad_w3<MTV, M1V, LZV>), grid, dim3(64), quad_lds, c->stream, A2d, KW, Btall, \
+                       stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, s.hdr, s.ovf_rows, s.ovf,       \
+                       perm, pl.max_trips, lv.epoch, lv.ready, 0, 0L)
+#define QQL(MTV, M1V) do { if (pl.quad_lazy) QQK(MTV, M1V, true); else QQK(MTV, M1V, false); } while (0)
+        if (pl.sel == 1) { if (pl.mem1) QQL(1, true); else QQL(1, false); }
+        else             { if (pl.mem1) QQL(2, true); else QQL(2, false); }
 #undef QQL
 #undef QQK
-        QP_NAME("k_qp_quad_w3<%d,%d,%d>:cap=%d", k <= 16 ? 1 : 2, p->memory <= 1, g_qp_quad_lazy && !live, cap);
+        QP_NAME("k_qp_quad_w3<%d,%d,%d>:cap=%d", pl.sel, pl.mem1, pl.quad_lazy, cap);
         if (live) {
             // clean-up: whatever the consumers did not take (they give up after a bounded wait)
             AA_CHECK_HIP(hipStreamWaitEvent(c->stream, c->evJoin, 0));
             lv.mode = 2;
-            QW32_LAUNCH(dim3(64), dim3(256), 0, c->stream, A2d, Btall,
-                               stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                               (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                               (const unsigned int *)nullptr, 1 << 30,
-                               (unsigned int *)nullptr, (int *)nullptr, (QpCarry *)nullptr, lv);
-            QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
-        } else if (cap < p->max_iterations) {
-            // the parked samples, one wave each.  defer_tail: on the side stream, results to
-            // tmpTall by slot; the caller's Z'X pass runs beside them on the weights as k_qp_quad
-            // left them and launch_qp_tail_fixup adds the rank-m correction afterwards -- the
-            // dependent chain of the longest sample (100-450 passes at ~0.9 us) hides behind an
-            // HBM-bound pass instead of idling the chip
-            const bool defer = defer_ok;
-            const int tail_cap = QP_TAIL_CAP;
-            if (defer && tail_cap > cap && tail_cap < p->max_iterations) {
-                // two stages: everything up to tail_cap passes here, at full speed on the whole chip;
-                // the few samples beyond it on the side stream beside the caller's Z'X pass
-                if (fused_order) {
-                    const QpOrder od{iters_dev, c->qpPerm.as<int>(), c->qpPerm.as<int>() + n, n, order_blocks};
-                    const dim3 og((unsigned)(QP_WAVE_BLOCKS + order_blocks));
-                    if (g_qp_wave_lazy)
-                        hipLaunchKernelGGL(k_qp_wave_ord<true>, og, dim3(256), 0, c->stream, od, A2d, Btall, stride_j,
-                                           stride_t, bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2,
-                                           c->tmpTall.as<double>());
-                    else
-                        hipLaunchKernelGGL(k_qp_wave_ord<false>, og, dim3(256), 0, c->stream, od, A2d, Btall, stride_j,
-                                           stride_t, bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, tail_cap, &hdr->pad, ovf2_rows, ovf2,
-                                           c->tmpTall.as<double>());
-                    c->qp_perm_ready = true;
-                    c->qp_perm_n = n;
-                    QP_NAME("k_qp_wave_ord<%d>:park=%d", g_qp_wave_lazy != 0, tail_cap);
-                } else {
-                QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, c->stream, A2d, Btall,
-                                   stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                                   (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr,
-                                   (const unsigned int *)nullptr, tail_cap, &hdr->pad, ovf2_rows, ovf2,
-                                   QpLive{0, 0, 0u, 0u, nullptr, nullptr}, 0, 0L, c->tmpTall.as<double>());
-                QP_NAME("k_qp_wave<32,1,%d>:park=%d", g_qp_wave_lazy != 0, tail_cap);
-                }
-                // the handful beyond tail_cap on the side stream.  (Tried: a CU-masked stream pair,
-                // hipExtStreamCreateWithCUMask -- 8 or 16 CUs for these chains alone, the rest of the chip for
-                // the caller's pass, so that the two share no SIMD.  With masked queues alive EVERY launch of the
-                // process, on any stream, took ~45 us longer (k_qp_setup 6 -> 50 us) and the iteration went
-                // from 2.0 to 3.0-3.2 ms: profiles/round4_ab.txt.)
-                hipStream_t ss = c->stream2;
-                AA_CHECK_HIP(hipEventRecord(c->evFork, c->stream));
-                AA_CHECK_HIP(hipStreamWaitEvent(ss, c->evFork, 0));
-                QW32_LAUNCH(dim3(64), dim3(256), 0, ss, A2d, Btall,
-                                   stride_j, stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                                   (const int *)ovf2_rows, (const QpCarry *)ovf2, c->tmpTall.as<double>(),
-                                   (const unsigned int *)&hdr->pad);
-                QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
-                AA_CHECK_HIP(hipEventRecord(c->evJoin, ss));
-                c->qp_tail_pending = true;
-                c->qp_tail_rows = ovf2_rows;
-                c->qp_tail_count = &hdr->pad;
-            } else {
-                hipStream_t s2 = c->stream;
-                double *zslot = nullptr;
-                if (defer) {
-                    AA_CHECK_HIP(hipEventRecord(c->evFork, c->stream));
-                    AA_CHECK_HIP(hipStreamWaitEvent(c->stream2, c->evFork, 0));
-                    s2 = c->stream2;
-                    zslot = c->tmpTall.as<double>();
-                }
-                if (fused_order && !defer) {
-                    const QpOrder od{iters_dev, c->qpPerm.as<int>(), c->qpPerm.as<int>() + n, n, order_blocks};
-                    const dim3 og((unsigned)(QP_WAVE_BLOCKS + order_blocks));
-                    if (g_qp_wave_lazy)
-                        hipLaunchKernelGGL(k_qp_wave_ord<true>, og, dim3(256), 0, s2, od, A2d, Btall, stride_j, stride_t,
-                                           bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, 1 << 30, (unsigned int *)nullptr, (int *)nullptr,
-                                           (QpCarry *)nullptr);
-                    else
-                        hipLaunchKernelGGL(k_qp_wave_ord<false>, og, dim3(256), 0, s2, od, A2d, Btall, stride_j, stride_t,
-                                           bsd, Ztall, ldz, k, *p, iters_dev, hdr, (const int *)ovf_rows,
-                                           (const QpCarry *)ovf, 1 << 30, (unsigned int *)nullptr, (int *)nullptr,
-                                           (QpCarry *)nullptr);
-                    c->qp_perm_ready = true;
-                    c->qp_perm_n = n;
-                    QP_NAME("k_qp_wave_ord<%d>", g_qp_wave_lazy != 0);
-                } else {
-                QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
-                                   stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                                   (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
-                QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
-                }
-                if (defer) {
-                    AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
-                    c->qp_tail_pending = true;
-                    c->qp_tail_rows = ovf_rows;
-                    c->qp_tail_count = &hdr->n_overflow;
-                }
-            }
+            WaveTail t{dim3(64), s.ovf_rows, s.ovf};
+            t.lv = lv;
+            AA_CHECK(launch_wave_tail(c, q, t));
         }
-    } else if (wave_only) {
-        long blocks = (n + 3) / 4;
-        if (blocks > 2048) blocks = 2048;
+        AA_CHECK(finish_parked(c, q, s, pl, n));
+        break;
+    }
+    case QpMap::wave_only:
 #define QWF(KWV, M1V)                                                                            \
-    hipLaunchKernelGGL((k_qp_wave<KWV, M1V>), dim3((unsigned)blocks), dim3(256), 0, c->stream, A2d, Btall, \
-                       stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, hdr,               \
-                       (const int *)ovf_rows, (const QpCarry *)ovf, (double *)nullptr)
-        if (KW == 64) { if (p->memory <= 1) QWF(64, true); else QWF(64, false); }
-        else          { if (p->memory <= 1) QWF(32, true); else QWF(32, false); }
+    hipLaunchKernelGGL((k_qp_wave<KWV, M1V>), grid, dim3(256), 0, c->stream, A2d, Btall, \
+                       stride_j, stride_t, bsd, Ztall, ldz, n, k, *p, iters_dev, s.hdr,               \
+                       (const int *)s.ovf_rows, (const QpCarry *)s.ovf, (double *)nullptr)
+        if (KW == 64) { if (pl.mem1) QWF(64, true); else QWF(64, false); }
+        else          { if (pl.mem1) QWF(32, true); else QWF(32, false); }
 #undef QWF
-        QP_NAME("k_qp_wave<%d,%d,1>", KW, p->memory <= 1);
-    } else {
-        // phase 1: every sample gets up to pass_cap passes in a lane
-        int cap = qp_pass_cap();
-        if (p->memory > 1 || p->max_iterations <= cap) cap = p->max_iterations;
-        // one wave per SIMD: lanes that finish early pull further samples, so a wave's
-        // trip count is the sum over ~n/65536 samples per lane instead of two full rounds
-        long waves = (n + 63) / 64;
-        if (waves > QP_WAVES) waves = QP_WAVES;
-        dim3 grid((unsigned)waves);
-        // samples ordered by their previous pass count (iters_dev still holds the counts of
-        // the previous update of this context; the kernels below overwrite them)
-        const int *perm = nullptr;
-        if (will_sort) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, sort_hist != nullptr));
+        QP_NAME("k_qp_wave<%d,%d,1>", KW, pl.mem1);
+        break;
+    case QpMap::lane:
+        // phase 1: every sample gets up to cap passes in a lane, in the order of the previous pass counts
+        if (pl.order == QpSampleOrder::sort_now) AA_CHECK(qp_order_rows(c, iters_dev, n, &perm, pl.sort_hist));
 #define QPL2(KQV, FULLV)                                                                       \
-    hipLaunchKernelGGL((k_qp<KQV, FULLV>), grid, dim3(64), 0, c->stream, Ad, Btall, stride_j,  \
-                       stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, hdr, ovf_rows, ovf, perm)
-#define QPL(KQV) do { if (k == KQV) QPL2(KQV, true); else QPL2(KQV, false); } while (0)
+    hipLaunchKernelGGL((k_qp<KQV, FULLV>), grid, dim3(64), 0, c->stream, s.A, Btall, stride_j, \
+                       stride_t, bsd, Ztall, ldz, n, k, *p, cap, iters_dev, s.hdr, s.ovf_rows, s.ovf, perm)
+#define QPL(KQV) do { if (pl.full) QPL2(KQV, true); else QPL2(KQV, false); } while (0)
         switch (KQ) { case 4: QPL(4); break; case 8: QPL(8); break; case 16: QPL(16); break;
                       default: QPL(32); break; }
 #undef QPL2
 #undef QPL
-        QP_NAME("k_qp<%d,%d>:cap=%d", KQ > 32 ? 32 : KQ, k == KQ, cap);
-        if (cap < p->max_iterations) {
-            // phase 2: the stragglers, one wave each (grid is fixed; the count is read on
-            // the device, so no host synchronisation between the phases)
-            const bool defer = defer_tail && !stats && c->stream2 && ldz == c->KP && KW == 32 &&
-                               c->dtype == AA_F32 &&
-                               c->tmpTall.bytes >= (size_t)n * 32 * sizeof(double);
-            hipStream_t s2 = c->stream;
-            double *zslot = nullptr;
-            if (defer) {
-                AA_CHECK_HIP(hipEventRecord(c->evFork, c->stream));
-                AA_CHECK_HIP(hipStreamWaitEvent(c->stream2, c->evFork, 0));
-                s2 = c->stream2;
-                zslot = c->tmpTall.as<double>();
-            }
-            QW32_LAUNCH(dim3((unsigned)QP_WAVE_BLOCKS), dim3(256), 0, s2, A2d, Btall, stride_j,
-                               stride_t, bsd, Ztall, ldz, (long)-1, k, *p, iters_dev, hdr,
-                               (const int *)ovf_rows, (const QpCarry *)ovf, zslot);
-            QP_NAME("k_qp_wave<32,1,%d>", g_qp_wave_lazy != 0);
-            if (defer) {
-                AA_CHECK_HIP(hipEventRecord(c->evJoin, c->stream2));
-                c->qp_tail_pending = true;
-                c->qp_tail_rows = ovf_rows;
-                c->qp_tail_count = &hdr->n_overflow;
-            }
-        }
+        QP_NAME("k_qp<%d,%d>:cap=%d", KQ, pl.full, cap);
+        // phase 2: the stragglers, one wave each (grid is fixed; the count is read on
+        // the device, so no host synchronisation between the phases)
+        AA_CHECK(finish_parked(c, q, s, pl, n));
+        break;
     }
     AA_CHECK_HIP(hipGetLastError());
     if (stats) {
         QpHeader h;
-        AA_CHECK_HIP(hipMemcpyAsync(&h, hdr, sizeof(h), hipMemcpyDeviceToHost, c->stream));
+        AA_CHECK_HIP(hipMemcpyAsync(&h, s.hdr, sizeof(h), hipMemcpyDeviceToHost, c->stream));
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));
         stats->total_passes = (long)h.total_passes;
         stats->max_passes = (int)h.max_passes;

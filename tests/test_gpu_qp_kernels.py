@@ -230,7 +230,7 @@ def test_every_qp_kernel_name_has_a_case():
         assert any(re.fullmatch(_format_pattern(fmt), piece) for piece in pieces), "no case expects %r" % fmt
     for piece in pieces:
         assert any(re.fullmatch(_format_pattern(fmt), piece) for fmt in formats), piece
-    # every instantiation the launcher can pick (the macros QPL, QQL, QWF, QPP, QW32_LAUNCH and the two row kernels)
+    # every instantiation the launcher can pick (the macros QPL, QQL, QWF, QPP, launch_wave_tail and the two row kernels)
     want = (["k_qp<%d,%d>" % (kq, full) for kq in (4, 8, 16, 32) for full in (0, 1)] +
             ["k_qp_quad_w3<%d,%d,%d>" % (mt, m1, lz) for mt in (1, 2) for m1 in (0, 1) for lz in (0, 1)] +
             ["k_qp_row<1>", "k_qp_row<2>", "k_qp_wave_ord<0>", "k_qp_wave_ord<1>", "k_qp_wave<32,1,0>"] +
