@@ -172,8 +172,8 @@ int aa_device_count(int *count);
  * Changes results at rounding level (another summation order):
  *   "pq_mfma"           0|1    1 (default): the two wide Grams of the line search on the f64 matrix cores;
  *                               0: the LDS / VALU kernel
- * None of the following six changes a bit of any result; tests/test_gpu_longrun.py:
- * test_schedule_knobs_do_not_change_a_bit pins that:
+ * None of the following seven changes a bit of any result; tests/test_gpu_longrun.py:
+ * test_schedule_knobs_do_not_change_a_bit pins that for the first six, tests/test_gpu_spg_tail.py for the last:
  *   "qp_fused_order"    0|1    1 (default): the sample order of the NEXT weights update is formed by extra
  *                               blocks of this update's continuation launch instead of two launches in
  *                               front of the four-lane kernel
@@ -184,7 +184,17 @@ int aa_device_count(int *count);
  *                               block of their pass (write-through partials), not by a launch of their own
  *   "setup_in_grad"     0|1    1 (default): the dictionary update's set-up block is block 0 of its first
  *                               gradient launch
- *   "gram_side"         0|1    Z'Z of the refresh after a weights update on the side stream (default 0) */
+ *   "gram_side"         0|1    Z'Z of the refresh after a weights update on the side stream (default 0)
+ *   "spg_tail"          0|1    1: every one-iteration dictionary update runs the whole tail of its SPG iteration
+ *                               (g_new, <d, g_new>, the BB step, the residual projection with ||res|| and the
+ *                               CONVERGED / MAX_FEVAL flags).  0 (default): the updates of aa_outer_iterations,
+ *                               and those of aa_iterate once the status record shows AA_SPG_FLAG_MAX_ITER, run
+ *                               x += lambda d alone -- nothing reads the rest there (csrc/solver.hip:
+ *                               spg_tail_needed).  Updates with stats, with more than one SPG iteration, behind
+ *                               aa_set_dictionary_inputs, of aa_dictionary_update, of the kernel form, of the
+ *                               restart slots and of multi-rank runs keep the tail whatever the value;
+ *                               aa_iterate with spg max_feval < 202 too.  (A PROJ_UNCONV of a skipped
+ *                               residual projection is, naturally, not reported.) */
 int aa_set_option(const char *name, int value);
 
 /* -------------------------------------------- stateless ops (unit-test surface) */
@@ -682,7 +692,10 @@ int aa_reduce_sparse_counts(aa_ctx *ctx, long out[2]);
  * csrc/aa_internal.h: ScalarSlot), copied to out[0..AA_SPG_SCALARS).  Layout: 0 tr, 1 tr(C HD),
  * 2 tr(M C K C'), 3 f_old, 4 f_new, 5 alpha (BB / first step), 6 alpha_set, 7 lambda,
  * 8 <d,g>, 9 <d,d>, 10 tr(D HD), 11 a1, 12 a2, 13 <d,g_new>, 14 ||res||^2, 15 ||res||_inf,
- * 16 n_feval, 17 flags, 18 projection multiplier, 19 max|P(x-g)-x|, 20 divisor of f. */
+ * 16 n_feval, 17 flags, 18 projection multiplier, 19 max|P(x-g)-x|, 20 divisor of f.
+ * After an update that skipped the SPG tail (option "spg_tail"; aa_spg_path ends in "tail:skip") 13, 14, 15
+ * and 19 are STALE -- what the latest update with a tail left --, 5 is the step length the update used, not the
+ * BB step behind it, and 17 lacks CONVERGED / MAX_FEVAL. */
 #define AA_SPG_SCALARS 21
 int aa_get_spg_scalars(aa_ctx *ctx, double *out);
 
@@ -757,6 +770,9 @@ int aa_qp_kernels(aa_ctx *ctx, int device, char *buf, int len);
  *   AA_SPG_ARRAY_Q       d' X of the last iteration (k x p; data form only)
  *   AA_SPG_ARRAY_FMEM    the line search's history f_mem[0 .. 15] (spg.py:153,198-199; entry 0 is f at the
  *                        start of the last iteration, entries beyond `memory` stay 0)
+ * After an update that skipped the SPG tail (option "spg_tail"; aa_spg_path ends in "tail:skip") AA_SPG_ARRAY_G
+ * is STALE: the buffer holds an older update's gradient, not that of the returned point (AA_SPG_ARRAY_G_PREV, _D,
+ * _GR and the others are the update's own).
  * Waits for the context's stream and side stream, launches nothing and steers nothing.  The element-wise
  * suite of the SPG step compares every kernel's output with the arrays it read
  * (tests/test_gpu_spg_step.py).  The reference has no counterpart (its arrays are NumPy locals of spg()). */
@@ -769,7 +785,8 @@ int aa_get_spg_array(aa_ctx *ctx, int which, double *out);
  * then every gradient launch ("k_grad<KP>:nb=blocks:rpb=rows per block") and every line search with its
  * template argument and grid: "k_gram_wide_pq_mfma<32>:nb=17:cpb=128;k_linesearch_fin" (fused; also
  * "k_gram_wide_pq<KP>"), "k_gram_wide<32>x2;k_scalar_stage" (data form, fuse_finalize = 0),
- * "k_gram_tall<64>x3;k_scalar_stage" (kernel form).  The string holds 511 characters: from the first entry
+ * "k_gram_tall<64>x3;k_scalar_stage" (kernel form).  An iteration that ran its tail ends with the gradient launch
+ * of g_new; one that skipped it (option "spg_tail") ends with "tail:skip" in that place.  The string holds 511 characters: from the first entry
  * that does not fit on, entries are dropped.  A host-side string: reading it launches nothing and it steers
  * nothing.  A test of one path has to know that it ran that path (tests/test_gpu_spg_step.py).  The
  * restart-slot launches are not recorded.  The reference has no counterpart (one code path).  Empty before

@@ -300,6 +300,13 @@ struct Ctx {
     long ride_count = 0;                       // ... and length
     double *ride_gather_next = nullptr;        // the next closing reduction of a projection goes here and waits (ride)
     bool weights_follow = false;               // a weights update follows this dictionary update in the same iteration
+    // Who can read the tail of a one-iteration dictionary SPG (dictionary_update: tail_needed).  loop_update: the
+    // update belongs to aa_outer_iterations / aa_iterate (aa_dictionary_update is the step-by-step entry: its
+    // scalars and arrays are read back).  loop_judged: a judge reads the SPG flags behind it; loop_spg_flags: the
+    // status record's spg_flags as the host last fetched them (run_device_loop, once per batch; 0 at the start of a
+    // loop) -- once they carry AA_SPG_FLAG_MAX_ITER no later residual projection changes what the fit reports.
+    bool loop_update = false, loop_judged = false;
+    int loop_spg_flags = 0;
     bool ride_grad_next = false;               // the next launch_grad's dot rides with the projection that follows it
 
     // data
@@ -420,6 +427,8 @@ int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, doubl
                 const aa_spg_params *sp = nullptr, int stage_after = -1,
                 const aa_spg_params *setup_sp = nullptr /* the update's set-up as block 0 */, double setup_fnorm = 0.0);
 int launch_tall_axpy_lambda(Ctx *c, double *x, const double *d);             // x += lambda * d
+// the same on the groups of 4 rows that launch_group_flags marked in d (Ctx::group_flags_fresh): the same bits
+int launch_tall_axpy_lambda_flagged(Ctx *c, double *x, const double *d, const unsigned char *flags);
 // flags[g] = 1 if any entry of rows 4g..4g+3 of the tall array compares != 0.0 (NaN does, -0.0 does not),
 // g < n_pad / 4; also zeroes the two slab counters of the gather kernel that follows
 int launch_group_flags(Ctx *c, const double *A_tall, unsigned char *flags, unsigned int *counters);
@@ -544,7 +553,7 @@ bool side_available(const Ctx *c);  // side stream + second scratch set usable (
 int side_begin(Ctx *c);            // launch_* calls go to the side stream (own scratch set) until side_end
 int side_begin_behind(Ctx *c);
 int side_end(Ctx *c);
-extern int g_proj_res_side, g_grad_side;
+extern int g_proj_res_side, g_grad_side, g_spg_tail;
 int proj_poll_multirank(Ctx *c);   // multi-rank: read the deferred overflow flag / list lengths (host sync point)   // multi-rank: row j -> wideScratch on every rank
 int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const double *alpha_dev,
                          double *out_host /* null: launches only (aa_time_kernel) */);
@@ -579,6 +588,12 @@ extern int g_fuse_finalize, g_fin_in_last, g_gram_side, g_setup_in_grad;     // 
 extern int g_pack_comm, g_pq_mfma;                                           // kernels_tall.hip
 extern int g_row_local_variant, g_row_local_split, g_row_local_acc64, g_f64_mfma;   // kernels_gemm.hip
 extern int g_reduce_sparse, g_reduce_sparse_max;                                    // kernels_gemm.hip
+// launch_reduce_rows with a flag buffer takes its flagged sequence, i.e. leaves the group flags of its operand in
+// that buffer (the condition of kernels_gemm.hip: launch_reduce_rows, restated for the callers that reuse the flags)
+inline bool reduce_rows_flags_operand(const Ctx *c)
+{
+    return g_reduce_sparse && !c->time_gemm && (c->dtype == AA_F32 || g_f64_mfma);
+}
 extern int g_qp_pass_cap, g_qp_mode, g_qp_quad_cap, g_qp_sort;               // kernels_qp.hip
 extern int g_qp_fused_order, g_qp_wave_lazy, g_qp_quad_lazy;                 // kernels_qp.hip
 extern int g_qp_overlap_tail, g_qp_live;                                     // kernels_qp.hip

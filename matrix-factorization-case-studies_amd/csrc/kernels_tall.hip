@@ -1274,6 +1274,39 @@ __global__ __launch_bounds__(256) void k_tall_axpy(double *__restrict__ x,
     if (i < elems) x[i] = x[i] + scal[SC_LAMBDA] * d[i];
 }
 
+// The same step on the aligned groups of 4 rows that k_group_flags marked in d (flags[g] != 0: the group
+// holds an entry != 0.0); block and wave map of k_group_flags, 8 groups per wave.  Every entry of an
+// unmarked group is +-0, where the dense step computes x + lambda * (+-0): x itself for a finite lambda and
+// an x that holds no -0.0 -- the dictionary is non-negative, and a zero of it is the +0.0 that fmax(., 0.0)
+// or an exact cancellation x + lambda d left -- so the marked groups are the only ones the dense step
+// changes, and on those both kernels evaluate the same expression.  (n_pad / 4 is a multiple of 8; rows < n
+// only, like the dense step.)
+template <int KP>
+__global__ __launch_bounds__(256) void k_tall_axpy_flagged(double *__restrict__ x, const double *__restrict__ d,
+                                                           const double *__restrict__ scal,
+                                                           const unsigned char *__restrict__ flags, long ngroups,
+                                                           long elems)
+{
+    constexpr int L = KP / 32;                 // pairs of entries per lane and group
+    const int lane = threadIdx.x & 63;
+    const long g0 = ((long)blockIdx.x * 4 + (threadIdx.x >> 6)) * 8;
+    if (g0 >= ngroups) return;                 // wave-uniform
+    const unsigned long long bytes = *reinterpret_cast<const unsigned long long *>(flags + g0);
+    if (bytes == 0ull) return;                 // wave-uniform
+    const double lam = scal[SC_LAMBDA];
+    for (int u = 0; u < 8; ++u) {
+        if (((bytes >> (8 * u)) & 0xffull) == 0ull) continue;
+#pragma unroll
+        for (int l = 0; l < L; ++l) {
+            const long e = (g0 + u) * (4 * KP) + 2 * (l * 64 + lane);   // a pair never straddles two rows
+            if (e >= elems) continue;
+            const double x0 = x[e], x1 = x[e + 1], d0 = d[e], d1 = d[e + 1];
+            x[e] = x0 + lam * d0;
+            x[e + 1] = x1 + lam * d1;
+        }
+    }
+}
+
 template <typename T>
 __global__ __launch_bounds__(256) void k_wide_axpy(double *__restrict__ P,
                                                    const double *__restrict__ Q,
@@ -2357,6 +2390,8 @@ int g_pack_comm = 1;            // multi-rank: small reductions ride in the tail
 int g_setup_in_grad = 1;        // the dictionary update's set-up block inside its first gradient launch (DictSetup)
 int g_gram_side = 0;            // Z'Z of the refresh after a weights update on the side stream, beside the Z'X pass
 int g_grad_side = 1;            // one SPG iteration per dictionary update: g_new, x += lambda d and the BB stage on the side stream too
+int g_spg_tail = 0;             // 1: a one-iteration dictionary update always runs the SPG tail (g_new, BB stage, residual
+                                // projection); 0: only where somebody can read it (dictionary_update: tail_needed)
 int g_proj_res_side = 1;        // the SPG's residual projection (flags only) on the side stream, beside the weights QP
 int g_proj_small = 1;           // short columns: threshold search of a projection in one kernel (k_proj_small)
 int g_fuse_finalize = 1;    // 1: the scalar stage that consumes a reduction rides in the kernel that finalizes it
@@ -2688,6 +2723,20 @@ int launch_tall_axpy_lambda(Ctx *c, double *x, const double *d)
     const long elems = c->n * c->KP;
     hipLaunchKernelGGL(k_tall_axpy, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
                        x, d, c->scalars.as<double>(), elems);
+    AA_CHECK_HIP(hipGetLastError());
+    return AA_OK;
+}
+
+int launch_tall_axpy_lambda_flagged(Ctx *c, double *x, const double *d, const unsigned char *flags)
+{
+    const long ngroups = c->n_pad / 4;
+    const dim3 grid((unsigned)((ngroups + 31) / 32));
+    if (c->KP == 32)
+        hipLaunchKernelGGL(k_tall_axpy_flagged<32>, grid, dim3(256), 0, c->stream, x, d,
+                           (const double *)c->scalars.as<double>(), flags, ngroups, c->n * c->KP);
+    else
+        hipLaunchKernelGGL(k_tall_axpy_flagged<64>, grid, dim3(256), 0, c->stream, x, d,
+                           (const double *)c->scalars.as<double>(), flags, ngroups, c->n * c->KP);
     AA_CHECK_HIP(hipGetLastError());
     return AA_OK;
 }

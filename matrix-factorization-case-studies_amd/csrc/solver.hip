@@ -333,6 +333,26 @@ static int slots_restore_P_warm(Ctx *c)
 }
 
 // ----------------------------------------------------------------- dictionary SPG
+// The tail of an SPG iteration: g_new and <d, g_new>, the BB step (spg.py:232-244), the residual projection with
+// ||res|| and the CONVERGED / MAX_FEVAL flags (spg.py:250-276).  A further SPG iteration reads all of it.  With
+// one iteration per update the next update forms its gradient from the new H and takes its first step length
+// from PROJ_ALPHA, so what is left are the readers outside the update: the caller's stats, the step-by-step
+// entries whose scalars and arrays are read back (aa_dictionary_update; updates behind
+// aa_set_dictionary_inputs), the collectives that ride with the tail (multi-rank), and the judge of a loop.  The
+// judge (iter_judge_thread0) masks CONVERGED out and ORs the rest into the sticky IterState::spg_flags, MAX_ITER
+// unless the update converged: once the host has seen MAX_ITER in the status record, a later tail can add
+// MAX_FEVAL only -- impossible while max_feval >= 202, the most evaluations one iteration makes (the start, and
+// 1 + 200 in linesearch_thread0) -- and the projection's own PROJ_UNCONV, which then reports on a projection
+// nothing needed.  aa_outer_iterations has no judge at all.
+static bool spg_tail_needed(const Ctx *c, const aa_spg_params *sp, const aa_spg_stats *st)
+{
+    if (g_spg_tail || st || sp->max_iterations > 1) return true;
+    if (c->form != AA_FORM_DATA || c->slots_aa || c->world > 1 || c->force_comm) return true;
+    if (!c->loop_update || c->dict_inputs_overridden) return true;
+    if (c->loop_judged && (sp->max_feval < 202 || !(c->loop_spg_flags & AA_SPG_FLAG_MAX_ITER))) return true;
+    return false;
+}
+
 // cost_out / cost_slot (device, nullable): where the cost after the update is recorded.
 // *cost_recorded tells the caller whether that happened inside the update (fused line search,
 // one SPG iteration) or is still to be done with launch_aa_cost.
@@ -418,6 +438,7 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
     std::vector<double> sc(SC_COUNT, 0.0);
     int n_iter = -1, flags = 0;
     bool grad_on_side = false;
+    const bool tail = spg_tail_needed(c, sp, st);
     for (int it = 0; it < sp->max_iterations; ++it) {
         n_iter = it;
         if (it == 0 && sp->alpha0 < 0.0) {                                      // spg.py:178-189
@@ -461,6 +482,24 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
             // x = x_old + lam d happens inside the gradient kernel (it reads d for <d, g_new>),
             // the BB stage (spg.py:232-244) in the last block of that kernel
             AA_CHECK(launch_wide_axpy_lambda(c, c->P.as<double>(), c->Q.as<double>(), operandT(c, c->P, c->Pw)));
+            if (!tail) {
+                // Nobody reads the tail (spg_tail_needed): the step x += lambda d is all that is left of it, on the
+                // main stream -- C K Z of the refresh after the weights update is its first reader -- and on the
+                // row groups the D'X pass flagged in d where it did (the same bits: k_tall_axpy_flagged).  No
+                // fork, nothing for refresh_after_weights to join, and the QP has the CUs to itself.  g_new, the
+                // BB scalars, ||res|| and the flags of the tail keep what an earlier update left there.
+                if (reduce_rows_flags_operand(c))
+                    AA_CHECK(launch_tall_axpy_lambda_flagged(c, x, c->Dt.as<double>(),
+                                                             c->groupFlags.as<unsigned char>()));
+                else
+                    AA_CHECK(launch_tall_axpy_lambda(c, x, c->Dt.as<double>()));
+                AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
+                // (not an SPG_NAME: the step tables of tests/test_spg_step_host.py hold the names of a whole step)
+                spg_name(c, "tail:skip");
+                std::swap(c->Gr, c->Gn);
+                std::swap(c->gk, c->gn);
+                break;
+            }
             AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
             // With one SPG iteration per update nobody on the main stream waits for g_new, the step
             // x += lambda d, the BB stage or the residual projection before the update of the
@@ -595,6 +634,7 @@ static const AaOption kOptions[] = {
     {"setup_in_grad", &g_setup_in_grad, 0, 1, true},
     {"gram_side", &g_gram_side, 0, 1, true},
     {"grad_side", &g_grad_side, 0, 1, true},
+    {"spg_tail", &g_spg_tail, 0, 1, true},
     {"pack_comm", &g_pack_comm, 0, 1, true},
 };
 
@@ -1365,7 +1405,10 @@ static int aa_enqueue_iteration(Ctx *c, const aa_spg_params *spg, const aa_qp_pa
     if (upd_dict) {
         bool recorded = false;
         c->weights_follow = upd_w;
+        c->loop_update = true;                     // who reads the SPG tail: spg_tail_needed
+        c->loop_judged = jd != nullptr;
         const int rcd = dictionary_update(c, spg, nullptr, true, cd, slot, &recorded);
+        c->loop_update = c->loop_judged = false;
         c->weights_follow = false;
         AA_CHECK(rcd);
         if (cd && !recorded) {
@@ -1471,6 +1514,7 @@ static int loop_records_begin(Ctx *c, int n_max, LoopRecords *rec)
     rec->st = c->iterState.as<IterState>();
     AA_CHECK_HIP(hipMemsetAsync(rec->slot, 0, sizeof(int), c->stream));
     AA_CHECK_HIP(hipMemsetAsync(rec->st, 0, sizeof(IterState), c->stream));
+    c->loop_spg_flags = 0;                       // the host's view of the zeroed record
     return AA_OK;
 }
 
@@ -1495,6 +1539,7 @@ static int run_device_loop(Ctx *c, const LoopRecords &rec, const aa_iter_params 
         done += batch;
         AA_CHECK_HIP(hipMemcpyAsync(&hs, rec.st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+        c->loop_spg_flags = hs.spg_flags;        // the next batch's dictionary updates consult it (spg_tail_needed)
         if (poll_multirank) AA_CHECK(proj_poll_multirank(c));
         if (hs.stop || (stop_not_definite && hs.not_definite)) break;
     }
