@@ -24,6 +24,7 @@
 #include <vector>
 
 #include "../../include/aa_hip.h"
+#include "dict_plan.h"
 
 namespace aa {
 
@@ -299,13 +300,9 @@ struct Ctx {
     double *ride_dst = nullptr;                // explicit tail content of a wide buffer (Z'Z behind Z'X): its start
     long ride_count = 0;                       // ... and length
     double *ride_gather_next = nullptr;        // the next closing reduction of a projection goes here and waits (ride)
-    bool weights_follow = false;               // a weights update follows this dictionary update in the same iteration
-    // Who can read the tail of a one-iteration dictionary SPG (dictionary_update: tail_needed).  loop_update: the
-    // update belongs to aa_outer_iterations / aa_iterate (aa_dictionary_update is the step-by-step entry: its
-    // scalars and arrays are read back).  loop_judged: a judge reads the SPG flags behind it; loop_spg_flags: the
-    // status record's spg_flags as the host last fetched them (run_device_loop, once per batch; 0 at the start of a
-    // loop) -- once they carry AA_SPG_FLAG_MAX_ITER no later residual projection changes what the fit reports.
-    bool loop_update = false, loop_judged = false;
+    // Who can read the tail of a one-iteration dictionary SPG (dict_plan.h: dict_tail_needed): the status record's
+    // spg_flags as the host last fetched them (run_device_loop, once per batch; 0 at the start of a loop) -- once
+    // they carry AA_SPG_FLAG_MAX_ITER no later residual projection changes what the fit reports.
     int loop_spg_flags = 0;
     bool ride_grad_next = false;               // the next launch_grad's dot rides with the projection that follows it
 
@@ -422,10 +419,22 @@ int tall_setup(Ctx *c);
 int launch_proj(Ctx *c, const double *x, const double *g, double a_const, int a_slot, int mode,
                 const aa_spg_params *sp = nullptr, int stage_after = -1);
 enum { PROJ_FEAS = 0, PROJ_ALPHA = 1, PROJ_DIR = 2, PROJ_RES = 3 };
-int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, double scale,
-                const double *d_for_dot /*nullable*/, int dot_slot, double *xupd = nullptr,
-                const aa_spg_params *sp = nullptr, int stage_after = -1,
-                const aa_spg_params *setup_sp = nullptr /* the update's set-up as block 0 */, double setup_fnorm = 0.0);
+// gout = (M Graw - H a) scale.  d_for_dot: <d, gout> goes to scalar slot dot_slot; xupd (needs d_for_dot):
+// x += lambda d in the same pass; stage_after >= 0 (with sp): the scalar stage that consumes <d, g> (ST_BB) runs
+// inside the finalize kernel; setup_sp: the dictionary update's set-up rides along as block 0 (DictSetup), with
+// setup_fnorm its SC_FNORM
+struct GradArgs {
+    const double *Graw;
+    double *gout;
+    const double *d_for_dot = nullptr;
+    int dot_slot = 0;
+    double *xupd = nullptr;
+    const aa_spg_params *sp = nullptr;
+    int stage_after = -1;
+    const aa_spg_params *setup_sp = nullptr;
+    double setup_fnorm = 0.0;
+};
+int launch_grad(Ctx *c, const double *H, double scale, const GradArgs &a);
 int launch_tall_axpy_lambda(Ctx *c, double *x, const double *d);             // x += lambda * d
 // the same on the groups of 4 rows that launch_group_flags marked in d (Ctx::group_flags_fresh): the same bits
 int launch_tall_axpy_lambda_flagged(Ctx *c, double *x, const double *d, const unsigned char *flags);
@@ -549,11 +558,10 @@ inline hipError_t ctx_memset(Ctx *c, void *dst, int value, size_t nbytes)
 {
     return hipMemsetAsync(dst, value, nbytes, c->stream);
 }
-bool side_available(const Ctx *c);  // side stream + second scratch set usable (single rank, fused stages)
+bool side_available(const Ctx *c);  // dict_side_available (dict_plan.h) of this context
 int side_begin(Ctx *c);            // launch_* calls go to the side stream (own scratch set) until side_end
 int side_begin_behind(Ctx *c);
 int side_end(Ctx *c);
-extern int g_proj_res_side, g_grad_side, g_spg_tail;
 int proj_poll_multirank(Ctx *c);   // multi-rank: read the deferred overflow flag / list lengths (host sync point)   // multi-rank: row j -> wideScratch on every rank
 int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const double *alpha_dev,
                          double *out_host /* null: launches only (aa_time_kernel) */);
@@ -586,6 +594,12 @@ extern int g_use_graph;                                                      // 
 extern int g_proj_mode, g_proj_small, g_proj_list_cap, g_proj_check_always;  // kernels_tall.hip
 extern int g_fuse_finalize, g_fin_in_last, g_gram_side, g_setup_in_grad;     // kernels_tall.hip
 extern int g_pack_comm, g_pq_mfma;                                           // kernels_tall.hip
+extern int g_proj_res_side, g_grad_side, g_spg_tail;                         // kernels_tall.hip
+inline DictKnobs dict_knobs()                    // the knobs dict_plan (dict_plan.h) decides by, as they are now
+{
+    return DictKnobs{g_fuse_finalize, g_setup_in_grad, g_grad_side, g_spg_tail, g_pack_comm, g_proj_mode,
+                     g_proj_res_side};
+}
 extern int g_row_local_variant, g_row_local_split, g_row_local_acc64, g_f64_mfma;   // kernels_gemm.hip
 extern int g_reduce_sparse, g_reduce_sparse_max;                                    // kernels_gemm.hip
 // launch_reduce_rows with a flag buffer takes its flagged sequence, i.e. leaves the group flags of its operand in

@@ -2391,7 +2391,7 @@ int g_setup_in_grad = 1;        // the dictionary update's set-up block inside i
 int g_gram_side = 0;            // Z'Z of the refresh after a weights update on the side stream, beside the Z'X pass
 int g_grad_side = 1;            // one SPG iteration per dictionary update: g_new, x += lambda d and the BB stage on the side stream too
 int g_spg_tail = 0;             // 1: a one-iteration dictionary update always runs the SPG tail (g_new, BB stage, residual
-                                // projection); 0: only where somebody can read it (dictionary_update: tail_needed)
+                                // projection); 0: only where somebody can read it (dict_plan.h: dict_tail_needed)
 int g_proj_res_side = 1;        // the SPG's residual projection (flags only) on the side stream, beside the weights QP
 int g_proj_small = 1;           // short columns: threshold search of a projection in one kernel (k_proj_small)
 int g_fuse_finalize = 1;    // 1: the scalar stage that consumes a reduction rides in the kernel that finalizes it
@@ -2597,8 +2597,7 @@ static void side_swap(Ctx *c)
 
 bool side_available(const Ctx *c)
 {
-    return g_proj_res_side && c->stream2 && c->proj2.p && c->evFork2 && c->world <= 1 && !c->force_comm &&
-           g_proj_mode == 0 && g_fuse_finalize;
+    return dict_side_available(dict_knobs(), c->stream2 && c->proj2.p && c->evFork2, c->world > 1 || c->force_comm);
 }
 
 int side_begin(Ctx *c)
@@ -2655,24 +2654,23 @@ void spg_name(Ctx *c, const char *fmt, ...)
     strcat(c->spg_path, item);
 }
 
-// xupd (nullable, needs d_for_dot): x += lambda d in the same pass.  stage_after >= 0 (with
-// sp): the scalar stage that consumes <d, g> (ST_BB) runs inside the finalize kernel.
-int launch_grad(Ctx *c, const double *Graw, const double *H, double *gout, double scale,
-                const double *d_for_dot, int dot_slot, double *xupd, const aa_spg_params *sp,
-                int stage_after, const aa_spg_params *setup_sp, double setup_fnorm)
+int launch_grad(Ctx *c, const double *H, double scale, const GradArgs &a)
 {
-    // setup_sp: the dictionary update's set-up rides along as block 0 (DictSetup)
+    const double *Graw = a.Graw, *d_for_dot = a.d_for_dot;
+    double *gout = a.gout, *xupd = a.xupd;
+    const aa_spg_params *sp = a.sp;
+    const int dot_slot = a.dot_slot, stage_after = a.stage_after;
     DictSetup ds;
     memset(&ds, 0, sizeof(ds));
-    if (setup_sp) {
+    if (a.setup_sp) {
         ds.on = 1;
         ds.state = c->gramState.as<double>();
         ds.trace = c->trace;
-        ds.fnorm = setup_fnorm;
+        ds.fnorm = a.setup_fnorm;
         ds.Mout = c->Mdev.as<double>();
         ds.gram = c->gramOut.as<double>();
         ds.sc = c->scalars.as<double>();
-        ds.sp = *setup_sp;
+        ds.sp = *a.setup_sp;
     }
     // 16 rows per wave and step with nothing in flight across steps: ~4 blocks per CU
     long gb = (c->n + 63) / 64;

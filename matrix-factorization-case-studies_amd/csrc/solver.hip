@@ -333,211 +333,234 @@ static int slots_restore_P_warm(Ctx *c)
 }
 
 // ----------------------------------------------------------------- dictionary SPG
-// The tail of an SPG iteration: g_new and <d, g_new>, the BB step (spg.py:232-244), the residual projection with
-// ||res|| and the CONVERGED / MAX_FEVAL flags (spg.py:250-276).  A further SPG iteration reads all of it.  With
-// one iteration per update the next update forms its gradient from the new H and takes its first step length
-// from PROJ_ALPHA, so what is left are the readers outside the update: the caller's stats, the step-by-step
-// entries whose scalars and arrays are read back (aa_dictionary_update; updates behind
-// aa_set_dictionary_inputs), the collectives that ride with the tail (multi-rank), and the judge of a loop.  The
-// judge (iter_judge_thread0) masks CONVERGED out and ORs the rest into the sticky IterState::spg_flags, MAX_ITER
-// unless the update converged: once the host has seen MAX_ITER in the status record, a later tail can add
-// MAX_FEVAL only -- impossible while max_feval >= 202, the most evaluations one iteration makes (the start, and
-// 1 + 200 in linesearch_thread0) -- and the projection's own PROJ_UNCONV, which then reports on a projection
-// nothing needed.  aa_outer_iterations has no judge at all.
-static bool spg_tail_needed(const Ctx *c, const aa_spg_params *sp, const aa_spg_stats *st)
+// What launches is decided by dict_plan (dict_plan.h) from the knobs and the facts of the call; the functions
+// below run the plan and ask nothing else.
+//
+// What the caller knows about an update.  cost_out / cost_slot (device, nullable): where the cost after the
+// update is recorded.  *cost_recorded tells the caller whether that happened inside the update (fused line
+// search, one SPG iteration) or is still to be done with launch_aa_cost.  weights_follow, loop_update,
+// loop_judged: see DictPlanIn.
+struct DictCall {
+    bool refresh = true;
+    double *cost_out = nullptr;
+    int *cost_slot = nullptr;
+    bool *cost_recorded = nullptr;
+    bool weights_follow = false, loop_update = false, loop_judged = false;
+};
+
+static DictPlanIn dict_plan_in(const Ctx *c, const aa_spg_params *sp, const aa_spg_stats *st, const DictCall &call)
 {
-    if (g_spg_tail || st || sp->max_iterations > 1) return true;
-    if (c->form != AA_FORM_DATA || c->slots_aa || c->world > 1 || c->force_comm) return true;
-    if (!c->loop_update || c->dict_inputs_overridden) return true;
-    if (c->loop_judged && (sp->max_feval < 202 || !(c->loop_spg_flags & AA_SPG_FLAG_MAX_ITER))) return true;
-    return false;
+    DictPlanIn in{};
+    in.form = c->form == AA_FORM_DATA ? (c->linear_kernel ? DictForm::data_as_kernel : DictForm::data)
+              : c->kernel.kind ? DictForm::implicit_kernel : DictForm::kernel_matrix;
+    in.slots_aa = c->slots_aa;
+    in.slots_mixed = slots_mixed(c);
+    in.multi = c->world > 1 || c->force_comm;
+    in.x_feasible = c->x_feasible;
+    in.products_valid = c->products_valid;
+    in.grams_valid = c->grams_valid;
+    in.ckz_valid = c->ckz_valid;
+    in.dict_inputs_overridden = c->dict_inputs_overridden;
+    in.stats = st != nullptr;
+    in.cost_dst = call.cost_out != nullptr;
+    in.max_iterations = sp->max_iterations;
+    in.max_feval = sp->max_feval;
+    in.alpha0_negative = sp->alpha0 < 0.0;
+    in.weights_follow = call.weights_follow;
+    in.loop_update = call.loop_update;
+    in.loop_judged = call.loop_judged;
+    in.max_iter_seen = (c->loop_spg_flags & AA_SPG_FLAG_MAX_ITER) != 0;
+    in.side_resources = c->stream2 && c->proj2.p && c->evFork2;
+    in.flags_operand = reduce_rows_flags_operand(c);
+    return in;
 }
 
-// cost_out / cost_slot (device, nullable): where the cost after the update is recorded.
-// *cost_recorded tells the caller whether that happened inside the update (fused line search,
-// one SPG iteration) or is still to be done with launch_aa_cost.
-static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, bool refresh,
-                             double *cost_out = nullptr, int *cost_slot = nullptr,
-                             bool *cost_recorded = nullptr)
+// The start (DictPlan::start): M, the scalars, f(x) and the products the first gradient reads.
+static int dict_start(Ctx *c, const DictPlan &pl, const aa_spg_params *sp)
+{
+    const double fnorm = (double)c->k;
+    if (pl.start == DictStart::fast_in_grad) return AA_OK;          // block 0 of the gradient launch does it
+    if (pl.start == DictStart::fast_setup) return launch_dict_setup(c, sp, fnorm);      // spg.py:153-157
+    const bool warm = pl.start == DictStart::warm;
+    double *x = c->Ct.as<double>();
+    double *gram = c->gramOut.as<double>();
+    // M = D Z'Z D  (archetypal_analysis.py:310,330), formed on the device
+    AA_CHECK(launch_scale_gram(c, c->Mdev.as<double>(), dev_ZtZ(c)));
+    AA_CHECK(launch_set_scalars(c, c->trace, fnorm));              // archetypal_analysis.py:265,277
+    if (pl.project_start) AA_CHECK(launch_proj(c, x, nullptr, 0.0, -1, PROJ_FEAS));
+    if (warm) {
+        AA_CHECK_HIP(hipMemcpyAsync(gram, dev_CKCt(c), (size_t)c->KP * c->KP * sizeof(double),
+                                    hipMemcpyDeviceToDevice, c->stream));
+    } else if (pl.data) {
+        if (pl.save_restore_P) AA_CHECK(slots_save_P(c));
+        AA_CHECK(launch_reduce_rows(c, x, c->P.as<double>(), operandT(c, c->P, c->Pw)));
+        if (pl.save_restore_P) AA_CHECK(slots_restore_P_warm(c));
+        AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), gram));
+    } else {
+        if (pl.implicit) {
+            AA_CHECK(kernel_kv(c, x, c->Gr.as<double>()));
+        } else {
+            AA_CHECK(launch_reduce_rows(c, x, c->wideScratch.as<double>(), nullptr));
+            AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gr.as<double>()));
+        }
+        AA_CHECK(launch_gram_tall(c, c->Gr.as<double>(), x, gram));
+    }
+    AA_CHECK(launch_tall_dot_scaled(c, x, c->H.as<double>(), c->alphaDev.as<double>(), SC_S1));
+    AA_CHECK(launch_scalar_stage(c, ST_INIT_F, sp, 0));                         // spg.py:156
+    // the slots that are in the middle of their fits start this update the way they always do
+    if (pl.warm_slots_setup) AA_CHECK(launch_dict_setup(c, sp, fnorm, slots_all_mask(c) & ~c->slots_cold));
+    if (pl.data && !warm) AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));
+    return AA_OK;
+}
+
+// One SPG iteration up to the accepted step length: the direction d = P(x - alpha g) - x, its products and the
+// line search.
+static int dict_direction_linesearch(Ctx *c, const DictPlan &pl, const aa_spg_params *sp, const DictCall &call)
+{
+    const int KP = c->KP;
+    const size_t GS = (size_t)KP * KP;
+    double *x = c->Ct.as<double>();
+    double *gram = c->gramOut.as<double>();
+    // multi-rank: the closing reduction of this projection (<d,g>, <d,d>, ...: read by the line search
+    // only) rides with the all-reduce of Q = D'X
+    if (pl.ride_dir) c->ride_gather_next = c->Q.as<double>() + (size_t)KP * c->p_pad;
+    AA_CHECK(launch_proj(c, x, c->gk.as<double>(), 0.0, SC_ALPHA, PROJ_DIR));   // spg.py:191-194,206
+    if (pl.data) {
+        // d = P(x - alpha g) - x is zero outside supp(x) and supp(P(.)): a few hundred rows
+        AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, false, &c->groupFlags));
+        if (pl.line_search == DictLineSearch::fused) {
+            // (P Q'), (Q Q'), the line search, the Gram of the accepted point and -- with one
+            // SPG iteration per update -- the cost after the update: one launch
+            AA_CHECK(launch_linesearch_fused(c, sp, pl.record_cost ? call.cost_out : nullptr,
+                                             pl.record_cost ? call.cost_slot : nullptr));
+            if (pl.record_cost && call.cost_recorded) *call.cost_recorded = true;
+        } else {
+            AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->Q.as<double>(), gram + GS));
+            AA_CHECK(launch_gram_wide(c, c->Q.as<double>(), c->Q.as<double>(), gram + 2 * GS));
+            AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 1));
+            SPG_NAME("k_gram_wide<%d>x2;k_scalar_stage", KP);
+        }
+        return AA_OK;
+    }
+    if (pl.implicit) {
+        AA_CHECK(kernel_kv(c, c->Dt.as<double>(), c->Gn.as<double>()));          // (D K)' = K D'
+    } else {
+        AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->wideScratch.as<double>(), nullptr, false,
+                                    &c->groupFlags));
+        AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gn.as<double>()));
+    }
+    AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), x, gram + GS));
+    AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), c->Dt.as<double>(), gram + 2 * GS));
+    AA_CHECK(launch_gram_tall(c, c->Gr.as<double>(), c->Dt.as<double>(), gram + 3 * GS));
+    AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 0));
+    SPG_NAME("k_gram_tall<%d>x3;k_scalar_stage", KP);
+    return AA_OK;
+}
+
+// The step x += lambda d and the tail of the iteration (DictPlan::tail): g_new with <d, g_new>, the BB stage
+// (spg.py:232-244) and the residual projection (spg.py:250-276).  Leaves the new products and gradient in Gr, gk.
+static int dict_tail(Ctx *c, const DictPlan &pl, const aa_spg_params *sp, double gscale)
+{
+    const int KP = c->KP;
+    double *x = c->Ct.as<double>();
+    GradArgs g{pl.data ? c->Gn.as<double>() : c->Gr.as<double>(), c->gn.as<double>()};
+    g.d_for_dot = c->Dt.as<double>();
+    g.dot_slot = SC_DGN;
+    g.sp = sp;
+    g.stage_after = ST_BB;
+    if (pl.data) {
+        AA_CHECK(launch_wide_axpy_lambda(c, c->P.as<double>(), c->Q.as<double>(), operandT(c, c->P, c->Pw)));
+        if (pl.tail_skipped()) {
+            // Nobody reads the tail (dict_tail_needed): the step x += lambda d is all that is left of it, on the
+            // main stream -- C K Z of the refresh after the weights update is its first reader -- and on the
+            // row groups the D'X pass flagged in d where it did (the same bits: k_tall_axpy_flagged).  No
+            // fork, nothing for refresh_after_weights to join, and the QP has the CUs to itself.  g_new, the
+            // BB scalars, ||res|| and the flags of the tail keep what an earlier update left there.
+            if (pl.tail == DictTail::skip_flagged)
+                AA_CHECK(launch_tall_axpy_lambda_flagged(c, x, c->Dt.as<double>(), c->groupFlags.as<unsigned char>()));
+            else
+                AA_CHECK(launch_tall_axpy_lambda(c, x, c->Dt.as<double>()));
+            AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
+            // (not an SPG_NAME: the step tables of tests/test_spg_step_host.py hold the names of a whole step)
+            spg_name(c, "tail:skip");
+            std::swap(c->Gr, c->Gn);
+            std::swap(c->gk, c->gn);
+            return AA_OK;
+        }
+        AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
+        // With one SPG iteration per update nobody on the main stream waits for g_new, the step
+        // x += lambda d, the BB stage or the residual projection before the update of the
+        // weights has run (the QP reads C XX' and the Gram of the accepted point only): the whole
+        // tail of the SPG iteration goes to the side stream and runs beside the QP (round 4:
+        // 36 + 14 us of gradient kernel and finalize step off the critical path).  Joined in
+        // refresh_after_weights before H = X (X'Z)' is overwritten (the gradient reads the old
+        // H) and before C K Z is formed from the updated C.
+        if (pl.tail == DictTail::side_whole) AA_CHECK(side_begin(c));
+        // multi-rank: <d, g_new> rides with the first reduction of the residual projection below
+        if (pl.ride_grad) c->ride_grad_next = true;
+        // x = x_old + lam d happens inside the gradient kernel (it reads d for <d, g_new>),
+        // the BB stage in the last block of that kernel
+        g.xupd = x;
+    } else {
+        AA_CHECK(launch_tall_axpy_lambda(c, x, c->Dt.as<double>()));            // x = x_old + lam d
+        AA_CHECK(launch_tall_axpy_lambda(c, c->Gr.as<double>(), c->Gn.as<double>()));
+    }
+    AA_CHECK(launch_grad(c, c->H.as<double>(), gscale, g));
+    // multi-rank, a weights update next: the closing sums of the residual projection (convergence flags
+    // only: read by the judge behind the weights update) wait for the Z'X all-reduce and ride behind Z'Z
+    if (pl.ride_res) c->ride_gather_next = c->ZtX.as<double>() + (size_t)KP * c->p_pad + (size_t)KP * KP;
+    // with one SPG iteration per update nobody waits for the flags: side stream
+    if (pl.tail == DictTail::side_whole) {
+        const int rc = launch_proj(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV);
+        AA_CHECK(side_end(c));
+        AA_CHECK(rc);
+    } else if (pl.tail == DictTail::side_proj)
+        AA_CHECK(launch_proj_side(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV));
+    else
+        AA_CHECK(launch_proj(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV));
+    if (pl.data) std::swap(c->Gr, c->Gn);
+    std::swap(c->gk, c->gn);
+    return AA_OK;
+}
+
+static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, const DictCall &call)
 {
     AA_REQUIRE(c->have_state && (c->grams_valid || c->dict_inputs_overridden), AA_ERR_STATE,
                "dictionary_update needs prepare() or set_dictionary_inputs() first");
     AA_REQUIRE(sp->max_iterations >= 1, AA_ERR_ARG, "spg max_iterations must be >= 1");
     AA_REQUIRE(sp->memory <= 16, AA_ERR_ARG,
                "spg memory = %d exceeds the HIP backend limit of 16", sp->memory);
-    const int k = c->k, KP = c->KP;
-    const bool data = c->form == AA_FORM_DATA;
-    if (cost_recorded) *cost_recorded = false;
+    const DictPlan pl = dict_plan(dict_knobs(), dict_plan_in(c, sp, st, call));
+    if (call.cost_recorded) *call.cost_recorded = false;
     AA_CHECK(join_side(c));
 
     double *x = c->Ct.as<double>();
-    double *gram = c->gramOut.as<double>();
-    const size_t GS = (size_t)KP * KP;
-    // the data form divides the gradient by n (:297), the kernel form by k (:288); a data matrix
-    // standing in for the kernel K = X X' (aa_set_linear_kernel) follows the kernel form
-    const double gscale = (data && !c->linear_kernel) ? 1.0 / (double)c->n_global : 1.0 / (double)k;
-
-    // spg.py:148 projects the start point.  A dictionary that came out of our own update
-    // (x_old + lambda d, a convex combination of simplex points) is feasible to rounding,
-    // and projecting it would move it by ~1e-17: skipped.  Caller-supplied factors are
-    // always projected.
-    // The same holds for its products: CX (P) and C XX' / C K (Gr) computed by the
-    // previous update's refresh (archetypal_analysis.py:618-619) are the f / gradient
-    // ingredients of this one (spg.py:156,176) -- the weights update in between does not
-    // touch the dictionary -- so two passes over X are saved (`warm`).
-    const bool warm = c->x_feasible && c->products_valid;
-    // fused small stages (fewer, fatter launches; aa_set_option("fuse_finalize", 0) restores the
-    // one-kernel-per-step sequence): with everything the update needs already in the Gram
-    // state, one block sets up M, the scalars and f(x)
-    const bool fused = data && g_fuse_finalize;
-    const bool fast = fused && warm && c->grams_valid && c->ckz_valid && !c->dict_inputs_overridden;
-    // (single fit: the set-up block rides in the gradient launch below, beside its row blocks)
-    const bool setup_in_grad = fast && g_setup_in_grad && !c->slots_aa;
+    const double gscale = 1.0 / (pl.scale_by_n ? (double)c->n_global : (double)c->k);
     c->spg_path[0] = 0;
     c->spg_path_full = false;
-    if (setup_in_grad) SPG_NAME("fast:in_grad");
-    else if (fast) SPG_NAME("fast:k_dict_setup");
-    else if (warm) SPG_NAME("warm");
+    if (pl.start == DictStart::fast_in_grad) SPG_NAME("fast:in_grad");
+    else if (pl.start == DictStart::fast_setup) SPG_NAME("fast:k_dict_setup");
+    else if (pl.start == DictStart::warm) SPG_NAME("warm");
     else SPG_NAME("cold");
-    if (fast) {
-        if (!setup_in_grad) AA_CHECK(launch_dict_setup(c, sp, (double)k));      // spg.py:153-157
-    } else {
-        // M = D Z'Z D  (archetypal_analysis.py:310,330), formed on the device
-        AA_CHECK(launch_scale_gram(c, c->Mdev.as<double>(), dev_ZtZ(c)));
-        AA_CHECK(launch_set_scalars(c, c->trace, (double)k));   // archetypal_analysis.py:265,277
-        if (!c->x_feasible) AA_CHECK(launch_proj(c, x, nullptr, 0.0, -1, PROJ_FEAS));
-        if (!warm) {
-            if (data) {
-                const bool mixed = slots_mixed(c);
-                if (mixed) AA_CHECK(slots_save_P(c));
-                AA_CHECK(launch_reduce_rows(c, x, c->P.as<double>(), operandT(c, c->P, c->Pw)));
-                if (mixed) AA_CHECK(slots_restore_P_warm(c));
-                AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->P.as<double>(), gram));
-            } else {
-                if (c->kernel.kind) {
-                    AA_CHECK(kernel_kv(c, x, c->Gr.as<double>()));
-                } else {
-                    AA_CHECK(launch_reduce_rows(c, x, c->wideScratch.as<double>(), nullptr));
-                    AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gr.as<double>()));
-                }
-                AA_CHECK(launch_gram_tall(c, c->Gr.as<double>(), x, gram));
-            }
-        } else {
-            AA_CHECK_HIP(hipMemcpyAsync(gram, dev_CKCt(c), GS * sizeof(double), hipMemcpyDeviceToDevice, c->stream));
-        }
-        AA_CHECK(launch_tall_dot_scaled(c, x, c->H.as<double>(), c->alphaDev.as<double>(), SC_S1));
-        AA_CHECK(launch_scalar_stage(c, ST_INIT_F, sp, 0));                     // spg.py:156
-        // the slots that are in the middle of their fits start this update the way they always do
-        if (slots_mixed(c)) AA_CHECK(launch_dict_setup(c, sp, (double)k, slots_all_mask(c) & ~c->slots_cold));
-        if (data && !warm) AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gr.as<double>()));
-    }
+    AA_CHECK(dict_start(c, pl, sp));
     c->products_valid = false;
-    AA_CHECK(launch_grad(c, c->Gr.as<double>(), c->H.as<double>(), c->gk.as<double>(), gscale, nullptr, 0, nullptr,
-                         nullptr, -1, setup_in_grad ? sp : nullptr, (double)k));
+    GradArgs g0{c->Gr.as<double>(), c->gk.as<double>()};
+    if (pl.start == DictStart::fast_in_grad) {
+        g0.setup_sp = sp;
+        g0.setup_fnorm = (double)c->k;
+    }
+    AA_CHECK(launch_grad(c, c->H.as<double>(), gscale, g0));
 
     std::vector<double> sc(SC_COUNT, 0.0);
     int n_iter = -1, flags = 0;
-    bool grad_on_side = false;
-    const bool tail = spg_tail_needed(c, sp, st);
     for (int it = 0; it < sp->max_iterations; ++it) {
         n_iter = it;
-        if (it == 0 && sp->alpha0 < 0.0) {                                      // spg.py:178-189
+        if (it == 0 && pl.alpha_first)                                          // spg.py:178-189
             AA_CHECK(launch_proj(c, x, c->gk.as<double>(), 1.0, -1, PROJ_ALPHA, sp, ST_ALPHA));
-        }
-        // multi-rank: the closing reduction of this projection (<d,g>, <d,d>, ...: read by the line search
-        // only) rides with the all-reduce of Q = D'X
-        const bool multi = c->world > 1 || c->force_comm;
-        if (multi && g_pack_comm && data && !c->slots_aa) c->ride_gather_next = c->Q.as<double>() + (size_t)KP * c->p_pad;
-        AA_CHECK(launch_proj(c, x, c->gk.as<double>(), 0.0, SC_ALPHA, PROJ_DIR)); // spg.py:191-194,206
-        if (data) {
-            // d = P(x - alpha g) - x is zero outside supp(x) and supp(P(.)): a few hundred rows
-            AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->Q.as<double>(), nullptr, false, &c->groupFlags));
-            if (fused) {
-                // (P Q'), (Q Q'), the line search, the Gram of the accepted point and -- with one
-                // SPG iteration per update -- the cost after the update: one launch
-                const bool rec = cost_out && sp->max_iterations == 1;
-                AA_CHECK(launch_linesearch_fused(c, sp, rec ? cost_out : nullptr, rec ? cost_slot : nullptr));
-                if (rec && cost_recorded) *cost_recorded = true;
-            } else {
-                AA_CHECK(launch_gram_wide(c, c->P.as<double>(), c->Q.as<double>(), gram + GS));
-                AA_CHECK(launch_gram_wide(c, c->Q.as<double>(), c->Q.as<double>(), gram + 2 * GS));
-                AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 1));
-                SPG_NAME("k_gram_wide<%d>x2;k_scalar_stage", KP);
-            }
-        } else {
-            if (c->kernel.kind) {
-                AA_CHECK(kernel_kv(c, c->Dt.as<double>(), c->Gn.as<double>()));  // (D K)' = K D'
-            } else {
-                AA_CHECK(launch_reduce_rows(c, c->Dt.as<double>(), c->wideScratch.as<double>(), nullptr, false,
-                                            &c->groupFlags));
-                AA_CHECK(launch_transpose_wide_to_tall(c, c->wideScratch.as<double>(), c->Gn.as<double>()));
-            }
-            AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), x, gram + GS));
-            AA_CHECK(launch_gram_tall(c, c->Gn.as<double>(), c->Dt.as<double>(), gram + 2 * GS));
-            AA_CHECK(launch_gram_tall(c, c->Gr.as<double>(), c->Dt.as<double>(), gram + 3 * GS));
-            AA_CHECK(launch_scalar_stage(c, ST_LINESEARCH, sp, 0));
-            SPG_NAME("k_gram_tall<%d>x3;k_scalar_stage", KP);
-        }
-        if (data) {
-            // x = x_old + lam d happens inside the gradient kernel (it reads d for <d, g_new>),
-            // the BB stage (spg.py:232-244) in the last block of that kernel
-            AA_CHECK(launch_wide_axpy_lambda(c, c->P.as<double>(), c->Q.as<double>(), operandT(c, c->P, c->Pw)));
-            if (!tail) {
-                // Nobody reads the tail (spg_tail_needed): the step x += lambda d is all that is left of it, on the
-                // main stream -- C K Z of the refresh after the weights update is its first reader -- and on the
-                // row groups the D'X pass flagged in d where it did (the same bits: k_tall_axpy_flagged).  No
-                // fork, nothing for refresh_after_weights to join, and the QP has the CUs to itself.  g_new, the
-                // BB scalars, ||res|| and the flags of the tail keep what an earlier update left there.
-                if (reduce_rows_flags_operand(c))
-                    AA_CHECK(launch_tall_axpy_lambda_flagged(c, x, c->Dt.as<double>(),
-                                                             c->groupFlags.as<unsigned char>()));
-                else
-                    AA_CHECK(launch_tall_axpy_lambda(c, x, c->Dt.as<double>()));
-                AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
-                // (not an SPG_NAME: the step tables of tests/test_spg_step_host.py hold the names of a whole step)
-                spg_name(c, "tail:skip");
-                std::swap(c->Gr, c->Gn);
-                std::swap(c->gk, c->gn);
-                break;
-            }
-            AA_CHECK(launch_row_local(c, operandT(c, c->P, c->Pw), c->Gn.as<double>()));
-            // With one SPG iteration per update nobody on the main stream waits for g_new, the step
-            // x += lambda d, the BB stage or the residual projection before the update of the
-            // weights has run (the QP reads C XX' and the Gram of the accepted point only): the whole
-            // tail of the SPG iteration goes to the side stream and runs beside the QP (round 4:
-            // 36 + 14 us of gradient kernel and finalize step off the critical path).  Joined in
-            // refresh_after_weights before H = X (X'Z)' is overwritten (the gradient reads the old
-            // H) and before C K Z is formed from the updated C.
-            grad_on_side = g_grad_side && sp->max_iterations == 1 && !st && side_available(c);
-            if (grad_on_side) AA_CHECK(side_begin(c));
-            // multi-rank: <d, g_new> rides with the first reduction of the residual projection below
-            if (multi && g_pack_comm && !c->slots_aa && g_proj_mode == 0 && g_fuse_finalize) c->ride_grad_next = true;
-            AA_CHECK(launch_grad(c, c->Gn.as<double>(), c->H.as<double>(), c->gn.as<double>(), gscale,
-                                 c->Dt.as<double>(), SC_DGN, x, sp, ST_BB));
-        } else {
-            AA_CHECK(launch_tall_axpy_lambda(c, x, c->Dt.as<double>()));        // x = x_old + lam d
-            AA_CHECK(launch_tall_axpy_lambda(c, c->Gr.as<double>(), c->Gn.as<double>()));
-            AA_CHECK(launch_grad(c, c->Gr.as<double>(), c->H.as<double>(), c->gn.as<double>(), gscale,
-                                 c->Dt.as<double>(), SC_DGN, nullptr, sp, ST_BB));
-        }
-        // multi-rank, a weights update next: the closing sums of the residual projection (convergence flags
-        // only: read by the judge behind the weights update) wait for the Z'X all-reduce and ride behind Z'Z
-        if (multi && g_pack_comm && data && !c->slots_aa && c->weights_follow && sp->max_iterations == 1 && !st &&
-            g_fuse_finalize)
-            c->ride_gather_next = c->ZtX.as<double>() + (size_t)KP * c->p_pad + (size_t)KP * KP;
-        // spg.py:250-276; with one SPG iteration per update nobody waits for the flags: side stream
-        if (grad_on_side) {
-            const int rc = launch_proj(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV);
-            AA_CHECK(side_end(c));
-            AA_CHECK(rc);
-        } else if (sp->max_iterations == 1 && !st && data)
-            AA_CHECK(launch_proj_side(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV));
-        else
-            AA_CHECK(launch_proj(c, x, c->gn.as<double>(), 1.0, -1, PROJ_RES, sp, ST_CONV));
-        if (data) std::swap(c->Gr, c->Gn);
-        std::swap(c->gk, c->gn);
-        // the host needs the flags only to decide on a further iteration or to report
-        if (st || it + 1 < sp->max_iterations) {
+        AA_CHECK(dict_direction_linesearch(c, pl, sp, call));
+        AA_CHECK(dict_tail(c, pl, sp, gscale));
+        if (pl.tail_skipped()) break;
+        if (pl.read_back(it)) {
             AA_CHECK_HIP(hipMemcpyAsync(sc.data(), c->scalars.p, SC_COUNT * sizeof(double),
                                         hipMemcpyDeviceToHost, c->stream));
             AA_CHECK_HIP(hipStreamSynchronize(c->stream));
@@ -556,7 +579,7 @@ static int dictionary_update(Ctx *c, const aa_spg_params *sp, aa_spg_stats *st, 
         st->res_norm = sqrt(sc[SC_RES2]);
     }
     c->x_feasible = true;
-    if (refresh) AA_CHECK(refresh_after_dictionary(c, false, fused));
+    if (call.refresh) AA_CHECK(refresh_after_dictionary(c, false, pl.ckct_done));
     return AA_OK;
 }
 
@@ -1375,7 +1398,7 @@ int aa_dictionary_update(aa_ctx *h, const aa_spg_params *params, aa_spg_stats *s
 {
     AA_REQUIRE(h && params, AA_ERR_ARG, "null argument");
     AA_CHECK_HIP(hipSetDevice(h->c.device));
-    return dictionary_update(&h->c, params, stats, true);
+    return dictionary_update(&h->c, params, stats, DictCall{});
 }
 
 int aa_weights_update(aa_ctx *h, const aa_qp_params *params, aa_qp_stats *stats)
@@ -1404,13 +1427,14 @@ static int aa_enqueue_iteration(Ctx *c, const aa_spg_params *spg, const aa_qp_pa
     }
     if (upd_dict) {
         bool recorded = false;
-        c->weights_follow = upd_w;
-        c->loop_update = true;                     // who reads the SPG tail: spg_tail_needed
-        c->loop_judged = jd != nullptr;
-        const int rcd = dictionary_update(c, spg, nullptr, true, cd, slot, &recorded);
-        c->loop_update = c->loop_judged = false;
-        c->weights_follow = false;
-        AA_CHECK(rcd);
+        DictCall call;
+        call.cost_out = cd;
+        call.cost_slot = slot;
+        call.cost_recorded = &recorded;
+        call.weights_follow = upd_w;
+        call.loop_update = true;                   // who reads the SPG tail: dict_tail_needed
+        call.loop_judged = jd != nullptr;
+        AA_CHECK(dictionary_update(c, spg, nullptr, call));
         if (cd && !recorded) {
             AA_CHECK(ensure_ckz(c));
             AA_CHECK(launch_aa_cost(c, cd, slot));
@@ -1539,7 +1563,7 @@ static int run_device_loop(Ctx *c, const LoopRecords &rec, const aa_iter_params 
         done += batch;
         AA_CHECK_HIP(hipMemcpyAsync(&hs, rec.st, sizeof(hs), hipMemcpyDeviceToHost, c->stream));
         AA_CHECK_HIP(hipStreamSynchronize(c->stream));
-        c->loop_spg_flags = hs.spg_flags;        // the next batch's dictionary updates consult it (spg_tail_needed)
+        c->loop_spg_flags = hs.spg_flags;        // the next batch's dictionary updates consult it (dict_tail_needed)
         if (poll_multirank) AA_CHECK(proj_poll_multirank(c));
         if (hs.stop || (stop_not_definite && hs.not_definite)) break;
     }
@@ -2196,6 +2220,10 @@ int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
     // the rule of every slot's judge; iteration, initial cost and status are the slot's own
     const LoopJudge slots_judge = loop_judge(&c->slots_ip, 0, 0.0, nullptr, 1);
     bool recorded = false;
+    DictCall call;
+    call.cost_out = c->slotCosts.as<double>();
+    call.cost_slot = c->slotCounters.as<int>();
+    call.cost_recorded = &recorded;
     for (int it = 0; it < n_iters; ++it) {
         if (c->slots_ip.delta != 0.0) {           // archetypal_analysis.py:590-609, once per slot
             AA_CHECK(ensure_ckz(c));
@@ -2205,8 +2233,7 @@ int aa_slots_run(aa_ctx *h, int n_iters, aa_slot_status *status)
             c->x_feasible = false;
             c->products_valid = false;
         }
-        AA_CHECK(dictionary_update(c, &c->slots_sp, nullptr, true, c->slotCosts.as<double>(),
-                                   c->slotCounters.as<int>(), &recorded));
+        AA_CHECK(dictionary_update(c, &c->slots_sp, nullptr, call));
         AA_REQUIRE(recorded, AA_ERR_STATE, "AA slots: the fused line search did not record the cost");
         c->slots_cold = 0;
         c->slots_cold_cols = 0xffffffffu;

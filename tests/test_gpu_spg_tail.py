@@ -1,4 +1,4 @@
-"""The SPG tail of a one-iteration dictionary update (option spg_tail; csrc/solver.hip: spg_tail_needed).
+"""The SPG tail of a one-iteration dictionary update (option spg_tail; csrc/dict_plan.h: dict_tail_needed).
 
 With one SPG iteration per update, g_new, <d, g_new>, the BB step and the residual projection with its
 CONVERGED / MAX_FEVAL flags have no reader in aa_outer_iterations, and in aa_iterate none once the status record
