@@ -238,8 +238,8 @@ int aa_ctx_p2p_init(aa_ctx *ctx, const void *handles, int rank, int world);
  * bench.py for the barrier + max-over-ranks timing); op: 0 = sum, 1 = max. */
 int aa_ctx_allreduce_host(aa_ctx *ctx, double *buf, int count, int op);
 
-/* Installing data.  Eleven entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
- * aa_set_data_rows_affine, aa_set_data_rows_model, aa_set_data_take, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
+/* Installing data.  Twelve entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
+ * aa_set_data_rows_affine, aa_set_data_rows_model, aa_set_data_take, aa_set_data_projected, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
  * the _resident forms of the last two.  Every one of them ("an install") first checks its arguments -- a call it
  * refuses has not touched ctx, which keeps the data it had -- and then replaces everything that belonged to the
  * previous matrix: the form and the kind of implicit kernel (none for a stored matrix), aa_set_linear_kernel, the
@@ -374,6 +374,34 @@ int aa_set_data_rows_model(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, 
  * launched or released: a bad one is AA_ERR_ARG like any other bad argument of an install, and the message names
  * the first. */
 int aa_set_data_take(aa_ctx *ctx, const aa_ctx *owner, const long *idx, long n);
+
+/* PCA of resident data (the EOF / PC input of bin/run_jra55_pca_gpnh.py and bin/run_jra55_pca_aa.py, which
+ * `run_pca` of notebooks/hadisst_pca.ipynb computes with sklearn.decomposition.PCA on the host): the Gram matrix of
+ * the centred matrix with itself, for one host eigen-solve of the smaller side, and the projection of row blocks
+ * onto the components, installed as a new block.  Both contractions on v_mfma_f64_16x16x4_f64
+ * (csrc/kernels_pca.hip), float64 arithmetic in both context dtypes: elements are widened on load and
+ * Xc[r][j] = (double)X[r][j] - shift[j] is one float64 subtraction, the rounding `Xd - m` makes in NumPy.
+ *
+ * aa_data_gram: side AA_GRAM_ROWS: G = Xc Xc' (n x n, k_gram_rows); AA_GRAM_COLS: G = Xc' Xc (p x p, k_gram_cols).
+ *   shift: p host doubles, or NULL for no centring.  out: d x d host doubles with leading dimension ldo, the whole
+ *   matrix; out[i][j] and out[j][i] are the same bits (only the 64 x 64 tiles with j >= i are computed, and both
+ *   places are written from the one value).  How the contraction is split is decided by csrc/gram_plan.h from the
+ *   side, the shape and the compute units; the splits are added in ascending order by a finish kernel, no atomics:
+ *   two calls return the same bits.  Data form with a stored matrix (AA_ERR_STATE otherwise), single rank,
+ *   d <= 8192 (AA_ERR_ARG above: the result goes through one dense eigen-solve on the host).
+ * aa_set_data_projected: an install ("installing data" above): ctx receives the n x q matrix
+ *     Y[r][i] = sum_j ((double)X[row0 + r][j] - shift[j]) V[i][j]
+ *   from owner's resident DATA matrix (k_project_rows).  V: q x p host doubles (leading dimension ldv),
+ *   1 <= q <= AA_MAX_PROJECTED; shift: p host doubles or NULL.  Sums in float64 over ascending j, rounded once to
+ *   ctx's element type.  The data types are equal, or the owner is float32 and ctx float64.  Otherwise the
+ *   preconditions and refusals of aa_set_data_rows; a non-finite entry of V or shift is AA_ERR_ARG before anything
+ *   of ctx is released. */
+#define AA_GRAM_ROWS 0
+#define AA_GRAM_COLS 1
+#define AA_MAX_PROJECTED 256
+int aa_data_gram(aa_ctx *ctx, int side, const double *shift, double *out, long ldo);
+int aa_set_data_projected(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, int q, const double *V, long ldv,
+                          const double *shift);
 
 /* KernelAA on the implicit linear kernel K = X X' (SURVEY 8(f4)): with `on` != 0 the resident
  * DATA matrix X (n x p) stands in for the n x n kernel matrix of _iterate_kernel_aa
@@ -721,6 +749,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * rows, 16 = the squared-deviation form of aa_data_grouped_sqdev (rows labelled r mod 12), both with their finish
  * kernel and without the copies; 17 = the model copy of aa_set_data_rows_model in its anomalies form (a 12-row shift
  * table and the trend) from the context's own matrix into a scratch copy; a stored data matrix is all they need.
+ * 18 / 19 = the Gram matrix of aa_data_gram by rows / by columns (uncentred: a zero shift table costs the same) with
+ * its finish kernel where gram_plan splits, without the copy to the host (the side's d <= 8192); 20 = the projection
+ * of aa_set_data_projected onto 167 components (a zero V) from the context's own matrix into a scratch block of the
+ * context's element type; a stored data matrix is all they need.
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

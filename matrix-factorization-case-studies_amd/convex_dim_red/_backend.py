@@ -18,6 +18,9 @@ import numpy as np
 AA_F32, AA_F64 = 0, 1
 FORM_DATA, FORM_KERNEL = 0, 1
 MAX_K = 64
+GRAM_SIDES = ("rows", "cols")    # AA_GRAM_ROWS, AA_GRAM_COLS
+GRAM_MAX_D = 8192                # largest Gram matrix aa_data_gram forms (it goes through one host eigen-solve)
+MAX_PROJECTED = 256              # AA_MAX_PROJECTED: most directions of aa_set_data_projected
 DIAG_KINDS = ("given", "ones", "poly", "linear")     # AA_DIAG_*: where aa_kernel_sample_residuals takes kappa(y, y) from
 
 SPG_FLAG_CONVERGED = 1
@@ -128,6 +131,9 @@ _SIGNATURES = {
     "aa_data_grouped_sqdev": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _ip, _dp, ctypes.c_int, _dp]),
     "aa_set_data_rows_model": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _ip, _dp, _dp, _dp,
                                               _dp, _dp]),
+    "aa_data_gram": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_long]),
+    "aa_set_data_projected": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _dp, ctypes.c_long,
+                                             _dp]),
     "aa_set_data_weighted": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_long, ctypes.c_long, ctypes.c_long,
                                             _dp, ctypes.c_long, ctypes.c_long,
                                             ctypes.POINTER(ctypes.c_ubyte), ctypes.POINTER(ctypes.c_long)]),
@@ -667,6 +673,39 @@ class Context(object):
         _check(self.lib.aa_data_grouped_sqdev(self.h, A.shape[0], _ptr(A), groups.ctypes.data_as(_ip), _ptr(centre),
                                               centre.shape[0], _ptr(out)))
         return out
+
+    def data_gram(self, side, shift=None):
+        """The Gram matrix of the resident data matrix, centred by ``shift`` (one value per column; None: not
+        centred), with itself (aa_data_gram): ``side='rows'`` -- ``Xc @ Xc.T`` (n, n); ``'cols'`` -- ``Xc.T @ Xc``
+        (p, p).  float64 on the f64 matrix cores in both context dtypes, exactly symmetric, the same bits on every
+        call; the side's size is at most ``GRAM_MAX_D``."""
+        if side not in GRAM_SIDES:
+            raise ValueError("side must be one of %r; got %r" % (GRAM_SIDES, side))
+        if shift is not None:
+            shift = _c64(shift)
+            if shift.shape != (self.p,):
+                raise ValueError("shift: %d values expected, one per column; got shape %r" % (self.p, shift.shape))
+        d = self.n if side == "rows" else self.p
+        out = np.empty((d, d))
+        _check(self.lib.aa_data_gram(self.h, GRAM_SIDES.index(side), None if shift is None else _ptr(shift),
+                                     _ptr(out), d))
+        return out
+
+    def set_data_projected(self, owner, row0, n, V, shift=None):
+        """``(owner[row0:row0 + n] - shift) @ V.T`` becomes this context's data matrix (aa_set_data_projected):
+        ``V`` is ``(q, p)``, ``q <= MAX_PROJECTED``; float64 sums on the f64 matrix cores, one rounding to this
+        context's dtype.  A float32 owner may feed a float64 context."""
+        V = _c64(V)
+        if V.ndim != 2 or V.shape[1] != owner.p:
+            raise ValueError("V: a (q, %d) matrix expected, one column per column of the owner; got shape %r"
+                             % (owner.p, V.shape))
+        if shift is not None:
+            shift = _c64(shift)
+            if shift.shape != (owner.p,):
+                raise ValueError("shift: %d values expected, one per column; got shape %r" % (owner.p, shift.shape))
+        _check(self.lib.aa_set_data_projected(self.h, owner.h, int(row0), int(n), V.shape[0], _ptr(V), V.shape[1],
+                                              None if shift is None else _ptr(shift)))
+        self._adopt(n, V.shape[0])
 
     def set_linear_kernel(self, on):
         """The resident data matrix X stands in for the kernel K = X X' of KernelAA

@@ -413,6 +413,21 @@ class DeviceData(object):
         return DeviceData(ctx, self.shape, self.valid, self.original_shape, self.scaling,
                           group_scaling=GroupScaling(stats, bool(center), labels))
 
+    def pca(self, n_components, center=True, side='auto'):
+        """The ``ResidentPCA`` model of this block with ``n_components`` leading components: what
+        ``sklearn.decomposition.PCA(n_components, svd_solver='full')`` fits on ``to_host()`` (``run_pca`` of the
+        reference notebook ``hadisst_pca.ipynb``), without the download.  The mean is ``column_stats()``'s (zeros
+        with ``center=False``); the Gram matrix of the centred block with itself (aa_data_gram, float64) over the
+        smaller side -- ``side='auto'``: by rows if n <= p, else by columns; 'rows' / 'cols' force one -- goes
+        through one ``numpy.linalg.eigh`` on the host.  By columns the components are the eigenvectors; by rows
+        they are ``diag(lambda^-1/2) U' Xc``, one weighted-sums pass per 16 components
+        (aa_data_weighted_column_sums).  Every component is oriented so that its entry of largest magnitude is
+        positive.  Refusals are ``ValueError``s raised before any device call: ``n_components`` not a positive
+        integer, above ``min(n - 1 if center else n, p)`` or above 256, and ``min(n, p)`` above 8192
+        (``_backend.GRAM_MAX_D``); after the eigen-solve, a component that a Gram matrix does not resolve."""
+        from .pca import fit_pca
+        return fit_pca(self, n_components, center=center, side=side)
+
     def unscale(self, array):
         """Host only: a ``(..., n_features)`` array in this block's units (archetypes, a dictionary's transpose,
         a reconstruction) back in the units before ``standardized()``: ``array * std (+ mean)``.  The identity

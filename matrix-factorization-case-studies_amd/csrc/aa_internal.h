@@ -25,6 +25,7 @@
 
 #include "../../include/aa_hip.h"
 #include "dict_plan.h"
+#include "gram_plan.h"
 
 namespace aa {
 
@@ -568,6 +569,17 @@ int launch_residual_cost(Ctx *c, const double *Ztall, const double *Wwide, const
 // column / row / total sums of squares of X - Z W' (Z = Zt, W = P) in one pass on the f64 matrix cores;
 // host outputs nullable; fetch == false: launches only (aa_time_kernel)
 int launch_residual_scores(Ctx *c, double *col_host, double *row_host, double *sse_host, bool fetch = true);
+
+// ------------------------------------------------------------------ kernels_pca.hip
+// G_dev ([pl.g_ld][pl.g_ld] doubles, whole 64 x 64 tiles) = Xc Xc' or Xc' Xc of c's stored matrix as gram_plan cut
+// it; shift_dev: p_pad doubles, zero padded (all zero: no centring); partial_dev: pl.partial_bytes (one split: unused)
+int launch_gram(Ctx *c, const GramPlan &pl, const double *shift_dev, double *partial_dev, double *G_dev);
+// the projection behind aa_set_data_projected: rows [row0, row0 + n) of owner_X, centred by shift_dev (owner_ld
+// doubles, zero padded), onto the q rows of V_dev ([project_v_rows(q)][owner_ld] doubles, zero padded) into
+// dst ([.][dst_ld] of dst_dtype), rows < n and columns < q only
+int project_v_rows(int q);
+int launch_project_rows(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, long p, long row0, long n, int q,
+                        const double *V_dev, const double *shift_dev, void *dst, long dst_ld, int dst_dtype);
 
 // ------------------------------------------------------------------ kernels_qp.hip
 // A_host (k x k) and bscale_host (k or null) come from the host, or -- A_host == nullptr --

@@ -1068,6 +1068,83 @@ int aa_set_data_take(aa_ctx *h, const aa_ctx *owner, const long *idx, long n)
     return AA_OK;
 }
 
+// the compute units gram_plan fills
+static int device_cus(const Ctx *c, int *cus)
+{
+    AA_CHECK_HIP(hipDeviceGetAttribute(cus, hipDeviceAttributeMultiprocessorCount, c->device));
+    return AA_OK;
+}
+
+// a p_pad-long float64 table on the device from p host values (null: zeros), the padding zero
+static int upload_padded_row(Ctx *c, ScopedDevBuf &dst, const double *src, long p, long p_pad)
+{
+    AA_CHECK(dst.alloc((size_t)p_pad * sizeof(double)));                      // zero filled
+    if (src) AA_CHECK_HIP(ctx_memcpy(c, dst.p, src, (size_t)p * sizeof(double), hipMemcpyHostToDevice));
+    return AA_OK;
+}
+
+int aa_data_gram(aa_ctx *h, int side, const double *shift, double *out, long ldo)
+{
+    AA_REQUIRE(h && out, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "aa_data_gram: no stored data matrix (data form)");
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "aa_data_gram is single-rank");
+    AA_REQUIRE(side == AA_GRAM_ROWS || side == AA_GRAM_COLS, AA_ERR_ARG, "aa_data_gram: side %d (AA_GRAM_ROWS or AA_GRAM_COLS)",
+               side);
+    const long d = side == AA_GRAM_ROWS ? c->n : c->p;
+    AA_REQUIRE(d <= GRAM_MAX_D, AA_ERR_ARG, "aa_data_gram: a %ld x %ld Gram matrix (at most %ld x %ld are formed)", d, d,
+               GRAM_MAX_D, GRAM_MAX_D);
+    AA_REQUIRE(ldo >= d, AA_ERR_ARG, "aa_data_gram: leading dimension %ld of a %ld x %ld result", ldo, d, d);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(join_side(c));
+    int cus = 0;
+    AA_CHECK(device_cus(c, &cus));
+    const GramPlan pl = gram_plan(side, c->n, c->p, (int)esize(c), cus);
+    ScopedDevBuf dshift, partial, G;
+    AA_CHECK(upload_padded_row(c, dshift, shift, c->p, c->p_pad));
+    AA_CHECK(partial.alloc((size_t)pl.partial_bytes));
+    AA_CHECK(G.alloc((size_t)pl.g_ld * pl.g_ld * sizeof(double)));
+    AA_CHECK(launch_gram(c, pl, dshift.as<double>(), partial.as<double>(), G.as<double>()));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy2d(c, out, (size_t)ldo * sizeof(double), G.p, (size_t)pl.g_ld * sizeof(double),
+                              (size_t)d * sizeof(double), (size_t)d, hipMemcpyDeviceToHost));
+    return AA_OK;
+}
+
+int aa_set_data_projected(aa_ctx *h, const aa_ctx *owner, long row0, long n, int q, const double *V, long ldv,
+                          const double *shift)
+{
+    AA_CHECK(check_owner(h, owner, "aa_set_data_projected", AA_ERR_ARG, DTYPE_MAY_WIDEN));
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
+               row0 + n, o->n);
+    AA_REQUIRE(q >= 1 && q <= AA_MAX_PROJECTED, AA_ERR_ARG, "aa_set_data_projected: %d components (1 to %d are supported)",
+               q, AA_MAX_PROJECTED);
+    AA_REQUIRE(V && ldv >= o->p, AA_ERR_ARG, "aa_set_data_projected: a %d x %ld matrix V with ldv >= %ld needed", q, o->p,
+               o->p);
+    // refused before anything of ctx is released: a non-finite direction or shift
+    for (int i = 0; i < q; ++i)
+        for (long j = 0; j < o->p; ++j)
+            AA_REQUIRE(V[(size_t)i * ldv + j] - V[(size_t)i * ldv + j] == 0.0, AA_ERR_ARG,
+                       "aa_set_data_projected: V[%d][%ld] = %g is not finite", i, j, V[(size_t)i * ldv + j]);
+    for (long j = 0; shift && j < o->p; ++j)
+        AA_REQUIRE(shift[j] - shift[j] == 0.0, AA_ERR_ARG, "aa_set_data_projected: shift[%ld] = %g is not finite", j,
+                   shift[j]);
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    ScopedDevBuf dshift, dV;                                                  // V widened to [rows of its tiles][p_pad]
+    AA_CHECK(upload_padded_row(c, dshift, shift, o->p, o->p_pad));
+    AA_CHECK(dV.alloc((size_t)project_v_rows(q) * o->p_pad * sizeof(double)));   // zero filled: both paddings
+    AA_CHECK_HIP(ctx_memcpy2d(c, dV.p, (size_t)o->p_pad * sizeof(double), V, (size_t)ldv * sizeof(double),
+                              (size_t)o->p * sizeof(double), (size_t)q, hipMemcpyHostToDevice));
+    AA_CHECK(install_begin(c, install_rows(n, q, round_up(q, 128))));
+    AA_CHECK(launch_project_rows(c, o->X.p, o->dtype, o->p_pad, o->p, row0, n, q, dV.as<double>(), dshift.as<double>(),
+                                 c->X.p, c->p_pad, c->dtype));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));   // the owner and the two tables have been read: they may go
+    install_commit(c);
+    return AA_OK;
+}
+
 int aa_data_column_moments(aa_ctx *h, double *mean, double *var)
 {
     AA_REQUIRE(h, AA_ERR_ARG, "null argument");
@@ -2823,9 +2900,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     else if (which == 12)                        // either stored form (not has_stored_data), like aa_pass_reduce_rows
         AA_REQUIRE(c->have_data && !c->kernel.kind && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
-    else if (which >= 13 && which <= 17)
+    else if (which >= 13 && which <= 20)
         AA_REQUIRE(has_stored_data(c) && c->world == 1 && !c->force_comm, AA_ERR_STATE,
-                   "aa_time_kernel 13 .. 17: a stored data matrix (data form), single rank");
+                   "aa_time_kernel 13 .. 20: a stored data matrix (data form), single rank");
     else
         AA_REQUIRE(has_stored_data(c) && c->have_state, AA_ERR_STATE, "aa_time_kernel: needs data-form state on a stored matrix");
     AA_CHECK_HIP(hipSetDevice(c->device));
@@ -2871,6 +2948,29 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
             rc = AA_ERR_HIP;
         }
     }
+    // 18 / 19: the Gram matrix by rows / by columns as gram_plan cuts it, uncentred; 20: the projection onto
+    // AA_TIME_PROJECTED components (a zero V: the values do not matter to the time) into a scratch block
+    enum { AA_TIME_PROJECTED = 167 };
+    GramPlan gpl = {};
+    ScopedDevBuf zshift, gram_partial, gram_out, proj_v;
+    const long proj_ld = round_up(AA_TIME_PROJECTED, 128);
+    if (which >= 18 && which <= 20 && rc == AA_OK) rc = zshift.alloc((size_t)c->p_pad * sizeof(double));
+    if ((which == 18 || which == 19) && rc == AA_OK) {
+        int cus = 0;
+        rc = device_cus(c, &cus);
+        gpl = gram_plan(which == 18 ? GRAM_ROWS : GRAM_COLS, c->n, c->p, (int)esize(c), cus);
+        if (rc == AA_OK && gpl.d > GRAM_MAX_D) {
+            set_error("aa_time_kernel %d: a %ld x %ld Gram matrix (at most %ld x %ld are formed)", which, gpl.d, gpl.d,
+                      GRAM_MAX_D, GRAM_MAX_D);
+            rc = AA_ERR_ARG;
+        }
+        if (rc == AA_OK) rc = gram_partial.alloc((size_t)gpl.partial_bytes);
+        if (rc == AA_OK) rc = gram_out.alloc((size_t)gpl.g_ld * gpl.g_ld * sizeof(double));
+    }
+    if (which == 20 && rc == AA_OK) {
+        rc = proj_v.alloc((size_t)project_v_rows(AA_TIME_PROJECTED) * c->p_pad * sizeof(double));
+        if (rc == AA_OK) rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * proj_ld * esize(c));
+    }
     // one untimed launch first
     for (int phase = 0; phase < 2 && rc == AA_OK; ++phase) {
         const int nrep = phase == 0 ? 1 : reps;
@@ -2905,6 +3005,11 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
                                        tables.as<double>() + (size_t)2 * AA_MAX_COEF_ROWS * c->p_pad,
                                        tables.as<double>() + (size_t)(2 * AA_MAX_COEF_ROWS + 1) * c->p_pad, coef.as<double>(),
                                        nullptr, scratch.p);
+            else if (which == 18 || which == 19)
+                rc = launch_gram(c, gpl, zshift.as<double>(), gram_partial.as<double>(), gram_out.as<double>());
+            else if (which == 20)
+                rc = launch_project_rows(c, c->X.p, c->dtype, c->p_pad, c->p, 0, c->n, AA_TIME_PROJECTED,
+                                         proj_v.as<double>(), zshift.as<double>(), scratch.p, proj_ld, c->dtype);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
@@ -2924,7 +3029,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (which >= 13 && which <= 17) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
+    if (which >= 13 && which <= 20) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
     return rc;
 }
 
