@@ -26,6 +26,7 @@
 #include "../../include/aa_hip.h"
 #include "dict_plan.h"
 #include "gram_plan.h"
+#include "pass_plan.h"
 
 namespace aa {
 
@@ -402,9 +403,7 @@ inline bool has_stored_data(const Ctx *c) { return c->have_data && !c->kernel.ki
 int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *outT,
                        bool main_only = false, DevBuf *flag_buf = nullptr);
 #define AA_SLAB_MODE_BYTES 256                 // Ctx::slabMode: a mode byte per slab (nslab <= 256), then two counters
-// default reduce_sparse_max: a quarter (float32) / half (float64) of a slab's groups, the largest swept fraction at
-// which the flagged sequence beat the dense pass at the headline shape (profiles/reduce_sparse_ab.txt, section 5)
-#define REDUCE_SPARSE_DEFAULT_DEN(dtype) ((dtype) == AA_F32 ? 4 : 2)
+static_assert(REDUCE_ROWS_MAX_SLABS <= AA_SLAB_MODE_BYTES, "a mode byte per slab");
 // second stage of the split-row reduction (after a main_only launch): sums the slab partials
 // plus `extra_slabs` further slabs appended by launch_reduce_rows_fixup
 int launch_reduce_rows_finish(Ctx *c, double *out_wide, void *outT, int extra_slabs);
@@ -614,11 +613,16 @@ inline DictKnobs dict_knobs()                    // the knobs dict_plan (dict_pl
 }
 extern int g_row_local_variant, g_row_local_split, g_row_local_acc64, g_f64_mfma;   // kernels_gemm.hip
 extern int g_reduce_sparse, g_reduce_sparse_max;                                    // kernels_gemm.hip
+inline PassKnobs pass_knobs()                    // the knobs the pass plans (pass_plan.h) decide by, as they are now
+{
+    return PassKnobs{g_row_local_variant, g_row_local_acc64, g_row_local_split, g_f64_mfma, g_reduce_sparse,
+                     g_reduce_sparse_max};
+}
 // launch_reduce_rows with a flag buffer takes its flagged sequence, i.e. leaves the group flags of its operand in
-// that buffer (the condition of kernels_gemm.hip: launch_reduce_rows, restated for the callers that reuse the flags)
+// that buffer: the plan's own predicate, for the callers that reuse the flags
 inline bool reduce_rows_flags_operand(const Ctx *c)
 {
-    return g_reduce_sparse && !c->time_gemm && (c->dtype == AA_F32 || g_f64_mfma);
+    return reduce_rows_takes_flags(pass_knobs(), c->dtype == AA_F32, c->time_gemm);
 }
 extern int g_qp_pass_cap, g_qp_mode, g_qp_quad_cap, g_qp_sort;               // kernels_qp.hip
 extern int g_qp_fused_order, g_qp_wave_lazy, g_qp_quad_lazy;                 // kernels_qp.hip

@@ -901,7 +901,7 @@ __global__ __launch_bounds__(!ACC64 ? (NCT == 1 ? 1024 : 768) : (NCT == 1 ? 768 
 // block barrier is the raw s_barrier (a __syncthreads would drain the DMAs in flight).  The fp32
 // accumulation chain ends after every tile (32 columns); the pieces are summed in float64 (see
 // k_row_local_f32_ws).
-constexpr int ROW_LOCAL_RING = 8;   // X pieces in a wave's ring: two tiles, one of them in flight (the launcher sizes the LDS by it)
+// (ROW_LOCAL_RING, the X pieces in a wave's ring, is pass_plan.h's: the plan sizes the LDS by it and names the kernel)
 __device__ __forceinline__ void dma16(const float *src, float *lds_uniform)
 {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)src,
@@ -1464,8 +1464,6 @@ int launch_stream_probe(Ctx *c, int variant)
 // ---------------------------------------------------------------------------
 // host launchers
 // ---------------------------------------------------------------------------
-#define PASS_NAME(WHICH, ...) snprintf(c->pass_names[WHICH], sizeof(c->pass_names[WHICH]), __VA_ARGS__)
-
 static void gemm_event(Ctx *c, int which)
 {
     if (!c->time_gemm) return;
@@ -1476,98 +1474,80 @@ static void gemm_event(Ctx *c, int which)
     }
 }
 
+// The reduce-over-rows kernels on element type T (float32; float64 on the matrix cores) share two signatures: the
+// dense kernel, gated by a mode byte per slab when it runs behind its gather twin, and the gather kernel.
+template <typename T>
+using ReduceRowsFn = void (*)(const T *, long, const double *, long, long, int, T *, const unsigned char *);
+template <typename T>
+struct ReduceRowsGather {
+    void (*gather)(const T *, long, const double *, long, long, int, T *, const unsigned char *, int, unsigned char *,
+                   unsigned int *);
+    ReduceRowsFn<T> gated;
+};
+
+template <typename T>
+static void reduce_rows_dense(Ctx *c, const ReduceRowsPlan &pl, ReduceRowsFn<T> dense, const double *A_tall,
+                              const unsigned char *mode)
+{
+    hipLaunchKernelGGL(dense, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(256), 0, c->stream, c->X.as<T>(),
+                       c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, c->partial.as<T>(), mode);
+}
+
 // The flagged sequence: group flags of the tall operand -> gather kernel -> gated dense kernel.
 // Three launches with the per-slab decision on the device: nothing here waits for the device, and
 // the sequence can be captured in a graph.
-static int launch_reduce_rows_flagged(Ctx *c, const double *A_tall, DevBuf *flag_buf)
+template <typename T>
+static int reduce_rows_flagged(Ctx *c, const ReduceRowsPlan &pl, const ReduceRowsGather<T> &k, const double *A_tall,
+                               DevBuf *flag_buf)
 {
     unsigned char *flags = flag_buf->as<unsigned char>();
     unsigned char *mode = c->slabMode.as<unsigned char>();
     unsigned int *counters = reinterpret_cast<unsigned int *>(mode + AA_SLAB_MODE_BYTES);
-    const long gps = c->rows_per_slab / 4;                   // groups per (full) slab
-    long limit = g_reduce_sparse_max < 0 ? gps / REDUCE_SPARSE_DEFAULT_DEN(c->dtype) : (long)g_reduce_sparse_max;
-    if (limit > gps) limit = gps;
     AA_CHECK(launch_group_flags(c, A_tall, flags, counters));
-    dim3 block(256);
-    if (c->dtype == AA_F32) {
-        dim3 grid((unsigned)((c->p_pad + 511) / 512), (unsigned)c->nslab);
-        float *part = c->partial.as<float>();
-#define RRG(NCTV)                                                                                      \
-    do {                                                                                               \
-        hipLaunchKernelGGL((k_reduce_rows_gather_f32<NCTV>), grid, block, 0, c->stream, c->X.as<float>(), \
-                           c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part,          \
-                           (const unsigned char *)flags, (int)limit, mode, counters);                  \
-        hipLaunchKernelGGL((k_reduce_rows_f32<NCTV, 4, true>), grid, block, 0, c->stream,              \
-                           c->X.as<float>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,             \
-                           (int)c->p_pad, part, (const unsigned char *)mode);                          \
-    } while (0)
-        if (c->KP == 32) RRG(1);
-        else RRG(2);
-#undef RRG
-    } else {
-        dim3 grid((unsigned)((c->p_pad + 255) / 256), (unsigned)c->nslab);
-        double *part = c->partial.as<double>();
-#define RDG(NTV)                                                                                       \
-    do {                                                                                               \
-        hipLaunchKernelGGL((k_reduce_rows_gather_f64_mfma<NTV>), grid, block, 0, c->stream,            \
-                           c->X.as<double>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,            \
-                           (int)c->p_pad, part, (const unsigned char *)flags, (int)limit, mode,        \
-                           counters);                                                                  \
-        hipLaunchKernelGGL((k_reduce_rows_f64_mfma<NTV, true>), grid, block, 0, c->stream,             \
-                           c->X.as<double>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad,            \
-                           (int)c->p_pad, part, (const unsigned char *)mode);                          \
-    } while (0)
-        if (c->KP == 32) RDG(2);
-        else RDG(4);
-#undef RDG
-    }
-    AA_CHECK_HIP(hipGetLastError());
+    hipLaunchKernelGGL(k.gather, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(256), 0, c->stream, c->X.as<T>(),
+                       c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, c->partial.as<T>(),
+                       (const unsigned char *)flags, (int)pl.gather_limit, mode, counters);
+    reduce_rows_dense<T>(c, pl, k.gated, A_tall, mode);
     return AA_OK;
 }
 
 int launch_reduce_rows(Ctx *c, const double *A_tall, double *out_wide, void *outT, bool main_only,
                        DevBuf *flag_buf)
 {
-    dim3 block(256);
-    const unsigned char *no_mode = nullptr;
-    // The float64 VALU kernel (f64_mfma = 0) has no gather twin: it stays dense.  So does every call while
-    // aa_gemm_timing is on: its event pairs time full passes (bench.py's roofline, two per outer iteration),
-    // and the dense pass gives the same bits.
-    const bool flagged = flag_buf && g_reduce_sparse && !c->time_gemm && (c->dtype == AA_F32 || g_f64_mfma);
-    if (!flagged) gemm_event(c, 0);
-    if (c->dtype == AA_F32) {
-        dim3 grid((unsigned)((c->p_pad + 511) / 512), (unsigned)c->nslab);
-        float *part = c->partial.as<float>();
-#define RRL(NCTV, UV)                                                                         \
-    hipLaunchKernelGGL((k_reduce_rows_f32<NCTV, UV>), grid, block, 0, c->stream, c->X.as<float>(), \
-                       c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode)
-        if (flagged) AA_CHECK(launch_reduce_rows_flagged(c, A_tall, flag_buf));
-        else if (c->KP == 32) RRL(1, 4);
-        else RRL(2, 4);
-        PASS_NAME(0, "k_reduce_rows_f32<%d,4>", c->KP / 32);
-#undef RRL
-    } else {
-        dim3 grid((unsigned)((c->p_pad + 255) / 256), (unsigned)c->nslab);
-        double *part = c->partial.as<double>();
-        if (g_f64_mfma) PASS_NAME(0, "k_reduce_rows_f64_mfma<%d>", c->KP == 32 ? 2 : 4);
-        else PASS_NAME(0, "k_reduce_rows_f64<%d>", c->KP);
-        if (flagged) AA_CHECK(launch_reduce_rows_flagged(c, A_tall, flag_buf));
-        else if (g_f64_mfma) {
-            if (c->KP == 32)
-                hipLaunchKernelGGL(k_reduce_rows_f64_mfma<2>, grid, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode);
-            else
-                hipLaunchKernelGGL(k_reduce_rows_f64_mfma<4>, grid, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part, no_mode);
-        } else if (c->KP == 32)
-            hipLaunchKernelGGL(k_reduce_rows_f64<32>, grid, block, 0, c->stream, c->X.as<double>(),
-                               c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
-        else
-            hipLaunchKernelGGL(k_reduce_rows_f64<64>, grid, block, 0, c->stream, c->X.as<double>(),
-                               c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad, part);
+    // every instantiation, [KP == 64]
+    static const ReduceRowsGather<float> gather32[2] = {{k_reduce_rows_gather_f32<1>, k_reduce_rows_f32<1, 4, true>},
+                                                        {k_reduce_rows_gather_f32<2>, k_reduce_rows_f32<2, 4, true>}};
+    static const ReduceRowsGather<double> gather64[2] = {
+        {k_reduce_rows_gather_f64_mfma<2>, k_reduce_rows_f64_mfma<2, true>},
+        {k_reduce_rows_gather_f64_mfma<4>, k_reduce_rows_f64_mfma<4, true>}};
+    static const ReduceRowsFn<float> dense32[2] = {k_reduce_rows_f32<1, 4>, k_reduce_rows_f32<2, 4>};
+    static const ReduceRowsFn<double> dense64[2] = {k_reduce_rows_f64_mfma<2>, k_reduce_rows_f64_mfma<4>};
+    static void (*const valu[2])(const double *, long, const double *, long, long, int, double *) = {
+        k_reduce_rows_f64<32>, k_reduce_rows_f64<64>};
+
+    const ReduceRowsPlan pl = reduce_rows_plan(
+        pass_knobs(), ReduceRowsIn{c->dtype == AA_F32, c->KP, c->p_pad, c->nslab, c->rows_per_slab, flag_buf != nullptr,
+                                   c->time_gemm});
+    const int kp64 = c->KP == 64;
+    pass_name(pl, c->pass_names[0], sizeof(c->pass_names[0]));
+    if (!pl.flagged) gemm_event(c, 0);
+    switch (pl.family) {
+        case ReduceRowsFamily::f32:
+            if (pl.flagged) AA_CHECK(reduce_rows_flagged<float>(c, pl, gather32[kp64], A_tall, flag_buf));
+            else reduce_rows_dense<float>(c, pl, dense32[kp64], A_tall, nullptr);
+            break;
+        case ReduceRowsFamily::f64_mfma:
+            if (pl.flagged) AA_CHECK(reduce_rows_flagged<double>(c, pl, gather64[kp64], A_tall, flag_buf));
+            else reduce_rows_dense<double>(c, pl, dense64[kp64], A_tall, nullptr);
+            break;
+        case ReduceRowsFamily::f64_valu:                    // (no gather twin: the plan never flags it)
+            hipLaunchKernelGGL(valu[kp64], dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3(256), 0, c->stream,
+                               c->X.as<double>(), c->p_pad, A_tall, c->rows_per_slab, c->n_pad, (int)c->p_pad,
+                               c->partial.as<double>());
+            break;
     }
     AA_CHECK_HIP(hipGetLastError());
-    if (!flagged) gemm_event(c, 0);
+    if (!pl.flagged) gemm_event(c, 0);
     if (main_only) return AA_OK;
     return launch_reduce_rows_finish(c, out_wide, outT, 0);
 }
@@ -1989,210 +1969,103 @@ int g_row_local_acc64 = 1;     // float32 row-local kernels: cut the fp32 accumu
                                // (variant 9), 2: in the register-staged wave-streaming kernel too (k > 32; costs
                                // it a wave per SIMD: 0.31 -> 0.6 ms)
 int g_row_local_split = 1;     // block-tiled kernels: split the contraction over column chunks when there are few row blocks
-static int row_local_variant(const Ctx *c)
+
+// The row-local kernels on element type T share two signatures: the plain one, and one with a trailing int -- W, the
+// waves per block (streaming families), or the column chunk (block-tiled families).
+template <typename T>
+using RowLocalFn = void (*)(const T *, long, const T *, int, double *, long);
+template <typename T>
+using RowLocalArgFn = void (*)(const T *, long, const T *, int, double *, long, int);
+
+template <typename T>
+static void row_local_launch(Ctx *c, const RowLocalPlan &pl, RowLocalFn<T> kernel, const void *B, double *dst)
 {
-    if (g_row_local_variant >= 0) return g_row_local_variant;
-    if (c->n_pad / 32 < 8 * 128) return 4;
-    // large shards: wave-streaming; k <= 32 with float64 sums of 32-column pieces through the LDS-DMA
-    // kernel (1 % slower than the register-staged kernel with one fp32 chain per row, 86 x closer to
-    // the exact product: rms error 3.5e-9 against 3.1e-7 of sum |x||b| at p = 4096)
-    return (c->KP == 32 && g_row_local_acc64 >= 1) ? 9 : 8;
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3((unsigned)pl.block), pl.lds,
+                       c->stream, c->X.as<T>(), c->p_pad, reinterpret_cast<const T *>(B), (int)c->p_pad, dst, c->n_pad);
+}
+
+template <typename T>
+static void row_local_launch(Ctx *c, const RowLocalPlan &pl, RowLocalArgFn<T> kernel, const void *B, double *dst,
+                             int arg)
+{
+    hipLaunchKernelGGL(kernel, dim3((unsigned)pl.grid_x, (unsigned)pl.grid_y), dim3((unsigned)pl.block), pl.lds,
+                       c->stream, c->X.as<T>(), c->p_pad, reinterpret_cast<const T *>(B), (int)c->p_pad, dst, c->n_pad,
+                       arg);
+}
+
+// A streaming family: kernels[which] with W waves per block, behind the raised dynamic-LDS limit -- set on all the
+// family's kernels, once per device, before its first launch there.
+static bool &row_local_lds_raised(const Ctx *c, RowLocalFamily family)
+{
+    static bool raised[ROW_LOCAL_FAMILIES][64] = {{false}};          // the attribute is per device
+    return raised[(int)family][c->device & 63];
+}
+
+template <typename T, int N>
+static int row_local_stream(Ctx *c, const RowLocalPlan &pl, const RowLocalArgFn<T> (&kernels)[N], int which,
+                            const void *B, double *dst)
+{
+    bool &raised = row_local_lds_raised(c, pl.family);
+    if (pl.raise_lds && !raised) {
+        for (const RowLocalArgFn<T> kernel : kernels)
+            AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(kernel),
+                                             hipFuncAttributeMaxDynamicSharedMemorySize, (int)PASS_LDS_LIMIT));
+        raised = true;
+    }
+    row_local_launch<T>(c, pl, kernels[which], B, dst, pl.W);
+    return AA_OK;
 }
 
 int launch_row_local(Ctx *c, const void *B_wideT, double *out_tall)
 {
-    dim3 block(256);
-    gemm_event(c, 1);
-    if (c->dtype == AA_F32 && row_local_variant(c) == 9 && c->KP == 32) {
-        // LDS-DMA wave-streaming kernel with float64 sums
-        const float *B = reinterpret_cast<const float *>(B_wideT);
-        const long tiles = c->n_pad / 32;
-        int W = (int)((tiles + 255) / 256);               // one block per CU where possible
-        if (W < 8) W = 8;
-        if (W > 16) W = 16;
-        const size_t lds = ((size_t)2 * 32 * 64 + (size_t)W * ROW_LOCAL_RING * 256) * sizeof(float);
-        dim3 grid((unsigned)((tiles + W - 1) / W)), blk((unsigned)(64 * W));
-        static bool attr_done[64] = {false};                // the attribute is per device
-        if (!attr_done[c->device & 63]) {
-            AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f32_dma),
-                                             hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_done[c->device & 63] = true;
-        }
-        PASS_NAME(1, "k_row_local_f32_dma<%d>", ROW_LOCAL_RING);
-        hipLaunchKernelGGL(k_row_local_f32_dma, grid, blk, lds, c->stream, c->X.as<float>(), c->p_pad, B,
-                           (int)c->p_pad, out_tall, c->n_pad, W);
-    } else if (c->dtype == AA_F32 && row_local_variant(c) == 8) {
-        // wave-streaming kernel: W waves per block, one block per CU where possible
-        const float *B = reinterpret_cast<const float *>(B_wideT);
-        const int nct = c->KP / 32;
-        const long tiles = c->n_pad / 32;
-        const bool a64 = g_row_local_acc64 >= 2;
-        const int wmax = !a64 ? (nct == 1 ? 16 : 12) : (nct == 1 ? 12 : 8);   // 160 KB of LDS; float64 sums: 3 (2) waves per SIMD
-        int W = (int)((tiles + 255) / 256);
-        if (W < 8) W = 8;                                 // the B slab loader assumes >= 512 threads
-        if (W > wmax) W = wmax;
-        const size_t lds = ((size_t)2 * c->KP * 128 + (size_t)W * 32 * 64) * sizeof(float);
-        static bool attr_set[64] = {false};                 // the attribute is per device
-        if (!attr_set[c->device & 63]) {
-            const void *fns[4] = {reinterpret_cast<const void *>(&k_row_local_f32_ws<1, false>),
-                                  reinterpret_cast<const void *>(&k_row_local_f32_ws<2, false>),
-                                  reinterpret_cast<const void *>(&k_row_local_f32_ws<1, true>),
-                                  reinterpret_cast<const void *>(&k_row_local_f32_ws<2, true>)};
-            for (const void *fn : fns)
-                AA_CHECK_HIP(hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-            attr_set[c->device & 63] = true;
-        }
-        dim3 grid((unsigned)((tiles + W - 1) / W)), blk((unsigned)(64 * W));
-#define RLW(NCTV, A64V)                                                                              \
-    hipLaunchKernelGGL((k_row_local_f32_ws<NCTV, A64V>), grid, blk, lds, c->stream, c->X.as<float>(), \
-                       c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad, W)
-        PASS_NAME(1, "k_row_local_f32_ws<%d,%d>", nct, (int)a64);
-        if (nct == 1) { if (a64) RLW(1, true); else RLW(1, false); }
-        else          { if (a64) RLW(2, true); else RLW(2, false); }
-#undef RLW
-    } else if (c->dtype == AA_F32 && row_local_variant(c) >= 2) {
-        const float *B = reinterpret_cast<const float *>(B_wideT);
-        // few row blocks (short shards): split the contraction over column chunks as well, about
-        // three blocks per CU, chunks of >= 512 columns (a multiple of every tile width)
-        const long rblocks = c->n_pad / 128;
-        int nsplit = 1, chunk = (int)c->p_pad;
-        if (rblocks < 384 && g_row_local_split) {
-            nsplit = (int)((768 + rblocks - 1) / rblocks);
-            const int max_split = (int)(c->p_pad / 512);
-            if (nsplit > max_split) nsplit = max_split;
-            if (nsplit < 1) nsplit = 1;
-        }
-        double *dst = out_tall;
-        if (nsplit > 1) {
-            chunk = (int)round_up((c->p_pad + nsplit - 1) / nsplit, 128);
-            nsplit = (int)((c->p_pad + chunk - 1) / chunk);
-        }
-        if (nsplit > 1) {
-            AA_CHECK(c->rlPartial.alloc((size_t)nsplit * c->n_pad * c->KP * sizeof(double)));
-            dst = c->rlPartial.as<double>();
-        }
-        dim3 grid((unsigned)rblocks, (unsigned)nsplit);
-#define RLB(NCTV, TCV, DBV)                                                                   \
-    do {                                                                                      \
-        if (g_row_local_acc64)                                                                \
-            hipLaunchKernelGGL((k_row_local_f32_blk<NCTV, TCV, DBV, true>), grid, block, 0, c->stream, \
-                               c->X.as<float>(), c->p_pad, B, (int)c->p_pad, dst, c->n_pad, chunk);    \
-        else                                                                                  \
-            hipLaunchKernelGGL((k_row_local_f32_blk<NCTV, TCV, DBV, false>), grid, block, 0, c->stream, \
-                               c->X.as<float>(), c->p_pad, B, (int)c->p_pad, dst, c->n_pad, chunk);    \
-    } while (0)
-        const int v = row_local_variant(c);
-        PASS_NAME(1, "k_row_local_f32_blk[v%d,acc64=%d,split=%d]", v, g_row_local_acc64 != 0, nsplit);
-        if (c->KP == 32) {
-            switch (v) {
-                case 3: RLB(1, 64, true); break;
-                case 4: RLB(1, 128, false); break;
-                case 5: RLB(1, 32, true); break;
-                case 6: RLB(1, 128, true); break;
-                case 7: RLB(1, 32, false); break;
-                default: RLB(1, 64, false); break;
-            }
-        } else {
-            switch (v) {
-                case 3: case 5: case 6: RLB(2, 64, true); break;
-                default: RLB(2, 64, false); break;
-            }
-        }
+    // every instantiation a family has; [KP == 64] where nothing else is said
+    static const RowLocalArgFn<float> dma[1] = {k_row_local_f32_dma};
+    static const RowLocalArgFn<float> ws32[4] = {k_row_local_f32_ws<1, false>, k_row_local_f32_ws<2, false>,
+                                                 k_row_local_f32_ws<1, true>, k_row_local_f32_ws<2, true>};   // [2 acc64 + (KP == 64)]
+    struct Blk { int nct, tile; bool dbuf; RowLocalArgFn<float> acc64, chain; };
+#define RLB(NCTV, TCV, DBV) \
+    {NCTV, TCV, DBV, k_row_local_f32_blk<NCTV, TCV, DBV, true>, k_row_local_f32_blk<NCTV, TCV, DBV, false>}
+    static const Blk blk[] = {RLB(1, 64, true),  RLB(1, 128, false), RLB(1, 32, true),  RLB(1, 128, true),
+                              RLB(1, 32, false), RLB(1, 64, false),  RLB(2, 64, true),  RLB(2, 64, false)};
 #undef RLB
-        if (nsplit > 1) {
-            const long elems = c->n_pad * c->KP;
-            hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
-                               (const double *)dst, elems, nsplit, out_tall);
+    static const RowLocalFn<float> lds[2] = {k_row_local_f32_lds<1>, k_row_local_f32_lds<2>};
+    static const RowLocalFn<float> global[2] = {k_row_local_f32<1, row_local_global_rt(1)>,
+                                                k_row_local_f32<2, row_local_global_rt(2)>};
+    static const RowLocalArgFn<double> ws64[2] = {k_row_local_f64_ws<2>, k_row_local_f64_ws<4>};
+    static const RowLocalArgFn<double> mfma[2] = {k_row_local_f64_mfma<2>, k_row_local_f64_mfma<4>};
+    static const RowLocalFn<double> valu[2] = {k_row_local_f64<32>, k_row_local_f64<64>};
+
+    const RowLocalPlan pl = row_local_plan(pass_knobs(), c->dtype == AA_F32, c->KP, c->n_pad, c->p_pad);
+    const int kp64 = c->KP == 64;
+    pass_name(pl, c->pass_names[1], sizeof(c->pass_names[1]));
+    gemm_event(c, 1);
+    // split over column chunks: a partial per chunk, summed behind the kernel
+    double *dst = out_tall;
+    if (pl.nsplit > 1) {
+        AA_CHECK(c->rlPartial.alloc(pl.partial_bytes));
+        dst = c->rlPartial.as<double>();
+    }
+    switch (pl.family) {
+        case RowLocalFamily::f32_dma: AA_CHECK(row_local_stream<float>(c, pl, dma, 0, B_wideT, dst)); break;
+        case RowLocalFamily::f32_ws: AA_CHECK(row_local_stream<float>(c, pl, ws32, 2 * pl.acc64 + kp64, B_wideT, dst)); break;
+        case RowLocalFamily::f32_blk: {
+            RowLocalArgFn<float> kernel = nullptr;
+            for (const Blk &k : blk)
+                if (k.nct == pl.targ && k.tile == pl.tile && k.dbuf == pl.dbuf) kernel = pl.acc64 ? k.acc64 : k.chain;
+            AA_REQUIRE(kernel, AA_ERR_STATE, "row-local pass: no block-tiled kernel of the planned shape");
+            row_local_launch<float>(c, pl, kernel, B_wideT, dst, pl.chunk);
+            break;
         }
-    } else if (c->dtype == AA_F32 && row_local_variant(c) == 1) {
-        const float *B = reinterpret_cast<const float *>(B_wideT);
-        dim3 grid((unsigned)(c->n_pad / 128));
-        PASS_NAME(1, "k_row_local_f32_lds<%d>", c->KP / 32);
-        if (c->KP == 32)
-            hipLaunchKernelGGL(k_row_local_f32_lds<1>, grid, block, 0, c->stream, c->X.as<float>(),
-                               c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
-        else
-            hipLaunchKernelGGL(k_row_local_f32_lds<2>, grid, block, 0, c->stream, c->X.as<float>(),
-                               c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
-    } else if (c->dtype == AA_F32) {
-        const float *B = reinterpret_cast<const float *>(B_wideT);
-        PASS_NAME(1, "k_row_local_f32<%d>", c->KP / 32);
-        if (c->KP == 32) {
-            constexpr int RT = 2;
-            dim3 grid((unsigned)((c->n_pad + 128 * RT - 1) / (128 * RT)));
-            hipLaunchKernelGGL((k_row_local_f32<1, RT>), grid, block, 0, c->stream,
-                               c->X.as<float>(), c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
-        } else {
-            constexpr int RT = 1;
-            dim3 grid((unsigned)((c->n_pad + 128 * RT - 1) / (128 * RT)));
-            hipLaunchKernelGGL((k_row_local_f32<2, RT>), grid, block, 0, c->stream,
-                               c->X.as<float>(), c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
-        }
-    } else {
-        const double *B = reinterpret_cast<const double *>(B_wideT);
-        dim3 grid((unsigned)(c->n_pad / 64));
-        if (g_f64_mfma == 2 || (g_f64_mfma == 1 && c->n_pad / 32 >= 8 * 128)) {
-            // wave-streaming kernel, W waves per block (see the float32 sibling)
-            const int nt = c->KP / 16;
-            const long tiles = c->n_pad / 32;
-            const int wmax = nt == 2 ? 14 : 10;                // 160 KB of LDS
-            int W = (int)((tiles + 255) / 256);
-            if (W < 8) W = 8;
-            if (W > wmax) W = wmax;
-            const size_t lds = ((size_t)2 * c->KP * 66 + (size_t)W * 32 * 34) * sizeof(double);
-            static bool attr_set64[64] = {false};               // the attribute is per device
-            if (!attr_set64[c->device & 63]) {
-                AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f64_ws<2>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                AA_CHECK_HIP(hipFuncSetAttribute(reinterpret_cast<const void *>(&k_row_local_f64_ws<4>),
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-                attr_set64[c->device & 63] = true;
-            }
-            dim3 gw((unsigned)((tiles + W - 1) / W)), bw((unsigned)(64 * W));
-            PASS_NAME(1, "k_row_local_f64_ws<%d>", nt);
-            if (nt == 2)
-                hipLaunchKernelGGL(k_row_local_f64_ws<2>, gw, bw, lds, c->stream, c->X.as<double>(), c->p_pad,
-                                   B, (int)c->p_pad, out_tall, c->n_pad, W);
-            else
-                hipLaunchKernelGGL(k_row_local_f64_ws<4>, gw, bw, lds, c->stream, c->X.as<double>(), c->p_pad,
-                                   B, (int)c->p_pad, out_tall, c->n_pad, W);
-        } else if (g_f64_mfma) {
-            // few row blocks (short, wide data): split the contraction over column chunks too
-            const long rblocks = c->n_pad / 64;
-            int nsplit = 1;
-            if (rblocks < 192 && g_row_local_split) {
-                nsplit = (int)((512 + rblocks - 1) / rblocks);
-                const int max_split = (int)(c->p_pad / 256);       // >= 256 columns per chunk
-                if (nsplit > max_split) nsplit = max_split;
-                if (nsplit < 1) nsplit = 1;
-            }
-            int chunk = (int)c->p_pad;
-            double *dst = out_tall;
-            if (nsplit > 1) {
-                chunk = (int)round_up((c->p_pad + nsplit - 1) / nsplit, 32);
-                nsplit = (int)((c->p_pad + chunk - 1) / chunk);
-                AA_CHECK(c->rlPartial.alloc((size_t)nsplit * c->n_pad * c->KP * sizeof(double)));
-                dst = c->rlPartial.as<double>();
-            }
-            dim3 g2((unsigned)rblocks, (unsigned)nsplit);
-            PASS_NAME(1, "k_row_local_f64_mfma<%d>[split=%d]", c->KP == 32 ? 2 : 4, nsplit);
-            if (c->KP == 32)
-                hipLaunchKernelGGL(k_row_local_f64_mfma<2>, g2, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, B, (int)c->p_pad, dst, c->n_pad, chunk);
-            else
-                hipLaunchKernelGGL(k_row_local_f64_mfma<4>, g2, block, 0, c->stream, c->X.as<double>(),
-                                   c->p_pad, B, (int)c->p_pad, dst, c->n_pad, chunk);
-            if (nsplit > 1) {
-                const long elems = c->n_pad * c->KP;
-                hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
-                                   (const double *)dst, elems, nsplit, out_tall);
-            }
-        } else if (PASS_NAME(1, "k_row_local_f64<%d>", c->KP), c->KP == 32)
-            hipLaunchKernelGGL(k_row_local_f64<32>, grid, block, 0, c->stream, c->X.as<double>(),
-                               c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
-        else
-            hipLaunchKernelGGL(k_row_local_f64<64>, grid, block, 0, c->stream, c->X.as<double>(),
-                               c->p_pad, B, (int)c->p_pad, out_tall, c->n_pad);
+        case RowLocalFamily::f32_lds: row_local_launch<float>(c, pl, lds[kp64], B_wideT, dst); break;
+        case RowLocalFamily::f32_global: row_local_launch<float>(c, pl, global[kp64], B_wideT, dst); break;
+        case RowLocalFamily::f64_ws: AA_CHECK(row_local_stream<double>(c, pl, ws64, kp64, B_wideT, dst)); break;
+        case RowLocalFamily::f64_mfma: row_local_launch<double>(c, pl, mfma[kp64], B_wideT, dst, pl.chunk); break;
+        case RowLocalFamily::f64_valu: row_local_launch<double>(c, pl, valu[kp64], B_wideT, dst); break;
+    }
+    if (pl.nsplit > 1) {
+        const long elems = c->n_pad * c->KP;
+        hipLaunchKernelGGL(k_sum_chunks, dim3((unsigned)((elems + 255) / 256)), dim3(256), 0, c->stream,
+                           (const double *)dst, elems, pl.nsplit, out_tall);
     }
     AA_CHECK_HIP(hipGetLastError());
     gemm_event(c, 1);

@@ -74,17 +74,11 @@ static int ensure_problem(Ctx *c, int k)
         AA_CHECK(c->Qw.alloc((size_t)KP * c->p_pad * sizeof(float)));
     }
     // split-row decomposition of the reduce-over-rows GEMM
-    const long colgroups = c->dtype == AA_F32 ? (c->p_pad + 511) / 512 : (c->p_pad + 255) / 256;
-    constexpr long REDUCE_ROWS_BLOCKS = 512;      // target block count, 2 per CU: 64 slabs at p = 4096
-    long nslab = (REDUCE_ROWS_BLOCKS + colgroups - 1) / colgroups;
-    if (nslab > 256) nslab = 256;
-    if (nslab < 1) nslab = 1;
-    long rps = round_up((c->n_pad + nslab - 1) / nslab, 32);
-    nslab = (c->n_pad + rps - 1) / rps;
-    c->nslab = nslab;
-    c->rows_per_slab = rps;
+    const PassSlabs slabs = pass_slabs(c->dtype == AA_F32, c->n_pad, c->p_pad);
+    c->nslab = slabs.nslab;
+    c->rows_per_slab = slabs.rows_per_slab;
     c->partial.release();
-    AA_CHECK(c->partial.alloc((size_t)(nslab + QP_FIX_SLABS) * KP * c->p_pad * esize(c)));
+    AA_CHECK(c->partial.alloc((size_t)(c->nslab + QP_FIX_SLABS) * KP * c->p_pad * esize(c)));
     AA_CHECK(c->groupFlags.alloc((size_t)c->n_pad / 4 + AA_SLACK_ROWS));
     AA_CHECK(c->slabMode.alloc(AA_SLAB_MODE_BYTES + 2 * sizeof(unsigned int)));
     AA_CHECK(tall_setup(c));

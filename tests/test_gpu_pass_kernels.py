@@ -52,7 +52,7 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-GEMM_SOURCE = os.path.join(ROOT, "matrix-factorization-case-studies_amd", "csrc", "kernels_gemm.hip")
+PLAN_SOURCE = os.path.join(ROOT, "matrix-factorization-case-studies_amd", "csrc", "pass_plan.h")
 
 # the defaults of kernels_gemm.hip (g_row_local_variant, g_row_local_acc64, g_row_local_split, g_f64_mfma)
 DEFAULTS = dict(row_local_variant=-1, row_local_acc64=1, row_local_split=1, f64_mfma=1)
@@ -303,8 +303,9 @@ def launch_model(dtype, options, n, p, k):
 
 
 def pass_name_formats():
-    """(which, format) of every PASS_NAME(...) call of kernels_gemm.hip."""
-    src = open(GEMM_SOURCE).read()
+    """(which, format) of every PASS_NAME(...) call of pass_plan.h, where the launchers of kernels_gemm.hip take
+    the names they report from."""
+    src = open(PLAN_SOURCE).read()
     return [(int(w), fmt) for w, fmt in re.findall(r'PASS_NAME\(\s*([01])\s*,\s*"([^"]+)"', src)]
 
 
