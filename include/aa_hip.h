@@ -238,8 +238,8 @@ int aa_ctx_p2p_init(aa_ctx *ctx, const void *handles, int rank, int world);
  * bench.py for the barrier + max-over-ranks timing); op: 0 = sum, 1 = max. */
 int aa_ctx_allreduce_host(aa_ctx *ctx, double *buf, int count, int op);
 
-/* Installing data.  Twelve entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
- * aa_set_data_rows_affine, aa_set_data_rows_model, aa_set_data_take, aa_set_data_projected, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
+/* Installing data.  Thirteen entry points give a context its matrix: aa_set_data, aa_share_data, aa_set_data_rows,
+ * aa_set_data_rows_affine, aa_set_data_rows_model, aa_set_data_rows_slots, aa_set_data_take, aa_set_data_projected, aa_set_data_weighted, aa_set_rbf_features, aa_set_poly_features and
  * the _resident forms of the last two.  Every one of them ("an install") first checks its arguments -- a call it
  * refuses has not touched ctx, which keeps the data it had -- and then replaces everything that belonged to the
  * previous matrix: the form and the kind of implicit kernel (none for a stored matrix), aa_set_linear_kernel, the
@@ -363,6 +363,39 @@ int aa_data_grouped_sqdev(aa_ctx *ctx, int G, const double *A, const int *group,
 int aa_set_data_rows_model(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, int G, const int *group,
                            const double *shift, const double *icpt, const double *slope, const double *t,
                            const double *scale);
+
+/* Calendar-slot climatology and anomalies of resident sub-monthly data (the .anom. / .std_anom. inputs of
+ * bin/run_jra55_*: deviations from a climatology per calendar slot -- 366 days, 1464 six-hourly steps of a year).
+ * A slot is an integer label 0 .. G - 1 per row, taken from the driver's time axis (leap days and irregular
+ * calendars are the driver's labels).  With hundreds of slots the coefficient matrix of
+ * aa_data_weighted_column_sums would be a sparse indicator, so these entry points are slot-major
+ * (csrc/kernels_slots.hip): the host sorts the rows by slot and cuts every slot's rows into chunks of at most
+ * AA_SLOT_CHUNK_ROWS (csrc/group_plan.h); one wave takes one chunk and AA_SLOT_TILE_COLS adjacent columns, keeps the
+ * slot's table row in registers and walks the chunk's rows.  The <= 16-group entry points above stay what they are.
+ *
+ * aa_data_slot_sums: out[g][j] = sum of X[t][j] over the rows t with slot[t] == g (centre NULL), or of
+ *   (X[t][j] - centre[g][j])^2 (centre: G x p host doubles).  slot: n host ints in [-1, G), n the resident rows, -1:
+ *   the row is not counted; out: G x p host doubles; counts (nullable): G host longs, the rows counted per slot.
+ *   float64 arithmetic in both context dtypes (elements widened on load).  Summation order: within a chunk the rows
+ *   are added one after the other in ascending row index, one chain per column; a finish kernel adds a slot's
+ *   chunks in ascending order; no atomics: two calls return the same bits.  A slot without counted rows gives
+ *   exactly 0.0 and count 0, and its row of centre is not read (it may hold NaN).  Data form with a stored matrix
+ *   (AA_ERR_STATE otherwise), single rank.  AA_ERR_ARG, the first offender named: G < 1 or G > AA_MAX_SLOTS, a
+ *   label outside [-1, G), a non-finite centre entry in a slot that a counted row uses.
+ * aa_set_data_rows_slots: aa_set_data_rows with Y[r][j] = (X[row0 + r][j] - shift[slot[r]][j]) / scale[slot[r]][j]:
+ *   one float64 subtraction and one true float64 division, nothing fused or approximated, rounded once to the
+ *   context's element type; either part is left out when its table is NULL, both NULL is refused.  slot: n host ints
+ *   in [0, G), one per row of the block; shift / scale: G x p host doubles.  Rows of the tables whose slot no row of
+ *   the block uses are not read (they may hold NaN).  AA_ERR_ARG like any other bad argument of an install, before
+ *   anything of ctx is released or launched: G < 1 or G > AA_MAX_SLOTS, a label outside [0, G), both tables NULL, a
+ *   non-finite shift or a zero or non-finite scale in a slot that a row of the block uses.  Otherwise the
+ *   preconditions and refusals of aa_set_data_rows. */
+#define AA_MAX_SLOTS 1464            /* 366 x 4: six-hourly steps of a leap year */
+#define AA_SLOT_CHUNK_ROWS 64        /* most rows of one slot a work item walks */
+#define AA_SLOT_TILE_COLS 256        /* adjacent columns of a work item: one 1024-byte run per row and vector */
+int aa_data_slot_sums(aa_ctx *ctx, int G, const int *slot, const double *centre, double *out, long *counts);
+int aa_set_data_rows_slots(aa_ctx *ctx, const aa_ctx *owner, long row0, long n, int G, const int *slot,
+                           const double *shift, const double *scale);
 
 /* Row gather on the device (seasonal subsets, k-fold splits, bootstrap resamples of a resident block, and the
  * support rows KernelAA.transform keeps, `X[support]`): rows idx[0..n) of owner's resident DATA matrix, in any
@@ -753,6 +786,10 @@ int aa_get_spg_scalars(aa_ctx *ctx, double *out);
  * its finish kernel where gram_plan splits, without the copy to the host (the side's d <= 8192); 20 = the projection
  * of aa_set_data_projected onto 167 components (a zero V) from the context's own matrix into a scratch block of the
  * context's element type; a stored data matrix is all they need.
+ * 21 = the per-slot sums of aa_data_slot_sums, 22 = their squared-deviation form (a zero centre table), both with
+ * their finish kernel and without the copies; 23 = the copy of aa_set_data_rows_slots with a shift table from the
+ * context's own matrix into a scratch copy; all three with the rows labelled r mod 366, and a stored data matrix is
+ * all they need.
  * ms_avg = average duration of one launch in milliseconds. */
 int aa_time_kernel(aa_ctx *ctx, int which, int reps, double *ms_avg);
 /* In-context timing of the two pass kernels: while enabled, every launch of the

@@ -14,8 +14,9 @@ from .simplex_projection import simplex_project_rows, simplex_project_columns
 from .spg import spg
 from .stochastic_matrices import left_stochastic_matrix, right_stochastic_matrix
 from ._backend import release_device_cache
-from .preprocessing import (ColumnScaling, ColumnStats, DeviceData, GroupScaling, GroupedColumnStats,
-                            SeasonalAnomalies, seasonal_coefficients, weight_and_flatten_on_device)
+from .preprocessing import (CalendarAnomalies, ColumnScaling, ColumnStats, DeviceData, GroupScaling,
+                            GroupedColumnStats, SeasonalAnomalies, calendar_smoother, seasonal_coefficients,
+                            weight_and_flatten_on_device)
 from .pca import ResidentPCA
 from .restarts import fit_restarts
 from .validation import KernelScores, Scores, time_series_cross_validate, time_series_folds
@@ -25,4 +26,5 @@ __all__ = ["ArchetypalAnalysis", "KernelAA", "GPNHConvexCoding", "furthest_sum",
            "left_stochastic_matrix", "right_stochastic_matrix", "release_device_cache",
            "DeviceData", "weight_and_flatten_on_device", "fit_restarts",
            "Scores", "KernelScores", "time_series_cross_validate", "time_series_folds", "ColumnStats", "ColumnScaling",
-           "seasonal_coefficients", "SeasonalAnomalies", "GroupedColumnStats", "GroupScaling", "ResidentPCA"]
+           "seasonal_coefficients", "SeasonalAnomalies", "GroupedColumnStats", "GroupScaling", "ResidentPCA",
+           "calendar_smoother", "CalendarAnomalies"]

@@ -21,6 +21,9 @@ MAX_K = 64
 GRAM_SIDES = ("rows", "cols")    # AA_GRAM_ROWS, AA_GRAM_COLS
 GRAM_MAX_D = 8192                # largest Gram matrix aa_data_gram forms (it goes through one host eigen-solve)
 MAX_PROJECTED = 256              # AA_MAX_PROJECTED: most directions of aa_set_data_projected
+MAX_SLOTS = 1464                 # AA_MAX_SLOTS: most calendar slots of aa_data_slot_sums / aa_set_data_rows_slots
+SLOT_CHUNK_ROWS = 64             # AA_SLOT_CHUNK_ROWS: most rows of one slot a work item of the slot kernels walks
+SLOT_TILE_COLS = 256             # AA_SLOT_TILE_COLS: adjacent columns of a work item
 DIAG_KINDS = ("given", "ones", "poly", "linear")     # AA_DIAG_*: where aa_kernel_sample_residuals takes kappa(y, y) from
 
 SPG_FLAG_CONVERGED = 1
@@ -131,6 +134,8 @@ _SIGNATURES = {
     "aa_data_grouped_sqdev": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _ip, _dp, ctypes.c_int, _dp]),
     "aa_set_data_rows_model": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _ip, _dp, _dp, _dp,
                                               _dp, _dp]),
+    "aa_data_slot_sums": (ctypes.c_int, [_vp, ctypes.c_int, _ip, _dp, _dp, ctypes.POINTER(ctypes.c_long)]),
+    "aa_set_data_rows_slots": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _ip, _dp, _dp]),
     "aa_data_gram": (ctypes.c_int, [_vp, ctypes.c_int, _dp, _dp, ctypes.c_long]),
     "aa_set_data_projected": (ctypes.c_int, [_vp, _vp, ctypes.c_long, ctypes.c_long, ctypes.c_int, _dp, ctypes.c_long,
                                              _dp]),
@@ -577,6 +582,29 @@ class Context(object):
                                                ptr[0], ptr[2], ptr[3], ptr[4], ptr[1]))
         self._adopt(n, owner.p)
 
+    def set_data_rows_slots(self, owner, row0, n, slots, shift=None, scale=None):
+        """``(owner[row0:row0 + n] - shift[slots]) / scale[slots]`` becomes this context's data matrix
+        (aa_set_data_rows_slots): the float64 roundings of that NumPy expression, one rounding to the context's
+        dtype.  ``slots``: n integers in ``[0, G)``, one per row of the block; ``shift`` / ``scale``: ``(G, p)``
+        tables, ``G <= MAX_SLOTS``, either may be None (part left out), not both.  Rows of the tables whose slot no
+        row of the block uses are not read."""
+        n = int(n)
+        tables = [None if a is None else _c64(a) for a in (shift, scale)]
+        if all(a is None for a in tables):
+            raise ValueError("a shift table, a scale table or both are needed")
+        G = max(a.shape[0] if a.ndim == 2 else 0 for a in tables if a is not None)
+        for a, name in zip(tables, ("shift", "scale")):
+            if a is not None and (a.ndim != 2 or a.shape != (G, owner.p)):
+                raise ValueError("%s: a (%d, %d) table expected, one row per slot; got shape %r"
+                                 % (name, G, owner.p, a.shape))
+        slots = np.ascontiguousarray(slots, dtype=np.intc)
+        if slots.shape != (n,):
+            raise ValueError("slots: %d labels expected, one per row; got shape %r" % (n, slots.shape))
+        ptr = [None if a is None else _ptr(a) for a in tables]
+        _check(self.lib.aa_set_data_rows_slots(self.h, owner.h, int(row0), n, G, slots.ctypes.data_as(_ip),
+                                               ptr[0], ptr[1]))
+        self._adopt(n, owner.p)
+
     def set_data_take(self, owner, indices=None):
         """Rows ``indices`` (any order, duplicates allowed; None: all rows in order) of ``owner``'s resident data
         matrix become this context's data matrix (aa_set_data_take): a device gather that owns its memory.  A
@@ -673,6 +701,27 @@ class Context(object):
         _check(self.lib.aa_data_grouped_sqdev(self.h, A.shape[0], _ptr(A), groups.ctypes.data_as(_ip), _ptr(centre),
                                               centre.shape[0], _ptr(out)))
         return out
+
+    def data_slot_sums(self, slots, n_slots, centre=None):
+        """``(sums, counts)`` of the resident data matrix per calendar slot (aa_data_slot_sums): ``sums[g] = sum of
+        X[t]`` over the rows with ``slots[t] == g``, or of ``(X[t] - centre[g]) ** 2`` with a ``(n_slots, p)`` table
+        ``centre``; ``slots``: n integers in ``[-1, n_slots)``, -1: row not counted; ``n_slots <= MAX_SLOTS``.
+        float64 arithmetic and a fixed summation order in both context dtypes.  A slot without counted rows has sums
+        exactly 0 and count 0, and its row of ``centre`` is not read.  Returns ``(n_slots, p)`` float64 and
+        ``(n_slots,)`` int64."""
+        G = int(n_slots)
+        slots = np.ascontiguousarray(slots, dtype=np.intc)
+        if slots.shape != (self.n,):
+            raise ValueError("slots: %d labels expected, one per row; got shape %r" % (self.n, slots.shape))
+        if centre is not None:
+            centre = _c64(centre)
+            if centre.shape != (G, self.p):
+                raise ValueError("centre: a (%d, %d) table expected; got shape %r" % (G, self.p, centre.shape))
+        out = np.empty((max(G, 0), self.p))
+        counts = np.zeros(max(G, 0), dtype=np.int64)
+        _check(self.lib.aa_data_slot_sums(self.h, G, slots.ctypes.data_as(_ip), None if centre is None else _ptr(centre),
+                                          _ptr(out), counts.ctypes.data_as(ctypes.POINTER(ctypes.c_long))))
+        return out, counts
 
     def data_gram(self, side, shift=None):
         """The Gram matrix of the resident data matrix, centred by ``shift`` (one value per column; None: not

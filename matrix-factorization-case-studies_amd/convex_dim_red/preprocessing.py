@@ -31,6 +31,13 @@ GroupedColumnStats = namedtuple("GroupedColumnStats", ("mean", "std", "counts"))
 # What ``DeviceData.standardized_by_group`` applied: the statistics, whether it centred, and the row labels.
 GroupScaling = namedtuple("GroupScaling", ("stats", "center", "groups"))
 
+# What a block made by ``DeviceData.calendar_anomalies`` had removed, as host arrays: ``climatology`` / ``scale``
+# (n_slots, n_features) float64 (``scale`` None without ``standardize``; rows of slots that had no base row hold NaN
+# unless ``harmonics`` filled the climatology), ``counts`` the base rows per slot, ``slots`` the block's row labels.
+CalendarAnomalies = namedtuple("CalendarAnomalies", ("n_slots", "base_rows", "harmonics", "climatology", "scale",
+                                                     "counts", "slots"))
+
+MAX_SLOTS = _backend.MAX_SLOTS   # calendar slots the slot-major device path takes (AA_MAX_SLOTS: 366 x 4)
 MAX_GROUPS = 16          # coefficient rows / groups one device pass takes (AA_MAX_COEF_ROWS)
 MAX_PERIOD = MAX_GROUPS - 2
 
@@ -127,6 +134,68 @@ def seasonal_coefficients(n, period, base_rows=None, trend_order=1):
     return np.vstack([cycle, slope, icpt]), np.vstack([cycle_parts, slope_parts, icpt_parts])
 
 
+def calendar_smoother(present, harmonics):
+    """Host only: the ``(G, G)`` float64 matrix ``S`` that smooths a per-slot table (a climatology by day or
+    six-hourly step of the year) and fills its empty slots: the least-squares projection onto a constant plus the
+    first ``harmonics`` annual harmonics ``cos(h theta_g), sin(h theta_g)``, ``theta_g = 2 pi g / G``, fitted over
+    the slots with ``present[g]`` and evaluated on all ``G`` -- ``S = B pinv(B[present])`` written into the present
+    columns, zero elsewhere, so ``S @ table`` never reads a row of an absent slot (a 29 February outside the base
+    period) and fills it from the fit.  ``present``: a non-empty 1-D boolean array; ``harmonics``: an integer >= 1
+    with ``2 harmonics + 1 <= present.sum()``.  Like ``seasonal_coefficients`` the model is an explicit matrix, so
+    the rounding of ``S @ table`` is bounded by ``(G + 2) u (|S| @ |table|)``."""
+    present = np.asarray(present)
+    if present.ndim != 1 or present.size < 1 or present.dtype != np.bool_:
+        raise ValueError("calendar_smoother: present must be a non-empty 1-D boolean array; got %s of shape %r"
+                         % (present.dtype, present.shape))
+    if not _is_int(harmonics) or harmonics < 1:
+        raise ValueError("calendar_smoother: harmonics must be an integer >= 1; got %r" % (harmonics,))
+    G, H, m = present.size, int(harmonics), int(present.sum())
+    if 2 * H + 1 > m:
+        raise ValueError("calendar_smoother: %d harmonics need %d slots with data; %d of %d have any"
+                         % (H, 2 * H + 1, m, G))
+    theta = 2.0 * np.pi * np.arange(G) / G
+    B = np.ones((G, 2 * H + 1))
+    for h in range(1, H + 1):
+        B[:, 2 * h - 1] = np.cos(h * theta)
+        B[:, 2 * h] = np.sin(h * theta)
+    S = np.zeros((G, G))
+    S[:, present] = B.dot(np.linalg.pinv(B[present]))
+    return S
+
+
+def _checked_slots(slots, n, n_slots, who):
+    """(labels as intc, number of slots) of one calendar-slot label per row, or ValueError."""
+    raw = np.asarray(slots)
+    if raw.ndim != 1 or raw.shape[0] != n:
+        raise ValueError("%s: one slot label per row (%d) expected; got shape %r" % (who, n, raw.shape))
+    if raw.dtype == np.bool_ or not np.issubdtype(raw.dtype, np.integer):
+        raise ValueError("%s: integer slot labels expected; got dtype %s" % (who, raw.dtype))
+    if raw.min() < 0:
+        raise ValueError("%s: slot labels start at 0; got %d" % (who, raw.min()))
+    if n_slots is None:
+        n_slots = int(raw.max()) + 1
+    elif not _is_int(n_slots) or n_slots < 1:
+        raise ValueError("%s: n_slots must be a positive integer; got %r" % (who, n_slots))
+    if n_slots > MAX_SLOTS:
+        raise ValueError("%s: n_slots = %d: more than %d slots" % (who, n_slots, MAX_SLOTS))
+    if raw.max() >= n_slots:
+        raise ValueError("%s: slot label %d with n_slots = %d" % (who, raw.max(), n_slots))
+    return raw.astype(np.intc), int(n_slots)
+
+
+def _checked_slot_table(table, n_slots, n_features, who):
+    table = np.asarray(table, dtype=np.float64)
+    if table.shape != (n_slots, n_features):
+        raise ValueError("%s must be (%d, %d), one row per slot; got shape %r" % (who, n_slots, n_features, table.shape))
+    return table
+
+
+def _first_bad(bad_mask, used):
+    """(slot, column) of the first True entry of ``bad_mask`` (n_slots, p) in a slot with ``used``, or None."""
+    bad = np.argwhere(bad_mask & used[:, None])
+    return None if bad.size == 0 else (int(bad[0][0]), int(bad[0][1]))
+
+
 def _checked_groups(groups, n, who):
     """(labels as intc, number of groups) of one label per row, or ValueError."""
     raw = np.asarray(groups)
@@ -199,12 +268,14 @@ class DeviceData(object):
     ``to_host()`` -- the matrix as float64 NumPy (downloaded once, then cached);
     ``scaling``  -- None, or the ``ColumnScaling`` a block made by ``standardized()`` was scaled with;
     ``anomaly``  -- None, or the ``SeasonalAnomalies`` model a block made by ``seasonal_anomalies()`` had removed;
-    ``group_scaling`` -- None, or the ``GroupScaling`` a block made by ``standardized_by_group()`` was scaled with.
+    ``group_scaling`` -- None, or the ``GroupScaling`` a block made by ``standardized_by_group()`` was scaled with;
+    ``calendar`` -- None, or the ``CalendarAnomalies`` record a block made by ``calendar_anomalies()`` had removed.
 
     Pass it as ``data`` to ``ArchetypalAnalysis.fit_transform / transform`` or
     ``GPNHConvexCoding.fit_transform``; ``close()`` (or ``with``) frees the device copy."""
 
-    def __init__(self, ctx, shape, valid, original_shape, scaling=None, anomaly=None, group_scaling=None):
+    def __init__(self, ctx, shape, valid, original_shape, scaling=None, anomaly=None, group_scaling=None,
+                 calendar=None):
         self._ctx = ctx
         self.shape = shape
         self.valid = valid
@@ -212,6 +283,7 @@ class DeviceData(object):
         self.scaling = scaling
         self.anomaly = anomaly
         self.group_scaling = group_scaling
+        self.calendar = calendar
         self.ndim = 2
         self._host = None
         self._stats = None
@@ -412,6 +484,117 @@ class DeviceData(object):
             raise
         return DeviceData(ctx, self.shape, self.valid, self.original_shape, self.scaling,
                           group_scaling=GroupScaling(stats, bool(center), labels))
+
+    def _slot_moments(self, counted, G, centre):
+        """(mean, counts) of the counted rows per slot, or with ``centre`` (root mean square about it, counts); NaN
+        where a slot has no counted row."""
+        sums, counts = self._ctx.data_slot_sums(counted, G, centre=centre)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            out = np.where(counts[:, None] > 0, sums / counts[:, None].astype(np.float64), np.nan)
+        return (out if centre is None else np.sqrt(out)), counts
+
+    def calendar_stats(self, slots, n_slots=None, rows=None, centre=None):
+        """``GroupedColumnStats(mean, std, counts)`` with ``(n_slots, n_features)`` tables: the column statistics of
+        each calendar slot, ``slots`` holding one integer label ``0 .. n_slots - 1`` per row (day of year, six-hourly
+        step of the year, pentad: the driver's time axis decides, leap days included), ``n_slots <= 1464`` (None:
+        the largest label + 1) -- ``groupby(time.dayofyear).mean() / .std()`` (ddof 0) for hundreds of groups, where
+        ``grouped_column_stats`` stops at 16.  ``rows = (lo, hi)`` counts only those rows, the base period.  ``std``
+        is ``sqrt(sum (x - c)^2 / count)`` about ``centre`` (an ``(n_slots, n_features)`` table), or without it about
+        the slot's own mean in a second sweep.  Slots without counted rows hold NaN and count 0.  Slot-major float64
+        sweeps over the resident matrix (aa_data_slot_sums).  Refusals are ``ValueError``s raised before any device
+        call, except a non-finite ``centre`` entry in a slot that has counted rows, which is one raised after the
+        first sweep."""
+        who = "DeviceData.calendar_stats"
+        n, p = self.shape
+        labels, G = _checked_slots(slots, n, n_slots, who)
+        lo, hi = _checked_row_range(rows, n, who + ": rows")
+        if centre is not None:
+            centre = _checked_slot_table(centre, G, p, who + ": centre")
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        counted = np.full(n, -1, dtype=np.intc)
+        counted[lo:hi] = labels[lo:hi]
+        mean, counts = self._slot_moments(counted, G, None)
+        if centre is not None:
+            bad = _first_bad(~np.isfinite(centre), counts > 0)
+            if bad:
+                raise ValueError("%s: centre[%d][%d] = %r is not finite" % ((who,) + bad + (centre[bad],)))
+        std, _ = self._slot_moments(counted, G, mean if centre is None else centre)
+        return GroupedColumnStats(mean, std, counts)
+
+    def calendar_anomalies(self, slots, n_slots=None, base_rows=None, harmonics=None, standardize=False, model=None):
+        """A new ``DeviceData`` (same device and dtype, a lifetime of its own) holding ``x - clim[g]`` with
+        ``g = slots[row]``, or ``(x - clim[g]) / scale[g]`` with ``standardize``: the deviations from a climatology
+        per calendar slot that the JRA-55 drivers read as ``.anom.`` / ``.std_anom.`` files, for up to 1464 slots
+        (``slots`` / ``n_slots`` as in ``calendar_stats``).  ``clim`` is the slot means over ``base_rows = (lo, hi)``
+        (None: all rows); with ``harmonics = H`` it is ``calendar_smoother(counts > 0, H) @ mean`` (empty slots
+        entering as 0 and filled from the fit).  ``scale[g]`` is the root mean square of ``x - clim[g]`` over the
+        slot's base rows: a second sweep, centred on the climatology that is actually subtracted.  ``model``: the
+        ``calendar`` record of another block (the training block's, for a validation or test block) to apply
+        instead; no statistics are taken then, and ``base_rows`` / ``harmonics`` beside it are refused.  Argument
+        refusals are ``ValueError``s raised before any device call; after the sums and before anything is copied, a
+        slot that a row of this block uses and whose climatology is not finite (no base row and no ``harmonics``) or
+        whose scale is zero or not finite is a ``ValueError`` that names slot and column.  ``valid``,
+        ``original_shape`` and ``scaling`` are inherited; ``calendar`` holds the ``CalendarAnomalies`` record (tied
+        to the row index: ``rows()`` and ``take()`` of the new block carry none).  Trends are not removed."""
+        who = "DeviceData.calendar_anomalies"
+        n, p = self.shape
+        S = None
+        if model is not None:
+            if not isinstance(model, CalendarAnomalies):
+                raise ValueError("%s: model must be a CalendarAnomalies record; got %r" % (who, type(model).__name__))
+            if base_rows is not None or harmonics is not None:
+                raise ValueError("%s: base_rows / harmonics belong to the block the model was taken from; "
+                                 "leave them out beside model" % who)
+            if n_slots is not None and n_slots != model.n_slots:
+                raise ValueError("%s: n_slots = %r, the model has %d" % (who, n_slots, model.n_slots))
+            labels, G = _checked_slots(slots, n, model.n_slots, who)
+            clim = _checked_slot_table(model.climatology, G, p, who + ": model.climatology")
+            scale = None
+            if standardize:
+                if model.scale is None:
+                    raise ValueError("%s: standardize needs a model with a scale (taken with standardize)" % who)
+                scale = _checked_slot_table(model.scale, G, p, who + ": model.scale")
+            lo, hi = model.base_rows
+            harmonics, counts = model.harmonics, model.counts
+        else:
+            labels, G = _checked_slots(slots, n, n_slots, who)
+            lo, hi = _checked_row_range(base_rows, n, who + ": base_rows")
+            if harmonics is not None:
+                if not _is_int(harmonics) or harmonics < 1:
+                    raise ValueError("%s: harmonics must be None or an integer >= 1; got %r" % (who, harmonics))
+                try:
+                    S = calendar_smoother(np.bincount(labels[lo:hi], minlength=G) > 0, harmonics)
+                except ValueError as e:
+                    raise ValueError("%s: harmonics: %s" % (who, e))
+        used = np.bincount(labels, minlength=G) > 0
+        if self._ctx is None or not self._ctx.h:
+            raise RuntimeError("DeviceData has been closed")
+        if model is None:
+            counted = np.full(n, -1, dtype=np.intc)
+            counted[lo:hi] = labels[lo:hi]
+            mean, counts = self._slot_moments(counted, G, None)
+            clim = mean if S is None else S.dot(np.where(np.isnan(mean), 0.0, mean))
+        bad = _first_bad(~np.isfinite(clim), used)
+        if bad:
+            raise ValueError("%s: the climatology of slot %d, column %d is %r: a row of the block uses the slot, no "
+                             "base row does and there are no harmonics to fill it" % ((who,) + bad + (clim[bad],)))
+        if model is None:
+            scale = self._slot_moments(counted, G, clim)[0] if standardize else None
+        if scale is not None:
+            bad = _first_bad(~np.isfinite(scale) | (scale == 0), used)
+            if bad:
+                raise ValueError("%s: the scale of slot %d, column %d is %r (zero or not finite); the division would "
+                                 "fill the column with inf / NaN" % ((who,) + bad + (scale[bad],)))
+        ctx = _backend.Context(dtype=self.dtype, device=self._ctx.device)
+        try:
+            ctx.set_data_rows_slots(self._ctx, 0, n, labels, shift=clim, scale=scale)
+        except Exception:
+            ctx.close()
+            raise
+        record = CalendarAnomalies(G, (lo, hi), None if harmonics is None else int(harmonics), clim, scale, counts,
+                                   labels)
+        return DeviceData(ctx, self.shape, self.valid, self.original_shape, self.scaling, calendar=record)
 
     def pca(self, n_components, center=True, side='auto'):
         """The ``ResidentPCA`` model of this block with ``n_components`` leading components: what

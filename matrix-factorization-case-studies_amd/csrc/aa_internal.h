@@ -26,6 +26,7 @@
 #include "../../include/aa_hip.h"
 #include "dict_plan.h"
 #include "gram_plan.h"
+#include "group_plan.h"
 #include "pass_plan.h"
 
 namespace aa {
@@ -490,6 +491,18 @@ int launch_col_weighted_sums(Ctx *c, int G, const double *At_dev /* n x 16 */, c
 int launch_model_rows(Ctx *c, const void *owner_X, long row0, const int *grp_dev, const double *shift_dev,
                       const double *icpt_dev, const double *slope_dev, const double *t_dev, const double *scale_dev,
                       void *dst = nullptr /* null: c->X; else a buffer of its layout (aa_time_kernel) */);
+// slot-major sums and copy for up to AA_MAX_SLOTS row labels (kernels_slots.hip) behind aa_data_slot_sums /
+// aa_set_data_rows_slots: a GroupPlan (group_plan.h) on the device -- rows: the row list by slot; chunks: (slot,
+// begin, len) per chunk; chunk_first: G + 1
+struct SlotPlanDev {
+    const int *rows, *chunks, *chunk_first;
+    long nchunk;
+    int G;
+};
+int launch_slot_sums(Ctx *c, const SlotPlanDev &pd, const double *centre_dev /* G x p_pad, nullable: plain sums */,
+                     double *partial_dev /* nchunk x p_pad */, double *out_dev /* G x p_pad */);
+int launch_slot_rows(Ctx *c, const void *owner_X, long row0, const SlotPlanDev &pd, const double *shift_dev,
+                     const double *scale_dev, void *dst = nullptr /* null: c->X; else a buffer of its layout */);
 // row gather behind aa_set_data_take (idx_dev null: the rows in order) and the float64 feature buffer of an
 // implicit kernel from a resident matrix; owner_dtype / owner_ld: element type and leading dimension of owner_X
 int launch_gather_rows(Ctx *c, const void *owner_X, int owner_dtype, long owner_ld, const long *idx_dev,

@@ -1288,6 +1288,115 @@ int aa_set_data_rows_model(aa_ctx *h, const aa_ctx *owner, long row0, long n, in
     return AA_OK;
 }
 
+// a GroupPlan on the device, one buffer of ints: rows | (slot, begin, len) per chunk | chunk_first
+static int upload_group_plan(Ctx *c, const GroupPlan &pl, ScopedDevBuf &buf, SlotPlanDev *pd)
+{
+    const size_t nr = pl.rows.size(), nc = (size_t)pl.chunks();
+    std::vector<int> host(nr + 3 * nc + pl.chunk_first.size());
+    std::copy(pl.rows.begin(), pl.rows.end(), host.begin());
+    for (size_t i = 0; i < nc; ++i) {
+        host[nr + 3 * i] = pl.chunk_slot[i];
+        host[nr + 3 * i + 1] = pl.chunk_begin[i];
+        host[nr + 3 * i + 2] = pl.chunk_len[i];
+    }
+    std::copy(pl.chunk_first.begin(), pl.chunk_first.end(), host.begin() + (long)(nr + 3 * nc));
+    AA_CHECK(buf.alloc(host.size() * sizeof(int)));
+    AA_CHECK_HIP(ctx_memcpy(c, buf.p, host.data(), host.size() * sizeof(int), hipMemcpyHostToDevice));
+    pd->rows = buf.as<int>();
+    pd->chunks = pd->rows + nr;
+    pd->chunk_first = pd->chunks + 3 * nc;
+    pd->nchunk = (long)nc;
+    pd->G = pl.G;
+    return AA_OK;
+}
+
+// Every entry of the rows of `table` (G x p) whose slot holds a row of the plan is finite (and, is_scale, not
+// zero); the other rows are not read.
+static int check_slot_table(const char *who, const char *name, const double *table, const GroupPlan &pl, long p,
+                            bool is_scale)
+{
+    for (int g = 0; table && g < pl.G; ++g) {
+        if (pl.start[(size_t)g + 1] == pl.start[(size_t)g]) continue;
+        const double *row = table + (size_t)g * p;
+        for (long j = 0; j < p; ++j)
+            AA_REQUIRE(row[j] - row[j] == 0.0 && !(is_scale && row[j] == 0.0), AA_ERR_ARG, "%s: %s[%d][%ld] = %g is %snot finite",
+                       who, name, g, j, row[j], is_scale ? "zero or " : "");
+    }
+    return AA_OK;
+}
+
+int aa_data_slot_sums(aa_ctx *h, int G, const int *slot, const double *centre, double *out, long *counts)
+{
+    AA_REQUIRE(h, AA_ERR_ARG, "null argument");
+    Ctx *c = &h->c;
+    AA_REQUIRE(has_stored_data(c), AA_ERR_STATE, "aa_data_slot_sums: no stored data matrix (data form)");
+    AA_REQUIRE(c->world == 1 && !c->force_comm, AA_ERR_ARG, "aa_data_slot_sums is single-rank");
+    AA_REQUIRE(G >= 1 && G <= AA_MAX_SLOTS, AA_ERR_ARG, "aa_data_slot_sums: %d slots (1 to %d are supported)", G,
+               AA_MAX_SLOTS);
+    AA_REQUIRE(slot && out, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(c->n < (1L << 31), AA_ERR_ARG, "aa_data_slot_sums: %ld rows (fewer than 2^31 are supported)", c->n);
+    const long bad = group_plan_first_bad_label(slot, c->n, G, -1);
+    AA_REQUIRE(bad < 0, AA_ERR_ARG, "aa_data_slot_sums: slot[%ld] = %d is outside [-1, %d)", bad, slot[bad], G);
+    const GroupPlan pl = group_plan(slot, c->n, G, AA_SLOT_CHUNK_ROWS);
+    AA_CHECK(check_slot_table("aa_data_slot_sums", "centre", centre, pl, c->p, false));
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    AA_CHECK(join_side(c));
+    ScopedDevBuf meta, dcen, partial, sums;
+    SlotPlanDev pd;
+    AA_CHECK(upload_group_plan(c, pl, meta, &pd));
+    AA_CHECK(partial.alloc((size_t)pl.chunks() * c->p_pad * sizeof(double)));
+    AA_CHECK(sums.alloc((size_t)G * c->p_pad * sizeof(double)));
+    if (centre) {
+        AA_CHECK(dcen.alloc((size_t)G * c->p_pad * sizeof(double)));      // zero filled: the padding columns stay zero
+        AA_CHECK_HIP(ctx_memcpy2d(c, dcen.p, (size_t)c->p_pad * sizeof(double), centre, (size_t)c->p * sizeof(double),
+                                  (size_t)c->p * sizeof(double), (size_t)G, hipMemcpyHostToDevice));
+    }
+    AA_CHECK(launch_slot_sums(c, pd, centre ? dcen.as<double>() : (const double *)nullptr, partial.as<double>(),
+                              sums.as<double>()));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    AA_CHECK_HIP(ctx_memcpy2d(c, out, (size_t)c->p * sizeof(double), sums.p, (size_t)c->p_pad * sizeof(double),
+                              (size_t)c->p * sizeof(double), (size_t)G, hipMemcpyDeviceToHost));
+    for (int g = 0; counts && g < G; ++g) counts[g] = (long)pl.start[(size_t)g + 1] - pl.start[(size_t)g];
+    return AA_OK;
+}
+
+int aa_set_data_rows_slots(aa_ctx *h, const aa_ctx *owner, long row0, long n, int G, const int *slot,
+                           const double *shift, const double *scale)
+{
+    AA_CHECK(check_owner(h, owner, "aa_set_data_rows_slots", AA_ERR_ARG, DTYPE_SAME));
+    Ctx *c = &h->c;
+    const Ctx *o = &owner->c;
+    AA_REQUIRE(row0 >= 0 && n >= 1 && n <= o->n && row0 <= o->n - n, AA_ERR_ARG, "bad row block [%ld, %ld) of %ld", row0,
+               row0 + n, o->n);
+    // refused before anything of ctx is released: too many slots, no table, a label without a table row, a
+    // non-finite shift or a zero or non-finite divisor in a slot that a row of the block uses
+    AA_REQUIRE(slot, AA_ERR_ARG, "null argument");
+    AA_REQUIRE(G >= 1 && G <= AA_MAX_SLOTS, AA_ERR_ARG, "aa_set_data_rows_slots: %d slots (1 to %d are supported)", G,
+               AA_MAX_SLOTS);
+    AA_REQUIRE(shift || scale, AA_ERR_ARG, "aa_set_data_rows_slots: a shift table, a scale table or both are needed");
+    AA_REQUIRE(n < (1L << 31), AA_ERR_ARG, "aa_set_data_rows_slots: %ld rows (fewer than 2^31 are supported)", n);
+    const long bad = group_plan_first_bad_label(slot, n, G, 0);
+    AA_REQUIRE(bad < 0, AA_ERR_ARG, "aa_set_data_rows_slots: slot[%ld] = %d is outside [0, %d)", bad, slot[bad], G);
+    const GroupPlan pl = group_plan(slot, n, G, AA_SLOT_CHUNK_ROWS);
+    AA_CHECK(check_slot_table("aa_set_data_rows_slots", "shift", shift, pl, o->p, false));
+    AA_CHECK(check_slot_table("aa_set_data_rows_slots", "scale", scale, pl, o->p, true));
+    AA_CHECK_HIP(hipSetDevice(c->device));
+    const size_t row = (size_t)o->p_pad * sizeof(double), used = (size_t)o->p * sizeof(double);
+    ScopedDevBuf meta, dtab;                              // dtab: shift | scale, G x p_pad each
+    SlotPlanDev pd;
+    AA_CHECK(upload_group_plan(c, pl, meta, &pd));
+    AA_CHECK(dtab.alloc((size_t)2 * G * row));
+    double *shift_dev = shift ? dtab.as<double>() : nullptr;
+    double *scale_dev = scale ? dtab.as<double>() + (size_t)G * o->p_pad : nullptr;
+    if (shift) AA_CHECK_HIP(ctx_memcpy2d(c, shift_dev, row, shift, used, used, (size_t)G, hipMemcpyHostToDevice));
+    if (scale) AA_CHECK_HIP(ctx_memcpy2d(c, scale_dev, row, scale, used, used, (size_t)G, hipMemcpyHostToDevice));
+    AA_CHECK(install_begin(c, install_rows(n, o->p, o->p_pad)));
+    AA_CHECK(launch_slot_rows(c, o->X.p, row0, pd, shift_dev, scale_dev));
+    AA_CHECK_HIP(hipStreamSynchronize(c->stream));
+    install_commit(c);
+    return AA_OK;
+}
+
 int aa_set_data_weighted(aa_ctx *h, const void *raw, int host_dtype, long n_total, long p_full, long ld,
                          const double *col_weight, long row0, long n, unsigned char *valid, long *p_valid)
 {
@@ -2894,9 +3003,9 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     else if (which == 12)                        // either stored form (not has_stored_data), like aa_pass_reduce_rows
         AA_REQUIRE(c->have_data && !c->kernel.kind && c->Dt.p && c->groupFlags.p, AA_ERR_STATE,
                    "aa_time_kernel 12: a stored matrix and a problem size (aa_set_state or aa_pass_reduce_rows_flagged) first");
-    else if (which >= 13 && which <= 20)
+    else if (which >= 13 && which <= 23)
         AA_REQUIRE(has_stored_data(c) && c->world == 1 && !c->force_comm, AA_ERR_STATE,
-                   "aa_time_kernel 13 .. 20: a stored data matrix (data form), single rank");
+                   "aa_time_kernel 13 .. 23: a stored data matrix (data form), single rank");
     else
         AA_REQUIRE(has_stored_data(c) && c->have_state, AA_ERR_STATE, "aa_time_kernel: needs data-form state on a stored matrix");
     AA_CHECK_HIP(hipSetDevice(c->device));
@@ -2965,6 +3074,25 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
         rc = proj_v.alloc((size_t)project_v_rows(AA_TIME_PROJECTED) * c->p_pad * sizeof(double));
         if (rc == AA_OK) rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * proj_ld * esize(c));
     }
+    // 21 .. 23: the slot-major kernels with the rows labelled r mod 366; 22: a zero centre table; 23: a zero shift
+    // table, into a scratch copy
+    enum { AA_TIME_SLOTS = 366 };
+    ScopedDevBuf slot_meta, slot_tab, slot_partial;
+    SlotPlanDev spd = {};
+    if (which >= 21 && which <= 23 && rc == AA_OK) {
+        if (c->n >= (1L << 31)) {
+            set_error("aa_time_kernel %d: %ld rows (fewer than 2^31 are supported)", which, c->n);
+            rc = AA_ERR_ARG;
+        }
+        std::vector<int> lab(rc == AA_OK ? (size_t)c->n : 0);
+        for (size_t r = 0; r < lab.size(); ++r) lab[r] = (int)(r % AA_TIME_SLOTS);
+        const GroupPlan pl = group_plan(lab.data(), (long)lab.size(), AA_TIME_SLOTS, AA_SLOT_CHUNK_ROWS);
+        if (rc == AA_OK) rc = upload_group_plan(c, pl, slot_meta, &spd);
+        if (rc == AA_OK) rc = slot_tab.alloc((size_t)AA_TIME_SLOTS * c->p_pad * sizeof(double));
+        if (rc == AA_OK && which != 23)
+            rc = slot_partial.alloc((size_t)(pl.chunks() + AA_TIME_SLOTS) * c->p_pad * sizeof(double));
+        if (rc == AA_OK && which == 23) rc = scratch.alloc((size_t)(c->n_pad + AA_SLACK_ROWS) * c->p_pad * esize(c));
+    }
     // one untimed launch first
     for (int phase = 0; phase < 2 && rc == AA_OK; ++phase) {
         const int nrep = phase == 0 ? 1 : reps;
@@ -3004,6 +3132,11 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
             else if (which == 20)
                 rc = launch_project_rows(c, c->X.p, c->dtype, c->p_pad, c->p, 0, c->n, AA_TIME_PROJECTED,
                                          proj_v.as<double>(), zshift.as<double>(), scratch.p, proj_ld, c->dtype);
+            else if (which == 21 || which == 22)
+                rc = launch_slot_sums(c, spd, which == 22 ? slot_tab.as<double>() : nullptr, slot_partial.as<double>(),
+                                      slot_partial.as<double>() + (size_t)spd.nchunk * c->p_pad);
+            else if (which == 23)
+                rc = launch_slot_rows(c, c->X.p, 0, spd, slot_tab.as<double>(), nullptr, scratch.p);
             else {
                 set_error("aa_time_kernel: unknown kernel %d", which);
                 rc = AA_ERR_ARG;
@@ -3023,7 +3156,7 @@ int aa_time_kernel(aa_ctx *h, int which, int reps, double *ms_avg)
     }
     (void)hipEventDestroy(e0);
     (void)hipEventDestroy(e1);
-    if (which >= 13 && which <= 20) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
+    if (which >= 13 && which <= 23) (void)hipStreamSynchronize(c->stream);   // the scratch buffers go
     return rc;
 }
 
